@@ -58,16 +58,18 @@ def parse_args():
                          "every rank owns a shard of that size (weak scaling)")
     ap.add_argument("--wide-sums", action="store_true", help="N > 1, sliced merge: exchange the sums as 21 plain planes (168 B per position) instead of the 14 packed ones (112 B)")
     ap.add_argument("--no-e2e", action="store_true", help="skip the end-to-end leg (ASEQ text on disk -> tables / calls through the command lines)")
-    ap.add_argument("--sustained", type=int, default=2000, help="passes of the sustained-rate block after the timed region (0 = skip)")
-    ap.add_argument("--cold-batches", type=int, default=3, help="N = 1: distinct resident batches the cold-HBM block rotates over after the timed region "
-                    "(no pass finds its inputs in the Infinity Cache); 0 or 1 = skip")
+    ap.add_argument("--sustained", type=int, default=None, help="passes of the sustained-rate block after the timed region (0 = skip; default: "
+                    "2000 with --full, else 0)")
+    ap.add_argument("--cold-batches", type=int, default=None, help="N = 1: distinct resident batches the cold-HBM block rotates over after the timed region "
+                    "(no pass finds its inputs in the Infinity Cache); 0 or 1 = skip (default: 3 with --full, else 0)")
     ap.add_argument("--ranges", type=int, default=2, help="N = 1: position ranges on concurrent streams INSIDE the library (ampli_set_ranges): "
                     "error_estimate and poisson_call cut the panel into this many tile-aligned ranges, each on a stream of its own, so that "
                     "back-to-back passes fill each other's partly filled rounds of workgroups.  1 = every launch whole, on one stream")
     ap.add_argument("--no-split-ranges", dest="split_ranges", action="store_false", help="the same as --ranges 1: the timed region on one stream, "
                     "per-kernel HIP events around undisturbed launches (what rounds 1-4 timed)")
-    ap.add_argument("--whole-rounds", type=int, default=4, help="N = 1: after the timed region, time the dominant reduce kernel on a panel of this many "
-                    "whole rounds of resident workgroups (what the partly filled last round of the configuration costs); 0 = skip")
+    ap.add_argument("--whole-rounds", type=int, default=None, help="N = 1: after the timed region, time the dominant reduce kernel on a panel of this many "
+                    "whole rounds of resident workgroups (what the partly filled last round of the configuration costs); 0 = skip (default: 4 with "
+                    "--full, else 0)")
     ap.add_argument("--cpu-baseline-full", action="store_true", help="time the reference's error estimation on ALL normals of config 3 (~6 min on one core)")
     ap.add_argument("--e2e", default=None, choices=list(CONFIGS), help="ONLY the end-to-end leg of that configuration, nothing else: its files written as ASEQ text, "
                     "both executables with their phase clocks, the reference's error estimation on a 6-file sample.  Opt-in because of its size "
@@ -99,7 +101,19 @@ def parse_args():
     ap.add_argument("--check", action="store_true", help="N>1: verify the merged table against a single-pass reduction of all shards")
     ap.add_argument("--no-strong-base", action="store_true", help="N>1, strong scaling: skip the one-GPU timing of the whole job on rank 0 "
                     "(strong_base / efficiency in the line)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true", help="everything behind the timed region as well: the CPU baseline, the end-to-end leg, the other "
+                    "record layouts, the one-stream pass, the sustained / cold-HBM / whole-rounds / shard-projection blocks, the copy ceiling, the "
+                    "separate poisson_call and all-scores timings, and at N > 1 the single-batch latency, collectives, tumour shard and one-GPU "
+                    "base.  Without it the run sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last timed step computed (error "
+                    "table, call mask, call list) as DIR/<name>.npy in float32 / float64; arrays beyond the size budget as a fixed, seeded sample")
+    args = ap.parse_args()
+    for name, full_default in (("sustained", 2000), ("cold_batches", 3), ("whole_rounds", 4)):
+        if getattr(args, name) is None:
+            setattr(args, name, full_default if args.full else 0)
+    if not args.full:
+        args.no_e2e = args.no_cpu_baseline = args.no_shard_projection = args.no_strong_base = True
+    return args
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -395,6 +409,32 @@ def kernel_source_sha():
     for f in ("ampli_kernels.hip", "ampli_math.h"):
         h.update(open(os.path.join(ROOT, "amplisolve_amd", "csrc", f), "rb").read())
     return h.hexdigest()
+
+
+DUMP_BUDGET_BYTES = 60 * 1000 * 1000  # --dump-outputs writes at most this much (under 64 MB)
+DUMP_SAMPLE_SEED = 0x5EED
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: each (name, numpy array) as d/<name>.npy, integers and float32 as float32, float64 as float64.  Arrays are
+    written whole in the order given while the budget lasts; one that no longer fits is written as a fixed, seeded sample of its
+    flattened elements (<name>.npy) beside the flat indices of that sample (<name>_index.npy, float64), the same for every run
+    with the same arguments."""
+    import numpy as np
+
+    os.makedirs(d, exist_ok=True)
+    left = DUMP_BUDGET_BYTES
+    for i, (name, a) in enumerate(arrays):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        share = left // (len(arrays) - i)  # what this array may take so that every later one still gets an equal share
+        if a.nbytes > share:
+            n = max(1, share // (a.itemsize + 8))
+            idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(a.size, size=min(n, a.size), replace=False))
+            np.save(os.path.join(d, f"{name}_index.npy"), idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+            left -= idx.size * 8
+        np.save(os.path.join(d, f"{name}.npy"), a)
+        left -= a.nbytes
 
 
 # ----------------------------------------------------------------------------------------------------
@@ -827,6 +867,25 @@ def main():
         t_red = sum(ctx.elapsed_ms(ev[i][0], ev[i][1]) for i in ev_steps) / len(ev_steps)
         t_call_main = sum(ctx.elapsed_ms(ev[i][2], ev[i][3]) for i in ev_steps) / len(ev_steps)  # main-stream part (all of it unless --async-drain)
     ctx.wait_calls()
+    if args.dump_outputs and rank == 0:
+        import numpy as np
+
+        # what the caller of the timed path holds after its last step, copied before anything below runs the kernels again
+        if lanes is not None:
+            lc, lf, lr = lanes[(args.steps - 1) % len(lanes)]
+            lc.wait_calls()
+            d_fin, d_res = lf, lr
+        else:
+            d_fin, d_res = fin, dict(call_mask=call_mask, calls_buf=calls_buf, n_calls=n_calls, capacity=cap)
+        torch.cuda.synchronize()
+        d_calls = (lanes[(args.steps - 1) % len(lanes)][0] if lanes is not None else ctx).read_calls(d_res)
+        dump_outputs(args.dump_outputs, [("error_table_rate", d_fin.rate.cpu().numpy()), ("error_table_thr", d_fin.thr.cpu().numpy()),
+                  ("error_table_code", d_fin.code.cpu().numpy()), ("error_table_germ_val", d_fin.germ_val.cpu().numpy()),
+                  ("error_table_germ_present", d_fin.germ_present.cpu().numpy()),
+                  # the call list in the reference's emission order (read_calls sorts it), one row per call, one column per field
+                  ("calls", np.stack([d_calls[f].astype(np.float64) for f in d_calls.dtype.names], axis=1) if len(d_calls)
+                   else np.zeros((0, len(d_calls.dtype.names)), np.float64)),
+                  ("call_mask", d_res["call_mask"].cpu().numpy())])
     if lanes is not None:
         n_calls, fin = lanes[0][2]["n_calls"], lanes[0][1]
     n_found = int(n_calls[::CALL_COUNTER_STRIDE].sum().item())
@@ -840,22 +899,25 @@ def main():
             n_borderline = None
     # the whole poisson_call (stream + drain kernels back to back), outside the timed region
     ctx.set_async_drain(False)
-    e0, e1 = ctx.event(), ctx.event()
-    ctx.record(e0)
-    for _ in range(5):
-        ctx.poisson_call(tumours, P, fin.thr, ref_code, 100, mode=mode, call_mask=call_mask, capacity=cap, calls_buf=calls_buf, n_calls=n_calls)
-    ctx.record(e1)
-    t_call_sep = ctx.elapsed_ms(e0, e1) / 5
+    t_call_sep = t_call_full = None
+    if args.full or args.async_drain:
+        e0, e1 = ctx.event(), ctx.event()
+        ctx.record(e0)
+        for _ in range(5):
+            ctx.poisson_call(tumours, P, fin.thr, ref_code, 100, mode=mode, call_mask=call_mask, capacity=cap, calls_buf=calls_buf, n_calls=n_calls)
+        ctx.record(e1)
+        t_call_sep = ctx.elapsed_ms(e0, e1) / 5
     # without --async-drain the whole call sits on the main stream and the in-region HIP events are the measurement
     t_call = t_call_sep if args.async_drain else t_call_main
-    # validation mode, outside the timed region: all six scores of every record, as the reference evaluates them
-    e0, e1 = ctx.event(), ctx.event()
-    n_calls.zero_()
-    ctx.record(e0)
-    for _ in range(3):
-        ctx.poisson_call(tumours, P, fin.thr, ref_code, 100, mode=POISSON_FULL, call_mask=call_mask)
-    ctx.record(e1)
-    t_call_full = ctx.elapsed_ms(e0, e1) / 3
+    if args.full:
+        # validation mode, outside the timed region: all six scores of every record, as the reference evaluates them
+        e0, e1 = ctx.event(), ctx.event()
+        n_calls.zero_()
+        ctx.record(e0)
+        for _ in range(3):
+            ctx.poisson_call(tumours, P, fin.thr, ref_code, 100, mode=POISSON_FULL, call_mask=call_mask)
+        ctx.record(e1)
+        t_call_full = ctx.elapsed_ms(e0, e1) / 3
     flags = int(fin.flags.item())
     if flags != 0:
         raise SystemExit("error_finalize reported an exactness-envelope violation")
@@ -881,7 +943,8 @@ def main():
     t_local_ms = None
     coll_ms, coll_bytes, strong_base = None, None, None
     single_batch_ms = None
-    if multi:
+    tumour_shard = None
+    if multi and args.full:
         # ONE batch with nothing else in flight: reduce -> exchange -> finalize of the slice -> all-gather -> poisson_call, host
         # clock around it, the slowest rank's figure.  What a single cohort through the command lines sees (their pipeline has
         # no other batch to hide the collectives behind); ms_per_step above is the pipelined throughput.
@@ -1102,7 +1165,7 @@ def main():
     # round costs (tools/sweep_tiles.py).  Outside the timed region; N = 1 only.
     # the practical ceiling beside the spec: a plain device-to-device copy of 1 GiB on this box, read + written bytes per second
     copy_ceiling = None
-    if not multi and lanes is None:
+    if not multi and lanes is None and args.full:
         try:
             nbytes = 1 << 30
             src_c, dst_c = torch.empty(nbytes, dtype=torch.uint8, device=ctx.device), torch.empty(nbytes, dtype=torch.uint8, device=ctx.device)
@@ -1158,7 +1221,7 @@ def main():
     # With position ranges in the timed region, the same pass once more WITHOUT them: every launch whole, on one stream, HIP events
     # around every kernel of every pass -- what rounds 1-4 timed, and the undisturbed kernel durations beside the overlapped ones.
     one_stream = None
-    if n_ranges > 1:
+    if n_ranges > 1 and args.full:
         try:
             ev1 = [[ctx.event() for _ in range(3)] for _ in range(args.steps)]
             for _ in range(max(2, args.warmup)):
@@ -1201,7 +1264,7 @@ def main():
             print(f"bench.py: the one_stream block failed: {exc}", file=sys.stderr)
 
     others = []
-    for name in [n for n in ("i32", "u24", "u16") if n in packed and n != layout and not multi and lanes is None]:
+    for name in [n for n in ("i32", "u24", "u16") if n in packed and n != layout and not multi and lanes is None and args.full]:
         # the same workload in the other record layouts, outside the timed region, for comparison
         an, at = packed[name]
         c2 = Context(dev_index)
@@ -1272,7 +1335,8 @@ def main():
                                  "launches (roofline_overlapped, roofline_pass)")
             else:  # no undisturbed measurement: the overlapped launches it is
                 red_bytes, call_bytes = red_bytes / n_ranges, call_bytes / n_ranges
-                roof_measured = "HIP events on each range's stream over the timed region (overlapping launches; the one_stream block failed)"
+                roof_measured = ("HIP events on each range's stream over the timed region (overlapping launches; " +
+                                 ("the one_stream block failed)" if args.full else "the one_stream block runs under --full)"))
         if t_red >= t_call:
             dom, dom_ms, dom_bytes = red_name, t_red, red_bytes
         else:
@@ -1363,15 +1427,16 @@ def main():
             fk = next((v for k, v in pm["kernels"].items() if f"poisson_full_kernel<{lay}>" in k and "fp64_wave_instructions" in v), None) if traffic_src else None
         except Exception:  # noqa: BLE001
             fk = None
-        out["roofline_fp64"] = {"bound": "fp64 vector issue", "kernel": f"poisson_full_kernel<{lay}> (all six scores of every record)", "avg_ms": t_call_full,
-                                "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
-                                "achieved": (fk["fp64_flops_if_all_lanes_active"] / (t_call_full * 1e-3) / 1e12) if fk else None,
-                                "frac": (fk["fp64_flops_if_all_lanes_active"] / (t_call_full * 1e-3) / 1e12 / FP64_PEAK_TFLOPS) if fk else None,
-                                "fp64_wave_instructions_per_launch": fk["fp64_wave_instructions"] if fk else None,
-                                "issue_slot_frac": (fk["fp64_wave_instructions"] * 4 / (1024 * 2.4e9 * t_call_full * 1e-3)) if fk else None,
-                                "hbm_frac_of_the_same_launch": call_bytes / (t_call_full * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                "source": "SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 of profiles/*/pmc_summary.json (offline, same kernel source)" if fk else
-                                          "no FP64 counters for this kernel source under profiles/ (run tools/collect_profiles.sh)"}
+        if t_call_full is not None:
+            out["roofline_fp64"] = {"bound": "fp64 vector issue", "kernel": f"poisson_full_kernel<{lay}> (all six scores of every record)", "avg_ms": t_call_full,
+                                    "peak": FP64_PEAK_TFLOPS, "unit": "TFLOP/s",
+                                    "achieved": (fk["fp64_flops_if_all_lanes_active"] / (t_call_full * 1e-3) / 1e12) if fk else None,
+                                    "frac": (fk["fp64_flops_if_all_lanes_active"] / (t_call_full * 1e-3) / 1e12 / FP64_PEAK_TFLOPS) if fk else None,
+                                    "fp64_wave_instructions_per_launch": fk["fp64_wave_instructions"] if fk else None,
+                                    "issue_slot_frac": (fk["fp64_wave_instructions"] * 4 / (1024 * 2.4e9 * t_call_full * 1e-3)) if fk else None,
+                                    "hbm_frac_of_the_same_launch": call_bytes / (t_call_full * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                    "source": "SQ_INSTS_VALU_{ADD,MUL,FMA,TRANS}_F64 of profiles/*/pmc_summary.json (offline, same kernel source)" if fk else
+                                              "no FP64 counters for this kernel source under profiles/ (run tools/collect_profiles.sh)"}
         if others:
             out["other_record_layouts"] = others
         if sustained:
@@ -1388,7 +1453,7 @@ def main():
             out["one_stream"] = one_stream
         if multi:
             out["communication"] = {"backend": dist.get_backend(), "world_size": dist.get_world_size(), "merge": args.merge,
-                                    "local_step_ms": t_local_ms, "exposed_ms_per_step": max(0.0, ms_per_step - t_local_ms),
+                                    "local_step_ms": t_local_ms, "exposed_ms_per_step": max(0.0, ms_per_step - t_local_ms) if t_local_ms is not None else None,
                                     "bytes_received_per_rank_and_step": coll_bytes,
                                     "collective_ms_per_round": coll_ms, "batches_per_round": (G if sliced else 1),
                                     "single_batch_latency_ms": single_batch_ms,

@@ -1,11 +1,115 @@
 """Shared test helpers (host-side synthetic panels through the product's host library)."""
+import contextlib
 import ctypes as C
+import gzip
+import os
 
 import numpy as np
 
 from amplisolve_amd import host_lib
 
 SEED = 0xA3F15017
+
+# ---- fixtures under tests/golden/, wherever the checkout lies ----
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+LIST_AS = "AMPLISOLVE_LIST_DIR_AS"
+# The order a directory's files are visited in is the iteration order of a hash map keyed by <directory string>/<file name> (EE:794-841,
+# VC:580-627), and the expected outputs under tests/golden/ were generated with the files under another directory string.  What they
+# depend on is that ORDER, recorded beside them: per fixture directory (relative to its root), the file that lists it.
+ORDER_FILES = {
+    "golden": {"toy_subset/NORMAL": "toy_subset/expected_visit_order.txt", "toy_subset/TUMOUR": "vc_ref/toy_subset_TUMOUR.order",
+               "mini_edge/NORMAL": "mini_edge/expected_visit_order.txt", "irregular/NORMAL": "irregular/expected_visit_order.txt"},
+    "toy_data": {"NORMAL_ASEQ_DIR": "toy/visit_order.txt", "TUMOUR_ASEQ_DIR": "toy/tumour_visit_order.txt"},
+}
+_ALIASES = {}
+
+
+def recorded_order(rel, name="golden"):
+    """the sample names of fixture directory `rel` in the order the outputs of tests/golden/ were generated with"""
+    with open(os.path.join(GOLDEN, ORDER_FILES[name][rel])) as f:
+        return [l.split()[0] for l in f if l.strip()]
+
+
+def recorded(path, root=GOLDEN, name="golden"):
+    """a directory string under which the host visits the files of fixture directory `path` (or of a copy of it) in the recorded order
+    (`path` itself for a directory that is not a fixture).  Found once per fixture directory among fixed candidate strings, with the
+    host's own sample_order as the judge: the key of a file is <string>/<file name> whatever directory the files lie in."""
+    from amplisolve_amd.hostio import sample_order
+
+    path = str(path)
+    if not path.startswith(str(root) + os.sep):
+        return path
+    rel = path[len(str(root)) + 1:]
+    if (name, rel) not in _ALIASES:
+        want = recorded_order(rel, name)
+        old = os.environ.get(LIST_AS)
+        try:
+            for k in range(100000):
+                os.environ[LIST_AS] = f"{name}-{k}/{rel}"
+                if sample_order(path) == want:
+                    _ALIASES[name, rel] = os.environ[LIST_AS]
+                    break
+            else:
+                raise AssertionError(f"no candidate directory string visits {rel} in the order {want}")
+        finally:
+            if old is None:
+                del os.environ[LIST_AS]
+            else:
+                os.environ[LIST_AS] = old
+    return _ALIASES[name, rel]
+
+
+def listed_as(path, root=GOLDEN, name="golden"):
+    """environment that makes the host visit a fixture directory's files in the recorded order (AMPLISOLVE_LIST_DIR_AS)"""
+    return {LIST_AS: recorded(path, root, name)}
+
+
+def cli_env(args, env=None):
+    """os.environ for a command line over fixture directories: the recorded order of its germline_dir= / tumour_dir= token (if
+    any), then the caller's own variables (which win)"""
+    e = dict(os.environ)
+    for a in args:
+        a = str(a)
+        if a.startswith(("germline_dir=", "tumour_dir=")):
+            e.update(listed_as(a.split("=", 1)[1]))
+    e.update(env or {})
+    return e
+
+
+@contextlib.contextmanager
+def listing(path, root=GOLDEN, name="golden"):
+    """in-process twin of listed_as: the host library reads AMPLISOLVE_LIST_DIR_AS from this process's environment"""
+    alias = listed_as(path, root, name)
+    old = os.environ.get(LIST_AS)
+    os.environ.update(alias)
+    try:
+        yield
+    finally:
+        if old is None:
+            del os.environ[LIST_AS]
+        else:
+            os.environ[LIST_AS] = old
+
+
+def golden_cohort(bed_or_table, aseq_dir=None, **kw):
+    """HostCohort over a fixture directory, its files visited in the recorded order"""
+    from amplisolve_amd.hostio import HostCohort
+
+    with listing(aseq_dir or ""):
+        return HostCohort(bed_or_table, aseq_dir, **kw)
+
+
+def toy_data(dst):
+    """the reference's Toy_data (panel BED, 5 normal and 3 tumour .PILEUP.ASEQ files), unpacked from tests/golden/toy_data/ into dst;
+    list its directories with listed_as(..., root=dst, name="toy_data")"""
+    src = os.path.join(GOLDEN, "toy_data")
+    for dirpath, _, files in os.walk(src):
+        out = os.path.join(str(dst), os.path.relpath(dirpath, src))
+        os.makedirs(out, exist_ok=True)
+        for f in files:
+            with open(os.path.join(out, f[:-3]), "wb") as o:
+                o.write(gzip.open(os.path.join(dirpath, f)).read())
+    return str(dst)
 
 
 def synth_recs(P, n, first=0, seed=SEED, depth=2000, tumour=False):

@@ -14,23 +14,30 @@ import pytest
 
 from amplisolve_amd.hostio import HostCohort, read_error_table
 from oracle import pyoracle as orc
-from tests.helpers import write_fresh_panel, write_fresh_tumours
+from tests.helpers import GOLDEN as G
+from tests.helpers import recorded_order, toy_data, write_fresh_panel, write_fresh_tumours
 from tests.test_panel_variants_vs_reference import _rename_chromosome, _vary
 
-G = "/root/repo/tests/golden"
 need_ref = pytest.mark.skipif(not (os.path.exists(orc.REF_VC_NOFISHER) and os.path.exists(orc.REF_EE_DRIVER)),
                               reason="oracle/_ref/AmpliSolveVariantCalling_noFisher is absent (make -C oracle where /root/reference exists)")
 
 
 @need_ref
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Toy_data"), reason="full Toy_data only exists in the build container")
-def test_reference_callvariants_without_fisher_reproduces_the_survey_digest(tmp_path):
+def test_reference_callvariants_without_fisher_reproduces_the_survey_digest(tmp_path, monkeypatch):
     """sha256 of the reference's Summary on Toy_data with columns 13-14 cut away, taken from a run of the whole
     program.  The build without the Fisher statements must give the same digest: what was left out touches nothing else."""
     import gzip
 
+    from amplisolve_amd.hostio import sample_order
+
     (tmp_path / "psn.txt").write_bytes(gzip.open(f"{G}/toy/positionSpecificNoise_0.0020.txt.gz").read())
-    r = subprocess.run([orc.REF_VC_NOFISHER, "errorFile=psn.txt", "tumour_dir=/root/reference/Toy_data/TUMOUR_ASEQ_DIR", "output_dir=o",
+    T = toy_data(tmp_path / "Toy_data")
+    want = recorded_order("TUMOUR_ASEQ_DIR", "toy_data")  # the order of the run the digest was taken from
+    # the reference keys its visit order by the directory string it is given: a relative spelling of the copy that hashes to that order
+    # (the host's sample_order keys the same container the same way)
+    monkeypatch.chdir(tmp_path)
+    tdir = next(t for t in ("./" * k + "Toy_data/TUMOUR_ASEQ_DIR" for k in range(64)) if sample_order(t) == want)
+    r = subprocess.run([orc.REF_VC_NOFISHER, "errorFile=psn.txt", f"tumour_dir={tdir}", "output_dir=o",
                         "coverage_cutoff=100", "p_value=0.05"], capture_output=True, text=True, cwd=tmp_path)
     assert r.returncode == 0, r.stdout[-500:]
     lines = (tmp_path / "o" / "Summary_Variant_Info.txt").read_text().splitlines()
@@ -39,7 +46,7 @@ def test_reference_callvariants_without_fisher_reproduces_the_survey_digest(tmp_
     assert hashlib.sha256(cut.encode()).hexdigest() == "4a324a65984ab3b296507a2dab7687b89d298aa87813d8e6edaab0d7deb5c13e"
     # the same call sequence with a clock around each step (bench.py's cpu_baseline) writes the same file
     (tmp_path / "o2" / "AmpliSolveVariantCalling_interm_files").mkdir(parents=True)
-    t = subprocess.run([orc.REF_VC_CALL_DRIVER, "time", "psn.txt", "/root/reference/Toy_data/TUMOUR_ASEQ_DIR", "o2", "100", "0.05"], capture_output=True, text=True, cwd=tmp_path)
+    t = subprocess.run([orc.REF_VC_CALL_DRIVER, "time", "psn.txt", tdir, "o2", "100", "0.05"], capture_output=True, text=True, cwd=tmp_path)
     assert t.returncode == 0 and "TIMING callVariants" in t.stderr
     assert (tmp_path / "o2" / "Summary_Variant_Info.txt").read_bytes() == (tmp_path / "o" / "Summary_Variant_Info.txt").read_bytes()
 

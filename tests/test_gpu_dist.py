@@ -44,7 +44,7 @@ def test_bench_strong_scaling_line_reports_the_tumour_shard(world):
     the single-cohort (unpipelined) one."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", free_port(), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "8", "--warmup", "3",
-           "--backend", "gloo", "--check", "--config", "c4s"]
+           "--backend", "gloo", "--check", "--config", "c4s", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -70,7 +70,7 @@ def test_bench_line_at_one_gpu_has_the_contract_fields():
     """`python bench.py` (N = 1) on the small configuration: ONE JSON line with the contract's fields, the roofline of the dominant
     kernel, and the self-checks of the blocks behind the timed region (layouts, the one-stream pass against the ranges') all true."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--config", "c2", "--steps", "6", "--warmup", "2", "--no-cpu-baseline", "--no-e2e",
-           "--sustained", "40", "--cold-batches", "2", "--whole-rounds", "1"]
+           "--sustained", "40", "--cold-batches", "2", "--whole-rounds", "1", "--full"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -97,3 +97,52 @@ def test_bench_line_at_one_gpu_has_the_contract_fields():
         assert abs(d["roofline"]["avg_ms"] - max(d["one_stream"]["error_reduce_ms"], d["one_stream"]["poisson_call_ms"])) < 1e-9
     assert 0 < d["roofline_pass"]["frac"] < 1
     assert d["sustained"]["passes"] == 40 and d["cold_hbm"]["batches"] == 2
+
+
+def test_plain_bench_line_and_its_dumped_outputs(tmp_path):
+    """Without --full the line still carries the contract's fields and times exactly --steps steps; --dump-outputs writes the last
+    timed step's outputs as float32 / float64 .npy files within the size budget, the same in two runs with the same arguments, and
+    the dumped error table / call mask are those of the same pass recomputed here."""
+    import numpy as np
+
+    runs = []
+    for k in range(2):
+        d = tmp_path / f"out{k}"
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--config", "c2", "--steps", "4", "--warmup", "1", "--dump-outputs", str(d)]
+        r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+        lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+        assert len(lines) == 1
+        line = json.loads(lines[0])
+        for key in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+            assert key in line, key
+        assert line["steps"] == 4 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert "cpu_baseline" not in line and "e2e" not in line and "sustained" not in line and "other_record_layouts" not in line
+        files = sorted(os.listdir(d))
+        assert {"error_table_thr.npy", "error_table_code.npy", "call_mask.npy", "calls.npy"} <= set(files)
+        assert sum(os.path.getsize(d / f) for f in files) <= 64 * 1000 * 1000
+        arrays = {f: np.load(d / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        runs.append(arrays)
+    assert runs[0].keys() == runs[1].keys()
+    for f in runs[0]:
+        assert np.array_equal(runs[0][f], runs[1][f]), f
+
+    import torch
+
+    from amplisolve_amd import Context
+    from bench import CONFIGS, SEED
+
+    cfg = CONFIGS["c2"]
+    P, S, T = cfg["P"], cfg["S"], cfg["T"]
+    c = Context(0)
+    try:
+        fin = c.error_estimate(c.synth_fill(P, S, seed=SEED, depth=cfg["depth"]), P, 0.002, 100)
+        res = c.poisson_call(c.synth_fill(P, T, seed=SEED, depth=cfg["depth"], tumour=True), P, fin.thr, c.synth_ref(P, seed=SEED), 100, capacity=1 << 20)
+        torch.cuda.synchronize()
+        assert np.array_equal(runs[0]["error_table_thr.npy"], fin.thr.cpu().numpy())
+        assert np.array_equal(runs[0]["error_table_code.npy"], fin.code.cpu().numpy().astype(np.float32))
+        assert np.array_equal(runs[0]["call_mask.npy"], res["call_mask"].cpu().numpy().astype(np.float32))
+        assert runs[0]["calls.npy"].shape[0] == c.n_calls_total(res)
+    finally:
+        c.close()

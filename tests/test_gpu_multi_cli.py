@@ -6,10 +6,13 @@ import sys
 
 import pytest
 
+from tests.helpers import GOLDEN as G
+from tests.helpers import cli_env, listed_as
+
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BIN = os.path.join(ROOT, "amplisolve_amd", "bin")
-G = "/root/repo/tests/golden"  # the goldens were taken with this directory literal (it decides the visit order, EE:794-841)
+# the goldens were taken under another directory string, which decides the visit order (EE:794-841): cli_env / listed_as replay it
 
 
 def free_port() -> int:
@@ -25,7 +28,7 @@ def torchrun(world, port, args, env=None):
     port = free_port()  # the callers' literals only tell the launches apart when reading a failure
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), "-m", "amplisolve_amd.multi"] + args
-    e = dict(os.environ, AMPLISOLVE_DIST_BACKEND="gloo", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), **(env or {}))
+    e = cli_env(args, dict(AMPLISOLVE_DIST_BACKEND="gloo", PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), **(env or {})))
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT, env=e)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     return r
@@ -85,7 +88,8 @@ def test_variant_calling_sharded_equals_one_process(tmp_path, world):
     table = f"{d}/expected_positionSpecificNoise_0.0020.txt"
     one = tmp_path / "one"
     r = subprocess.run([f"{BIN}/AmpliSolveVariantCalling", f"errorFile={table}", f"tumour_dir={d}/TUMOUR", f"output_dir={one}",
-                        "coverage_cutoff=100", "p_value=0.05"], capture_output=True, text=True, env=dict(os.environ, AMPLISOLVE_STRICT_EXIT="1"))
+                        "coverage_cutoff=100", "p_value=0.05"], capture_output=True, text=True, env=dict(os.environ, AMPLISOLVE_STRICT_EXIT="1",
+                                                                                                         **listed_as(f"{d}/TUMOUR")))
     assert r.returncode == 0, r.stdout + r.stderr
     out = tmp_path / "multi"
     torchrun(world, 29561 + world, ["AmpliSolveVariantCalling", f"errorFile={table}", f"tumour_dir={d}/TUMOUR", f"output_dir={out}",
@@ -149,7 +153,8 @@ def test_failing_shard_ends_the_job(tmp_path):
 def test_without_a_launcher_it_is_the_one_process_pipeline(tmp_path):
     d = f"{G}/toy_subset"
     out = tmp_path / "solo"
-    e = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), AMPLISOLVE_REFBASES_FILE=f"{d}/refbases.txt")
+    e = dict(os.environ, PYTHONPATH=ROOT + os.pathsep + os.environ.get("PYTHONPATH", ""), AMPLISOLVE_REFBASES_FILE=f"{d}/refbases.txt",
+             **listed_as(f"{d}/NORMAL"))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         e.pop(k, None)
     r = subprocess.run([sys.executable, "-m", "amplisolve_amd.multi", "AmpliSolveErrorEstimation", f"panel_design={d}/panel.bed",
@@ -169,7 +174,7 @@ def test_native_rccl_transport_both_command_lines_on_a_communicator_of_one(tmp_p
     out = tmp_path / "native"
     r = subprocess.run([f"{BIN}/AmpliSolveErrorEstimation", f"panel_design={d}/panel.bed", "reference_genome=unused.fa", f"germline_dir={d}/NORMAL",
                         "C_value=0.002", "coverage_cutoff=100", "default_error=0.01", f"output_dir={out}"], capture_output=True, text=True,
-                       timeout=300, env=env)
+                       timeout=300, env=dict(env, **listed_as(f"{d}/NORMAL")))
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert "shard 1/1" in r.stdout
     assert (out / "positionSpecificNoise_0.0020.txt").read_text() == open(f"{d}/expected_positionSpecificNoise_0.0020.txt").read()
@@ -179,7 +184,7 @@ def test_native_rccl_transport_both_command_lines_on_a_communicator_of_one(tmp_p
     one, nat = tmp_path / "one", tmp_path / "native_vc"
     for o, e in ((one, dict(os.environ, AMPLISOLVE_STRICT_EXIT="1")), (nat, env)):
         r = subprocess.run([f"{BIN}/AmpliSolveVariantCalling", f"errorFile={table}", f"tumour_dir={d}/TUMOUR", f"output_dir={o}",
-                            "coverage_cutoff=100", "p_value=0.05"], capture_output=True, text=True, timeout=300, env=e)
+                            "coverage_cutoff=100", "p_value=0.05"], capture_output=True, text=True, timeout=300, env=dict(e, **listed_as(f"{d}/TUMOUR")))
         assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     assert (nat / "Summary_Variant_Info.txt").read_text() == (one / "Summary_Variant_Info.txt").read_text()
     assert not [n for n in os.listdir(nat) if ".part" in n]
@@ -214,8 +219,8 @@ def native_run(world, exe, args, out, fake, env=None):
     os.makedirs(out, exist_ok=True)
     procs = []
     for k in range(world):
-        e = dict(os.environ, AMPLISOLVE_WORLD_SIZE=str(world), AMPLISOLVE_RANK=str(k), AMPLISOLVE_DEVICE="0", AMPLISOLVE_RCCL_LIB=fake,
-                 AMPLISOLVE_ID_FILE=os.path.join(str(out), "rendezvous.id"), AMPLISOLVE_RCCL_TIMEOUT="120", **(env or {}))
+        e = cli_env(args, dict(AMPLISOLVE_WORLD_SIZE=str(world), AMPLISOLVE_RANK=str(k), AMPLISOLVE_DEVICE="0", AMPLISOLVE_RCCL_LIB=fake,
+                               AMPLISOLVE_ID_FILE=os.path.join(str(out), "rendezvous.id"), AMPLISOLVE_RCCL_TIMEOUT="120", **(env or {})))
         procs.append(subprocess.Popen([f"{BIN}/{exe}"] + args + [f"output_dir={out}"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=e))
     outs = [p.communicate(timeout=600)[0] for p in procs]
     assert all(p.returncode == 0 for p in procs), "\n=====\n".join(o[-2000:] for o in outs)
@@ -260,14 +265,14 @@ def test_native_mode_several_ranks_variant_calling(tmp_path, fake_rccl, world):
     table = f"{d}/expected_positionSpecificNoise_0.0020.txt"
     one = tmp_path / "one"
     r = subprocess.run([f"{BIN}/AmpliSolveVariantCalling", f"errorFile={table}", f"tumour_dir={d}/TUMOUR", f"output_dir={one}", "coverage_cutoff=100", "p_value=0.05"],
-                       capture_output=True, text=True, env=dict(os.environ, AMPLISOLVE_STRICT_EXIT="1"))
+                       capture_output=True, text=True, env=dict(os.environ, AMPLISOLVE_STRICT_EXIT="1", **listed_as(f"{d}/TUMOUR")))
     assert r.returncode == 0, r.stdout + r.stderr
     out = tmp_path / "native"
     os.makedirs(out)
     procs = []
     for k in range(world):
         e = dict(os.environ, AMPLISOLVE_WORLD_SIZE=str(world), AMPLISOLVE_RANK=str(k), AMPLISOLVE_DEVICE="0", AMPLISOLVE_RCCL_LIB=fake_rccl,
-                 AMPLISOLVE_ID_FILE=str(out / "rendezvous.id"))
+                 AMPLISOLVE_ID_FILE=str(out / "rendezvous.id"), **listed_as(f"{d}/TUMOUR"))
         procs.append(subprocess.Popen([f"{BIN}/AmpliSolveVariantCalling", f"errorFile={table}", f"tumour_dir={d}/TUMOUR", f"output_dir={out}", "coverage_cutoff=100",
                                        "p_value=0.05"], stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, env=e))
     outs = [p.communicate(timeout=600)[0] for p in procs]

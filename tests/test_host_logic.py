@@ -239,14 +239,16 @@ def test_cohort_shards_partition_the_visit_order():
     for record (what every rank of amplisolve_amd.multi parses)."""
     from amplisolve_amd.dist import shard_range
 
-    d = "/root/repo/tests/golden/mini_edge"
-    whole = HostCohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
+    from tests.helpers import GOLDEN, golden_cohort
+
+    d = f"{GOLDEN}/mini_edge"
+    whole = golden_cohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
     S = whole.S
     assert whole.first_sample == 0 and whole.total_samples == S and S >= 5
     for n in (2, 3, S + 2):
         seen = []
         for k in range(n):
-            part = HostCohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt", shard=(k, n))
+            part = golden_cohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt", shard=(k, n))
             lo, hi = shard_range(S, k, n)
             assert (part.first_sample, part.S, part.total_samples) == (lo, hi - lo, S)
             assert part.names == whole.names[lo:hi]

@@ -13,9 +13,10 @@ import pytest
 
 from amplisolve_amd.hostio import HostCohort, read_error_table, sample_order
 from oracle import pyoracle as orc
+from tests.helpers import GOLDEN as G
+from tests.helpers import golden_cohort, listing, toy_data
 
-G = "/root/repo/tests/golden"  # literal: the sample visit order hashes the directory string
-pytestmark = pytest.mark.skipif(not os.path.isdir(G), reason="fixtures are addressed through the /root/repo path")
+# the sample visit order hashes the directory string: golden_cohort / listing replay the one the fixtures were made under
 
 
 def oracle_table(co, C, cov, tmp_path, name="t.txt"):
@@ -31,7 +32,7 @@ def oracle_table(co, C, cov, tmp_path, name="t.txt"):
                                             (0.01, 500, "expected_positionSpecificNoise_0.0100_cov500.txt")])
 def test_toy_subset_table_is_byte_identical(tmp_path, C, cov, expected):
     d = f"{G}/toy_subset"
-    co = HostCohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
+    co = golden_cohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
     assert co.names == open(f"{d}/expected_visit_order.txt").read().split()
     assert co.E > 0 and co.stats()["offpanel"] == 0
     _, _, got = oracle_table(co, C, cov, tmp_path)
@@ -41,7 +42,7 @@ def test_toy_subset_table_is_byte_identical(tmp_path, C, cov, expected):
 def test_toy_subset_integer_counts_match_reference(tmp_path):
     """Count_Hash of the reference (the integer quorum counts, EE:1665) == oracle cnt, key by key."""
     d = f"{G}/toy_subset"
-    co = HostCohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
+    co = golden_cohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
     acc = orc.error_reduce(co.recs, co.P, 0.002, 100, E=co.E, dup_off=co.dup_off)
     exp = dict(l.split() for l in open(f"{d}/expected_counts.txt"))
     assert len(exp) == 4 * co.P
@@ -56,7 +57,7 @@ def test_mini_edge_table_is_byte_identical(tmp_path, tag, C, cov):
     """Synthetic edge cases: absent lines, duplicated positions, FW or BW = 0 (NaN gate), depth around the cutoff,
     AF around 5 %, quorum edges, chrX / chrM, N and soft-masked reference bases."""
     d = f"{G}/mini_edge"
-    co = HostCohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
+    co = golden_cohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
     assert co.names == open(f"{d}/expected_visit_order.txt").read().split()
     acc, fin, got = oracle_table(co, C, cov, tmp_path)
     assert got == open(f"{d}/expected_positionSpecificNoise_{tag}.txt").read()
@@ -149,7 +150,7 @@ def test_error_table_reader_round_trip(tmp_path):
     """The same reader against the ORACLE's finalize (text round trip, 0.01 substitution): a self-consistency check beside
     the reference pin above."""
     d = f"{G}/toy_subset"
-    co = HostCohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
+    co = golden_cohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
     acc, fin, _ = oracle_table(co, 0.002, 100, tmp_path, "rt.txt")
     ref, thr = read_error_table(str(tmp_path / "rt.txt"))
     assert np.array_equal(ref, co.ref_code)
@@ -184,27 +185,40 @@ def test_sequence_context_against_the_reference_functions(tmp_path, name):
         assert flagged > 0
 
 
-def test_tumour_visit_order_against_the_reference(tmp_path):
+def test_tumour_visit_order_against_the_reference(tmp_path, monkeypatch):
     """a1, VC twin (VC:387-394, 580-627): the order callVariants visits the tumour files in (VC:672) is the iteration order
-    of the reference's own TumourFileList_Hash for the same directory literal."""
+    of the reference's own TumourFileList_Hash for the same directory string -- the recorded one replayed, and (where the reference
+    build is present) the reference's own walk of these files under a directory string of this run."""
+    import shutil
+    import subprocess
+
     want = [l.split("\t")[0] for l in open(f"{G}/vc_ref/toy_subset_TUMOUR.order").read().splitlines()]
-    assert sample_order(f"{G}/toy_subset/TUMOUR") == want and sorted(want) == ["T1", "T2", "T3"]
+    with listing(f"{G}/toy_subset/TUMOUR"):
+        assert sample_order(f"{G}/toy_subset/TUMOUR") == want and sorted(want) == ["T1", "T2", "T3"]
+    if os.path.exists(orc.REF_VC_DRIVER):
+        shutil.copytree(f"{G}/toy_subset/TUMOUR", tmp_path / "TUMOUR")
+        monkeypatch.chdir(tmp_path)
+        for t in ("TUMOUR", "./TUMOUR", str(tmp_path / "TUMOUR")):
+            r = subprocess.run([orc.REF_VC_DRIVER, "order", t, "list.txt"], capture_output=True, text=True, cwd=tmp_path)
+            assert r.returncode == 0
+            assert sample_order(t) == [l.split("\t")[0] for l in r.stdout.splitlines()]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Toy_data"), reason="full Toy_data only exists in the build container")
 def test_full_toy_data_digest(tmp_path):
     """Config 1 of BASELINE.json: the whole Toy_data panel, digest of the reference's table."""
-    T = "/root/reference/Toy_data"
+    T = toy_data(tmp_path / "Toy_data")
     refb = tmp_path / "refbases.txt"
     refb.write_bytes(gzip.open(f"{G}/toy/refbases.txt.gz").read())
-    co = HostCohort(f"{T}/AmpliSeq_30genes_Designed-1.bed", f"{T}/NORMAL_ASEQ_DIR", refbases_file=str(refb))
+    with listing(f"{T}/NORMAL_ASEQ_DIR", root=T, name="toy_data"):
+        co = HostCohort(f"{T}/AmpliSeq_30genes_Designed-1.bed", f"{T}/NORMAL_ASEQ_DIR", refbases_file=str(refb))
     assert co.names == open(f"{G}/toy/visit_order.txt").read().split()
     assert (co.P, co.walk_len, co.S) == (40814, 41486, 5)
     _, _, got = oracle_table(co, 0.002, 100, tmp_path)
     want = open(f"{G}/toy/digests.txt").read().split()[2]
     assert hashlib.sha256(got.encode()).hexdigest() == want == "ebb19204f4d1ca3020be3ee8b7457564c817f64c88166b11aa0f847ed826ba3a"
     assert got == gzip.open(f"{G}/toy/positionSpecificNoise_0.0020.txt.gz").read().decode()
-    assert sample_order(f"{T}/TUMOUR_ASEQ_DIR") == ["T3", "T2", "T1"]
+    with listing(f"{T}/TUMOUR_ASEQ_DIR", root=T, name="toy_data"):
+        assert sample_order(f"{T}/TUMOUR_ASEQ_DIR") == ["T3", "T2", "T1"]
 
 
 def test_scorer_against_reference_grid():
@@ -255,7 +269,7 @@ def test_irregular_lines_oracle_reproduces_the_reference_table():
     (tests/golden/irregular, generated by make_golden_irregular.py from the compiled reference)."""
     d = os.path.join(G, "irregular")
     for tag, C_value, cov in (("0.0020_cov100", 0.002, 100), ("0.0100_cov1", 0.01, 1)):
-        co = HostCohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
+        co = golden_cohort(f"{d}/panel.bed", f"{d}/NORMAL", refbases_file=f"{d}/refbases.txt")
         assert co.names == open(f"{d}/expected_visit_order.txt").read().split()
         rd = co.rd_plane()
         assert rd is not None and (rd != np.iinfo(np.int32).min).sum() == co.stats()["irregular"] == 383

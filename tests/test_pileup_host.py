@@ -40,12 +40,13 @@ def test_oracle_known_answer_columns(tmp_path):
                                  "chr1\t103\t.\t.\t.\t.\t0\t0\t2\t0\t2\t0\t0\t1\t0", "chr1\t103\t.\t.\t.\t.\t0\t0\t2\t0\t2\t0\t0\t1\t0"]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Toy_data"), reason="reference fixtures are not on this machine")
 def test_oracle_format_has_the_properties_of_the_reference_outputs():
     """What the reference's own outputs of this step show (there is no input BAM to go further): header, 15 tab-separated columns,
     RD = A+C+G+T, reverse counts within the totals, positions listed twice written twice with identical counts."""
-    path = "/root/reference/Toy_data/NORMAL_ASEQ_DIR/N1.PILEUP.ASEQ"
-    lines = open(path).read().splitlines()
+    import gzip
+
+    path = os.path.join(helpers.GOLDEN, "toy_data", "NORMAL_ASEQ_DIR", "N1.PILEUP.ASEQ.gz")
+    lines = gzip.open(path).read().decode().splitlines()
     assert lines[0] == po.aseq_text([], {}, 0).strip()
     seen = {}
     twice = 0

@@ -9,12 +9,12 @@ O=gpurun_out/r06_end
 mkdir -p $O
 W=${1:-all}
 if [ "$W" = bench ] || [ "$W" = all ]; then
-python bench.py > $O/bench_default.json 2> $O/bench_default.err; tail -c 200 $O/bench_default.json; echo
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; tail -c 200 $O/bench_default.json; echo
 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/bench_driver_cmd.json 2> $O/bench_driver_cmd.err; tail -c 120 $O/bench_driver_cmd.json; echo
-python bench.py --ranges 1 --no-e2e --no-cpu-baseline > $O/bench_one_stream.json 2> $O/bench_one_stream.err; tail -c 120 $O/bench_one_stream.json; echo
-python bench.py --gpus 2 --backend gloo --check --steps 8 --warmup 2 --config c4s > $O/bench_gloo2_c4s.json 2> $O/bench_gloo2_c4s.err; tail -c 120 $O/bench_gloo2_c4s.json; echo
-python bench.py --force-dist --config c4 --steps 16 --warmup 4 --check > $O/bench_force_dist_c4.json 2> $O/bench_force_dist_c4.err; tail -c 120 $O/bench_force_dist_c4.json; echo
-python bench.py --config c5 --no-e2e --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_c5.json 2> $O/bench_c5.err; tail -c 120 $O/bench_c5.json; echo
+python bench.py --full --ranges 1 --no-e2e --no-cpu-baseline > $O/bench_one_stream.json 2> $O/bench_one_stream.err; tail -c 120 $O/bench_one_stream.json; echo
+python bench.py --full --gpus 2 --backend gloo --check --steps 8 --warmup 2 --config c4s > $O/bench_gloo2_c4s.json 2> $O/bench_gloo2_c4s.err; tail -c 120 $O/bench_gloo2_c4s.json; echo
+python bench.py --full --force-dist --config c4 --steps 16 --warmup 4 --check > $O/bench_force_dist_c4.json 2> $O/bench_force_dist_c4.err; tail -c 120 $O/bench_force_dist_c4.json; echo
+python bench.py --full --config c5 --no-e2e --no-cpu-baseline --steps 10 --warmup 3 > $O/bench_c5.json 2> $O/bench_c5.err; tail -c 120 $O/bench_c5.json; echo
 python bench.py --e2e c4 > $O/e2e_c4.json 2> $O/e2e_c4.err; tail -c 120 $O/e2e_c4.json; echo
 python tools/full_mode_bench.py > $O/full_mode.log 2>&1; tail -1 $O/full_mode.log
 fi
