@@ -22,8 +22,9 @@ BIN = os.path.join(PKG, "bin")
 HIP_LIB = os.path.join(LIB, "libamplisolve_hip.so")
 HOST_LIB = os.path.join(LIB, "libamplisolve_host.so")
 
-# ampli_kernels.hip: the path's kernels + their C ABI; ampli_pileup.hip: the upstream counting kernel; ampli_comm.hip: RCCL binding
-HIP_SOURCES = ["ampli_kernels.hip", "ampli_pileup.hip", "ampli_comm.hip"]
+# ampli_kernels.hip: the path's kernels + their C ABI; ampli_runtime.hip: context, streams, memory and settings;
+# ampli_pileup.hip: the upstream counting kernel; ampli_comm.hip: RCCL binding
+HIP_SOURCES = ["ampli_kernels.hip", "ampli_runtime.hip", "ampli_pileup.hip", "ampli_comm.hip"]
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off"]
 CXX_FLAGS = ["-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-pthread"]
 

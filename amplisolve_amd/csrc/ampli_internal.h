@@ -1,5 +1,5 @@
 // amplisolve_amd/csrc/ampli_internal.h -- what the translation units of libamplisolve_hip.so share: the context behind
-// ampli_ctx and the error plumbing.  Not part of the ABI (include/amplisolve_hip.h is).
+// ampli_ctx, the error plumbing and the stream helpers of ampli_runtime.hip.  Not part of the ABI (include/amplisolve_hip.h is).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -109,3 +109,16 @@ static inline hipStream_t main_stream(ampli_ctx *ctx)
     if (ctx->ranges_open) (void)ampli_ranges_join_internal(ctx);
     return ctx->stream;
 }
+
+// ampli_runtime.hip: what the launchers need of the context's streams
+int join_drain(ampli_ctx *ctx);                        // the context's stream waits for a drain still running on the side stream
+bool is_capturing(ampli_ctx *ctx);                     // the context's stream is capturing a graph (ampli_graph_begin)
+bool ranges_apply(ampli_ctx *ctx, long long P);        // a launch over P positions runs as position ranges (ampli_set_ranges)
+int ranges_fork(ampli_ctx *ctx, long long P);          // open the ranges' section for a panel of P positions
+void range_cuts(long long P, int n, long long cut[AMPLI_MAX_RANGES + 1]); // n tile-aligned ranges of [0, P)
+// Every range runs on a stream the context created itself, range 0 included: HIP deals streams to the device's few hardware queues
+// (four by default) in the order of their creation, and two ranges on one queue run one after the other.  Streams created back to
+// back here land on different queues; the caller's stream -- created who knows when -- is only forked from and joined into.
+// (Round 5's first form ran range 0 on the caller's stream: two and three ranges overlapped, four did not -- ranges 2 and 3 took
+// twice the time of ranges 0 and 1, 0.176 ms per pass against 0.132 with two.)
+static inline hipStream_t lane_stream(ampli_ctx *ctx, const int k) { return ctx->lanes[k].stream; }

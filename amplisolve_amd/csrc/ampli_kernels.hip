@@ -1,503 +1,42 @@
-// amplisolve_amd/csrc/ampli_kernels.hip -- HIP kernels + C ABI of libamplisolve_hip.so (gfx950, wave64).
+// amplisolve_amd/csrc/ampli_kernels.hip -- the HIP kernels of libamplisolve_hip.so (gfx950, wave64), their launchers and C ABI.
 //
-// Kernels (HBM-bound integer / scalar-FP work, no MFMA); LAY = record layout (32 / 24 / 16 bytes per record):
-//   error_reduce_kernel<FAST,G,LAY>   EE:1149-1296 (+clones), EE:1565-1631 (+clones)   one record read per (position, sample);
-//                                 epilogue: fused finalize_lane (one GPU), packed sums (all-reduce merge) or slice-major
-//                                 sums + germ-max pairs (position-sliced merge)
-//   acc_merge_kernel / acc_merge_ptr_kernel / gm_merge_kernel   ordered combines of partial accumulator tables
-//   acc_pack_kernel / acc_unpack_kernel / acc_pack_sliced_kernel   additive planes <-> exchange buffers
-//   error_finalize_kernel / error_finalize_merged_kernel / error_finalize_slice_kernel
-//                                 EE:1659-1714 (+clones), sentinel rule EE:1260/1318/1374/1431, text round trip EE:1704 -> VC:889
-//   error_table_unslice_kernel    gathered blocks of a sliced merge -> plane-major error table
-//   poisson_stream_kernel<LAY> + poisson_drain_kernel   VC:752-898 (+clones), VC:3721-3884   one record read per (position, tumour)
-//   poisson_call_kernel<MODE,LAY>                  the same evaluated in place (validation mode, dense outputs)
-//   records_pack16_kernel / records_pack24_kernel  int32 records -> the packed layouts
+// HBM-bound integer / scalar-FP work, no MFMA.  LAY = record layout (AMPLI_RECORDS_I32 / _U16 / _U24: 32 / 16 / 24 bytes per record).
+// The file follows the path; every stage holds its kernels, then their launchers and entry points:
+//   records            records_pack16_kernel / records_pack24_kernel   int32 records -> the packed layouts
+//   error reduce       error_reduce_kernel<FAST,G,LAY>   EE:1149-1296 (+clones), EE:1565-1631 (+clones)   one record read per
+//                        (position, sample); epilogue: fused finalize_lane (one GPU), packed sums (all-reduce merge) or slice-major
+//                        sums + germ-max pairs (position-sliced merge)
+//                      error_reduce_u16_kernel / error_reduce_u24_kernel<DUP,TAB>   the same with a compact per-position state, the
+//                        shipped shape for packed records; dup_tiles_kernel lists the tiles they leave to error_reduce_kernel
+//                      error_sums_inorder_kernel<LAY>   the eight threshold sums in the reference's own order (outside the envelope)
+//   merges and slices  acc_merge_kernel / acc_merge_ptr_kernel / gm_merge_kernel   ordered combines of partial accumulator tables
+//                      acc_pack_kernel / acc_unpack_kernel / acc_pack_sliced_kernel   additive planes <-> exchange buffers
+//                      error_finalize_slice_kernel -> error_table_unslice_kernel   one slice's error-table block -> plane-major table
+//   finalize           error_finalize_kernel / error_finalize_merged_kernel   EE:1659-1714 (+clones), sentinel rule
+//                        EE:1260/1318/1374/1431, text round trip EE:1704 -> VC:889
+//   Poisson            poisson_stream_kernel<LAY,IRR> + poisson_drain_kernel   VC:752-898 (+clones), VC:3721-3884   prefilter mode:
+//                        one record read per (position, tumour), the few scores past the gate queued and drained
+//                      poisson_full_kernel<LAY>   all-scores mode: light scores in place, heavy ones compacted per workgroup
+//                      poisson_call_kernel<MODE,LAY>   one lane per record, every score in place: the dense VAF output (either mode)
+//                      lgamma_table_kernel   kf_lgamma at the integers, for the drain and the all-scores mode
+//   auxiliary          score_batch_kernel / score_dense_batch_kernel / roundtrip_batch_kernel   scorer and text round trip on lists
+//                      synth_fill_kernel / synth_ref_kernel   synthetic panels (ampli_synth.h)
 // See include/amplisolve_hip.h for the data layout and DESIGN.md for the rooflines.  The library's other translation units:
-// ampli_pileup.hip (pileup_count_kernel, the step upstream of the path), ampli_comm.hip (RCCL binding of the multi-GPU merge),
-// ampli_internal.h (the context they share).
+// ampli_runtime.hip (context, streams, memory, settings), ampli_pileup.hip (pileup_count_kernel, the step upstream of the path),
+// ampli_comm.hip (RCCL binding of the multi-GPU merge), ampli_internal.h (what they share).
 #include <hip/hip_runtime.h>
 
-#include <cstdio>
-#include <cstdlib>
 #include <algorithm>
 #include <cstring>
-#include <new>
 #include <string>
+#include <type_traits>
 
 #include "../../include/amplisolve_hip.h"
 #include "ampli_internal.h"
 #include "ampli_math.h"
 #include "ampli_synth.h"
 
-extern "C" int ampli_abi_version(void) { return AMPLI_ABI_VERSION; }
-
-extern "C" const char *ampli_strerror(int code)
-{
-    switch (code) {
-    case AMPLI_OK: return "ok";
-    case AMPLI_E_INVALID: return "invalid argument";
-    case AMPLI_E_HIP: return "HIP runtime error (no MI355X visible, or a call failed)";
-    case AMPLI_E_NOMEM: return "out of memory";
-    case AMPLI_E_ENVELOPE: return "accumulators left the exactness envelope";
-    case AMPLI_E_CAPACITY: return "call list capacity exceeded";
-    case AMPLI_E_RANGE: return "count outside the integer envelope (>= 2^24)";
-    case AMPLI_E_COMM_TIMEOUT: return "RCCL communicator start-up timed out (the process must end)";
-    default: return "unknown error";
-    }
-}
-
-extern "C" int ampli_device_count(void)
-{
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess) return 0;
-    return n;
-}
-
-// the same, saying WHY when there is nothing to count: the number of devices, or -1 with hipGetDeviceCount's own error
-// name and text in msg ("hipErrorNoDevice: no ROCm-capable device is detected")
-extern "C" int ampli_device_probe(char *msg, size_t cap)
-{
-    int n = 0;
-    const hipError_t e = hipGetDeviceCount(&n);
-    if (msg && cap) msg[0] = 0;
-    if (e == hipSuccess) return n;
-    (void)hipGetLastError(); // do not leave the error behind for the next call's check
-    if (msg && cap) snprintf(msg, cap, "%s: %s", hipGetErrorName(e), hipGetErrorString(e));
-    return -1;
-}
-
-extern "C" int ampli_ctx_create(int device_ordinal, void *stream, ampli_ctx **out)
-{
-    if (!out) return AMPLI_E_INVALID;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return AMPLI_E_HIP;
-    if (device_ordinal < 0 || device_ordinal >= n) return AMPLI_E_INVALID;
-    ampli_ctx *ctx = new (std::nothrow) ampli_ctx();
-    if (!ctx) return AMPLI_E_NOMEM;
-    ctx->device = device_ordinal;
-    if (hipSetDevice(device_ordinal) != hipSuccess) { delete ctx; return AMPLI_E_HIP; }
-    hipDeviceProp_t prop;
-    if (hipGetDeviceProperties(&prop, device_ordinal) == hipSuccess) ctx->n_cu = prop.multiProcessorCount;
-    if (stream == AMPLI_STREAM_OWN) {
-        if (hipStreamCreateWithFlags(&ctx->stream, hipStreamNonBlocking) != hipSuccess) { delete ctx; return AMPLI_E_HIP; }
-        ctx->own_stream = true;
-    } else {
-        ctx->stream = (hipStream_t)stream; // NULL = the device's default (null) stream
-    }
-    if (hipMalloc((void **)&ctx->d_flags, 256) != hipSuccess || hipMemset(ctx->d_flags, 0, 256) != hipSuccess) {
-        if (ctx->own_stream) (void)hipStreamDestroy(ctx->stream);
-        delete ctx;
-        return AMPLI_E_NOMEM;
-    }
-    *out = ctx;
-    return AMPLI_OK;
-}
-
-extern "C" void ampli_ctx_destroy(ampli_ctx *ctx)
-{
-    if (!ctx) return;
-    (void)hipSetDevice(ctx->device);
-    if (ctx->ws) (void)hipFree(ctx->ws);
-    if (ctx->d_flags) (void)hipFree(ctx->d_flags);
-    for (int k = 0; k < AMPLI_MAX_RANGES; ++k) {
-        AmpliLane &l = ctx->lanes[k];
-        if (l.stream) { (void)hipStreamSynchronize(l.stream); (void)hipStreamDestroy(l.stream); }
-        if (l.q.items) (void)hipFree(l.q.items);
-        if (l.q.n) (void)hipFree(l.q.n);
-        if (l.done) (void)hipEventDestroy(l.done);
-    }
-    if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
-    if (ctx->d_lgtab) (void)hipFree(ctx->d_lgtab);
-    if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
-    if (ctx->ev_stream_done) (void)hipEventDestroy(ctx->ev_stream_done);
-    if (ctx->ev_drain_done) (void)hipEventDestroy(ctx->ev_drain_done);
-    if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
-}
-
-extern "C" const char *ampli_last_error(ampli_ctx *ctx) { return ctx ? ctx->err.c_str() : "no context"; }
-extern "C" void *ampli_stream(ampli_ctx *ctx) { return ctx ? (void *)main_stream(ctx) : nullptr; }
-
-// main stream waits for the drain kernel still running on the side stream (no host block)
-static int join_drain(ampli_ctx *ctx)
-{
-    if (ctx->drain_pending) {
-        HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_drain_done, 0));
-        ctx->drain_pending = false;
-    }
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_set_async_drain(ampli_ctx *ctx, int32_t on)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (on && !ctx->side) {
-        HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side, hipStreamNonBlocking));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_stream_done, hipEventDisableTiming));
-        HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_drain_done, hipEventDisableTiming));
-    }
-    if (!on) { int rc = join_drain(ctx); if (rc) return rc; }
-    ctx->async_drain = on ? 1 : 0;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_wait_calls(ampli_ctx *ctx)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    return join_drain(ctx);
-}
-
-// ---------------------------------------------------------------------------
-// Position ranges on concurrent streams (ampli_set_ranges; include/amplisolve_hip.h).  With n > 1 ranges ampli_error_estimate and
-// ampli_poisson_call (prefilter mode) cut the panel into n tile-aligned ranges of positions, every range on a stream the context
-// created for it (lane_stream below), each range's poisson_call behind its own error_estimate.  The section opens with a fork (the
-// lanes' streams wait for everything enqueued on the context's stream so far) and stays open across calls: back-to-back passes
-// over independent batches overlap -- one range's poisson_call and another's error_reduce fill each other's partly filled rounds
-// of workgroups.  It closes (the context's stream waits for every lane) at the next ordinary call: main_stream().
-// ---------------------------------------------------------------------------
-static void range_cuts(const long long P, const int n, long long cut[AMPLI_MAX_RANGES + 1])
-{
-    const long long tiles = (P + 63) / 64;
-    for (int k = 0; k < n; ++k) cut[k] = std::min<long long>(P, (tiles * k / n) * 64);
-    cut[n] = P;
-}
-
-// Every range runs on a stream the context created itself, range 0 included: HIP deals streams to the device's few hardware queues
-// (four by default) in the order of their creation, and two ranges on one queue run one after the other.  Streams created back to
-// back here land on different queues; the caller's stream -- created who knows when -- is only forked from and joined into.
-// (Round 5's first form ran range 0 on the caller's stream: two and three ranges overlapped, four did not -- ranges 2 and 3 took
-// twice the time of ranges 0 and 1, 0.176 ms per pass against 0.132 with two.)
-static inline hipStream_t lane_stream(ampli_ctx *ctx, const int k) { return ctx->lanes[k].stream; }
-
-int ampli_ranges_join_internal(ampli_ctx *ctx)
-{
-    if (!ctx->ranges_open) return AMPLI_OK;
-    // Every lane is joined whatever happens to another: a lane whose event cannot be recorded or waited for is waited for on the
-    // host instead, and only a lane that cannot be joined at all leaves an error -- a sticky one (main_stream() has no way to return
-    // it), which the entry point that asked for the stream reports from check_launch().  The section counts as closed only then.
-    int rc = AMPLI_OK;
-    for (int k = 0; k < ctx->n_ranges; ++k) {
-        hipError_t e = hipEventRecord(ctx->lanes[k].done, ctx->lanes[k].stream);
-        if (e == hipSuccess) e = hipStreamWaitEvent(ctx->stream, ctx->lanes[k].done, 0);
-        if (e != hipSuccess) e = hipStreamSynchronize(ctx->lanes[k].stream);
-        if (e != hipSuccess) {
-            ctx->err = std::string("joining position range ") + std::to_string(k) + ": " + hipGetErrorString(e);
-            ctx->sticky = rc = AMPLI_E_HIP;
-        }
-    }
-    ctx->ranges_open = false;
-    return rc;
-}
-
-// open the section for a panel of P positions (or keep it open if it is cut for the same panel)
-static int ranges_fork(ampli_ctx *ctx, const long long P)
-{
-    if (ctx->ranges_open && ctx->ranges_P == P) return AMPLI_OK;
-    { int rc = ampli_ranges_join_internal(ctx); if (rc) return rc; }
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-    for (int k = 0; k < ctx->n_ranges; ++k) HIP_TRY(ctx, hipStreamWaitEvent(ctx->lanes[k].stream, ctx->ev_fork, 0));
-    ctx->ranges_open = true;
-    ctx->ranges_P = P;
-    return AMPLI_OK;
-}
-
-// ranges apply to a launch over P positions: switched on, not capturing, and every range at least two tiles
-static bool ranges_apply(ampli_ctx *ctx, const long long P)
-{
-    if (ctx->n_ranges <= 1 || (P + 63) / 64 < 2ll * ctx->n_ranges) return false;
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (ctx->stream && hipStreamIsCapturing(ctx->stream, &st) == hipSuccess && st == hipStreamCaptureStatusActive) return false;
-    return true;
-}
-
-// Two streams overlap only if HIP has put them on different hardware queues -- it deals streams to a few queues (four by default) by
-// rules of its own, and two ranges on one queue simply run one after the other (measured: three ranges of which two shared a queue,
-// 0.18 ms per pass against 0.155 on one stream).  ampli_set_ranges therefore CHECKS: a short sleeping kernel on both streams at once
-// takes its own time if they overlap and twice that if they do not; a stream that shares a queue with an earlier range's is
-// replaced by a new one (a few tries).  ~0.2 ms per pair, once.
-__global__ void lane_probe_kernel(const int iters)
-{
-    for (int i = 0; i < iters; ++i) __builtin_amdgcn_s_sleep(127); // 127 x 64 cycles: ~3.4 us per turn at 2.4 GHz; bounded
-}
-
-static int lanes_overlap(ampli_ctx *ctx, hipStream_t a, hipStream_t b, bool *overlap)
-{
-    struct Events { // destroyed on every path out
-        hipEvent_t e[3] = {nullptr, nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    for (hipEvent_t &x : ev.e) HIP_TRY(ctx, hipEventCreate(&x));
-    hipEvent_t e0 = ev.e[0], e1 = ev.e[1], e2 = ev.e[2];
-    float alone = 0, both = 0;
-    for (int pass = 0; pass < 2; ++pass) { // the first pass warms the kernel's code object and both queues
-        HIP_TRY(ctx, hipEventRecord(e0, a));
-        hipLaunchKernelGGL(lane_probe_kernel, dim3(1), dim3(64), 0, a, 24);
-        HIP_TRY(ctx, hipEventRecord(e1, a));
-        HIP_TRY(ctx, hipStreamSynchronize(a));
-        HIP_TRY(ctx, hipEventElapsedTime(&alone, e0, e1));
-        HIP_TRY(ctx, hipEventRecord(e0, a));
-        hipLaunchKernelGGL(lane_probe_kernel, dim3(1), dim3(64), 0, a, 24);
-        hipLaunchKernelGGL(lane_probe_kernel, dim3(1), dim3(64), 0, b, 24);
-        HIP_TRY(ctx, hipEventRecord(e1, a));
-        HIP_TRY(ctx, hipEventRecord(e2, b));
-        HIP_TRY(ctx, hipStreamSynchronize(a));
-        HIP_TRY(ctx, hipStreamSynchronize(b));
-        float ta = 0, tb = 0;
-        HIP_TRY(ctx, hipEventElapsedTime(&ta, e0, e1));
-        HIP_TRY(ctx, hipEventElapsedTime(&tb, e0, e2));
-        both = ta > tb ? ta : tb;
-    }
-    *overlap = both < 1.6f * alone; // one after the other: ~2 x
-    return check_launch(ctx, "lane_probe_kernel");
-}
-
-extern "C" int ampli_ranges_concurrent(const ampli_ctx *ctx) { return ctx ? ctx->ranges_verified : AMPLI_E_INVALID; }
-
-extern "C" int ampli_set_ranges(ampli_ctx *ctx, int32_t n_ranges)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (n_ranges < 1 || n_ranges > AMPLI_MAX_RANGES) return fail(ctx, AMPLI_E_INVALID, "set_ranges: 1 .. 4 ranges");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rc = ampli_ranges_join_internal(ctx); if (rc) return rc; }
-    if (n_ranges > 1 && !ctx->ev_fork) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-    ctx->ranges_verified = n_ranges > 1 ? 1 : 0;
-    for (int k = 0; k < n_ranges && n_ranges > 1; ++k) {
-        AmpliLane &l = ctx->lanes[k];
-        if (!l.done) HIP_TRY(ctx, hipEventCreateWithFlags(&l.done, hipEventDisableTiming));
-        if (l.stream && l.verified) continue; // kept from an earlier call: already known to overlap with the lanes before it
-        struct Spare { // streams set aside during the search, destroyed on every path out
-            hipStream_t s[8];
-            int n = 0;
-            ~Spare() { for (int i = 0; i < n; ++i) (void)hipStreamDestroy(s[i]); }
-        } spare;
-        bool ok = false;
-        for (int attempt = 0; attempt < 8 && !ok; ++attempt) {
-            if (!l.stream) HIP_TRY(ctx, hipStreamCreateWithFlags(&l.stream, hipStreamNonBlocking));
-            ok = true;
-            for (int j = 0; j < k && ok; ++j) {
-                int rc = lanes_overlap(ctx, ctx->lanes[j].stream, l.stream, &ok);
-                if (rc) return rc;
-            }
-            // a stream that shares a queue with an earlier range's is kept alive until the search ends: destroyed at once, the next one
-            // created would take its place on the same queue
-            if (!ok) { spare.s[spare.n++] = l.stream; l.stream = nullptr; }
-        }
-        if (!ok) { l.stream = spare.s[--spare.n]; ctx->ranges_verified = 0; } // no luck: the ranges still give the right results, two of them in turn
-        l.verified = ok;
-    }
-    ctx->n_ranges = n_ranges;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_ranges_join(ampli_ctx *ctx)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    return ampli_ranges_join_internal(ctx);
-}
-
-// an event on range `range`'s stream, WITHOUT closing the section: brackets that range's share of the calls around it (the
-// kernels' durations under the overlap the ranges exist for)
-extern "C" int ampli_range_event_record(ampli_ctx *ctx, int32_t range, void *ev)
-{
-    if (!ctx || !ev || range < 0 || range >= ctx->n_ranges) return AMPLI_E_INVALID;
-    // without ranges (n_ranges = 1) there are no lanes: range 0 is the context's own stream
-    HIP_TRY(ctx, hipEventRecord((hipEvent_t)ev, ctx->n_ranges > 1 ? lane_stream(ctx, range) : main_stream(ctx)));
-    return AMPLI_OK;
-}
-
-// ---------------------------------------------------------------------------
-// hipGraph capture of a sequence of ampli_* calls (launch-bound small panels: a pass over a 10k-position panel is
-// four ~10 us kernels, so the launches themselves dominate).  Capture needs a real stream (AMPLI_STREAM_OWN or any
-// non-null stream) and warm workspaces: run the sequence once before capturing; a call that would have to allocate
-// or synchronise while capturing fails with AMPLI_E_INVALID.
-// ---------------------------------------------------------------------------
-static bool is_capturing(ampli_ctx *ctx)
-{
-    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
-    if (!ctx->stream) return false;
-    if (hipStreamIsCapturing(ctx->stream, &st) != hipSuccess) return false;
-    return st == hipStreamCaptureStatusActive;
-}
-
-extern "C" int ampli_graph_begin(ampli_ctx *ctx)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!main_stream(ctx)) return fail(ctx, AMPLI_E_INVALID, "graph capture needs a non-default stream (AMPLI_STREAM_OWN)");
-    { int rc = join_drain(ctx); if (rc) return rc; }
-    HIP_TRY(ctx, hipStreamBeginCapture(main_stream(ctx), hipStreamCaptureModeThreadLocal));
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_graph_end(ampli_ctx *ctx, void **graph_exec)
-{
-    if (!ctx || !graph_exec) return AMPLI_E_INVALID;
-    hipGraph_t g = nullptr;
-    HIP_TRY(ctx, hipStreamEndCapture(main_stream(ctx), &g));
-    hipGraphExec_t e = nullptr;
-    hipError_t err = hipGraphInstantiate(&e, g, nullptr, nullptr, 0);
-    (void)hipGraphDestroy(g);
-    if (err != hipSuccess) return fail(ctx, AMPLI_E_HIP, "hipGraphInstantiate failed");
-    *graph_exec = (void *)e;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_graph_launch(ampli_ctx *ctx, void *graph_exec)
-{
-    if (!ctx || !graph_exec) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipGraphLaunch((hipGraphExec_t)graph_exec, main_stream(ctx)));
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_graph_destroy(void *graph_exec)
-{
-    return hipGraphExecDestroy((hipGraphExec_t)graph_exec) == hipSuccess ? AMPLI_OK : AMPLI_E_HIP;
-}
-
-extern "C" int ampli_sync(ampli_ctx *ctx)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    { int rc = join_drain(ctx); if (rc) return rc; }
-    HIP_TRY(ctx, hipStreamSynchronize(main_stream(ctx)));
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_pinned_alloc(size_t bytes, void **out)
-{
-    if (!out) return AMPLI_E_INVALID;
-    return hipHostMalloc(out, bytes, hipHostMallocDefault) == hipSuccess ? AMPLI_OK : AMPLI_E_NOMEM;
-}
-extern "C" int ampli_pinned_free(void *p) { return hipHostFree(p) == hipSuccess ? AMPLI_OK : AMPLI_E_HIP; }
-// pin memory the caller already owns and has filled (the command lines' parsers start before the runtime is up)
-extern "C" int ampli_host_register(ampli_ctx *ctx, void *p, size_t bytes)
-{
-    if (!p || !bytes) return AMPLI_E_INVALID;
-    if (ctx && hipSetDevice(ctx->device) != hipSuccess) return AMPLI_E_HIP; // the calling thread may not be the one that made the context
-    return hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess ? AMPLI_OK : AMPLI_E_NOMEM;
-}
-extern "C" int ampli_host_unregister(void *p) { return hipHostUnregister(p) == hipSuccess ? AMPLI_OK : AMPLI_E_HIP; }
-
-extern "C" int ampli_dev_alloc(ampli_ctx *ctx, size_t bytes, void **d_out)
-{
-    if (!ctx || !d_out) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (hipMalloc(d_out, bytes ? bytes : 1) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "hipMalloc failed");
-    return AMPLI_OK;
-}
-extern "C" int ampli_dev_free(ampli_ctx *ctx, void *d_p)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipFree(d_p));
-    return AMPLI_OK;
-}
-extern "C" int ampli_copy_h2d(ampli_ctx *ctx, void *d_dst, const void *src, size_t bytes)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipMemcpyAsync(d_dst, src, bytes, hipMemcpyHostToDevice, main_stream(ctx)));
-    return AMPLI_OK;
-}
-extern "C" int ampli_copy_d2h(ampli_ctx *ctx, void *dst, const void *d_src, size_t bytes)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    { int rc = join_drain(ctx); if (rc) return rc; }
-    HIP_TRY(ctx, hipMemcpyAsync(dst, d_src, bytes, hipMemcpyDeviceToHost, main_stream(ctx)));
-    return AMPLI_OK;
-}
-extern "C" int ampli_memset_d(ampli_ctx *ctx, void *d_dst, int byte, size_t bytes)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipMemsetAsync(d_dst, byte, bytes, main_stream(ctx)));
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_event_create(void **ev)
-{
-    if (!ev) return AMPLI_E_INVALID;
-    hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return AMPLI_E_HIP;
-    *ev = (void *)e;
-    return AMPLI_OK;
-}
-extern "C" int ampli_event_destroy(void *ev) { return hipEventDestroy((hipEvent_t)ev) == hipSuccess ? AMPLI_OK : AMPLI_E_HIP; }
-extern "C" int ampli_event_record(ampli_ctx *ctx, void *ev)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipEventRecord((hipEvent_t)ev, main_stream(ctx)));
-    return AMPLI_OK;
-}
-extern "C" int ampli_event_sync(void *ev) { return hipEventSynchronize((hipEvent_t)ev) == hipSuccess ? AMPLI_OK : AMPLI_E_HIP; }
-extern "C" int ampli_event_elapsed_ms(void *a, void *b, float *ms)
-{
-    if (hipEventSynchronize((hipEvent_t)b) != hipSuccess) return AMPLI_E_HIP;
-    return hipEventElapsedTime(ms, (hipEvent_t)a, (hipEvent_t)b) == hipSuccess ? AMPLI_OK : AMPLI_E_HIP;
-}
-
-extern "C" int ampli_set_record_layout(ampli_ctx *ctx, int32_t layout)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (layout != AMPLI_RECORDS_I32 && layout != AMPLI_RECORDS_U16 && layout != AMPLI_RECORDS_U24)
-        return fail(ctx, AMPLI_E_INVALID, "set_record_layout: unknown layout");
-    ctx->rec_layout = layout;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_set_slice_group(ampli_ctx *ctx, int32_t group_size, int32_t group_index)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (group_size < 1 || group_index < 0 || group_index >= group_size) return fail(ctx, AMPLI_E_INVALID, "set_slice_group: 0 <= index < size");
-    ctx->grp_size = group_size;
-    ctx->grp_index = group_index;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_set_tuning(ampli_ctx *ctx, int32_t reduce_sample_splits, int32_t reduce_general, int32_t reduce_lane_groups)
-{
-    if (!ctx || reduce_sample_splits < 0 || (reduce_lane_groups != 0 && reduce_lane_groups != 1 && reduce_lane_groups != 2 && reduce_lane_groups != 4))
-        return AMPLI_E_INVALID;
-    ctx->reduce_splits = reduce_sample_splits;
-    ctx->reduce_general = reduce_general ? 1 : 0;
-    ctx->reduce_groups = reduce_lane_groups; // lane groups per wave (0 = auto)
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_set_reduce_compact(ampli_ctx *ctx, int32_t on)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    ctx->reduce_compact = on ? 1 : 0;
-    ctx->reduce_compact_u16_only = on == 2 ? 1 : 0; // 2: the compact-state kernel for uint16 records only (A/B runs of the 24-bit form)
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_last_reduce_kernel(const ampli_ctx *ctx)
-{
-    return ctx && ctx->last_reduce_kernel >= 0 ? ctx->last_reduce_kernel : AMPLI_E_INVALID;
-}
-
-extern "C" int ampli_set_poisson_tuning(ampli_ctx *ctx, int32_t rows_per_wave, int32_t drain_blocks_per_shard)
-{
-    if (!ctx || rows_per_wave < 0 || drain_blocks_per_shard < 0 || drain_blocks_per_shard > 65535) return AMPLI_E_INVALID;
-    ctx->pc_rows_per_wave = rows_per_wave;
-    ctx->pc_drain_blocks = drain_blocks_per_shard;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_set_queue_items(ampli_ctx *ctx, int64_t items)
-{
-    if (!ctx || items < 0) return AMPLI_E_INVALID;
-    ctx->queue_min_items = (size_t)items;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_ctx_flags(ampli_ctx *ctx, int32_t *out, int32_t clear)
-{
-    if (!ctx || !out) return AMPLI_E_INVALID;
-    { int rc = join_drain(ctx); if (rc) return rc; }
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_flags, sizeof(int), hipMemcpyDeviceToHost, main_stream(ctx)));
-    HIP_TRY(ctx, hipStreamSynchronize(main_stream(ctx)));
-    if (clear) HIP_TRY(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof(int), main_stream(ctx)));
-    return AMPLI_OK;
-}
+// ==== records: layouts, the cohort a kernel reads, int32 -> packed records =============================================================
 
 // streaming 16-byte load of record data (default cache policy: non-temporal loads measured 4-10 % slower)
 __device__ __forceinline__ int4 ld_stream(const int4 *p) { return *p; }
@@ -540,9 +79,9 @@ struct RecView {
     const int *rd_ext;
 };
 
-template <int LAY> __host__ __device__ constexpr int rec_bytes_of()
+__host__ __device__ constexpr int rec_bytes(const int layout)
 {
-    return LAY == AMPLI_RECORDS_U24 ? 24 : (LAY == AMPLI_RECORDS_U16 ? 16 : 32);
+    return layout == AMPLI_RECORDS_U24 ? 24 : (layout == AMPLI_RECORDS_U16 ? 16 : 32);
 }
 
 template <int LAY> __device__ __forceinline__ RawRec<LAY> rec_load_at(const char *__restrict__ q)
@@ -580,6 +119,150 @@ template <int LAY> __device__ __forceinline__ void rec_decode(const RawRec<LAY> 
         fw = r.a; bw = r.b;
     }
 }
+
+// 8 x int32 records -> 8 x uint16 records (AMPLI_ABSENT -> 0xFFFF); *overflow is raised for a count above 65534
+__global__ __launch_bounds__(256) void records_pack16_kernel(const int4 *__restrict__ in, const long long n, uint4 *__restrict__ out,
+                                                             int *__restrict__ overflow)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int4 a = in[i * 2], b = in[i * 2 + 1];
+    const bool absent = a.x == AMPLI_ABSENT;
+    const unsigned v[8] = {absent ? 0xFFFFu : (unsigned)a.x, (unsigned)a.y, (unsigned)a.z, (unsigned)a.w,
+                           (unsigned)b.x, (unsigned)b.y, (unsigned)b.z, (unsigned)b.w};
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bad |= (j == 0 && absent) ? false : v[j] > 65534u;
+    if (bad) atomicOr(overflow, 1);
+    out[i] = make_uint4((v[0] & 0xFFFFu) | (v[1] << 16), (v[2] & 0xFFFFu) | (v[3] << 16), (v[4] & 0xFFFFu) | (v[5] << 16),
+                        (v[6] & 0xFFFFu) | (v[7] << 16));
+}
+
+// 8 x int32 records -> 8 x 24-bit records (AMPLI_ABSENT -> 0xFFFFFF); *overflow is raised for a count above 2^24 - 2
+__global__ __launch_bounds__(256) void records_pack24_kernel(const int4 *__restrict__ in, const long long n, uint2 *__restrict__ out,
+                                                             int *__restrict__ overflow)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int4 a = in[i * 2], b = in[i * 2 + 1];
+    const bool absent = a.x == AMPLI_ABSENT;
+    const unsigned v[8] = {absent ? 0xFFFFFFu : (unsigned)a.x, (unsigned)a.y, (unsigned)a.z, (unsigned)a.w,
+                           (unsigned)b.x, (unsigned)b.y, (unsigned)b.z, (unsigned)b.w};
+    bool bad = false;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) bad |= (j == 0 && absent) ? false : v[j] > 0xFFFFFEu;
+    if (bad) atomicOr(overflow, 1);
+    unsigned w[6];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) { // four 24-bit fields -> three dwords
+        const unsigned f0 = v[4 * h] & 0xFFFFFFu, f1 = v[4 * h + 1] & 0xFFFFFFu, f2 = v[4 * h + 2] & 0xFFFFFFu, f3 = v[4 * h + 3] & 0xFFFFFFu;
+        w[3 * h] = f0 | (f1 << 24);
+        w[3 * h + 1] = (f1 >> 8) | (f2 << 16);
+        w[3 * h + 2] = (f2 >> 16) | (f3 << 8);
+    }
+    out[i * 3] = make_uint2(w[0], w[1]);
+    out[i * 3 + 1] = make_uint2(w[2], w[3]);
+    out[i * 3 + 2] = make_uint2(w[4], w[5]);
+}
+
+// what the kernels read: a cohort (or one chunk of a streamed one) resident on the device
+struct DevCohort {
+    RecView rv;
+    int layout;   // AMPLI_RECORDS_*
+    int n;        // samples
+    long long E;  // extra-occurrence slots per sample
+    const unsigned *dup_off; // [P+1]: extras of position p are e in [dup_off[p], dup_off[p+1])   (error_reduce)
+    const unsigned *ext_pos; // [E]: position of extra e                                          (poisson_call)
+};
+
+// the dense interchange layout [n][P+E] in the context's record layout (the classic entry points)
+static DevCohort dense_cohort(const ampli_ctx *ctx, const void *d_recs, int64_t P, int64_t E, int n, const uint32_t *dup_off,
+                              const uint32_t *ext_pos)
+{
+    DevCohort c;
+    c.layout = ctx->rec_layout;
+    c.rv.base = (const char *)d_recs;
+    c.rv.row_stride = P + E;
+    c.rv.ext = (const char *)d_recs + (size_t)P * rec_bytes(c.layout);
+    c.rv.ext_stride = P + E;
+    c.rv.rd = nullptr; c.rv.rd_ext = nullptr;
+    c.n = n; c.E = E; c.dup_off = dup_off; c.ext_pos = ext_pos;
+    return c;
+}
+
+static int cohort_from_records(ampli_ctx *ctx, const ampli_records *r, int64_t P, DevCohort &c)
+{
+    if (!r || !r->recs || r->n_samples <= 0 || r->E < 0) return fail(ctx, AMPLI_E_INVALID, "records: recs, n_samples > 0 and E >= 0 are required");
+    if (r->layout != AMPLI_RECORDS_I32 && r->layout != AMPLI_RECORDS_U16 && r->layout != AMPLI_RECORDS_U24)
+        return fail(ctx, AMPLI_E_INVALID, "records: unknown layout");
+    c.layout = r->layout;
+    c.n = r->n_samples;
+    c.E = r->E;
+    c.dup_off = r->dup_off; c.ext_pos = r->ext_pos;
+    c.rv.rd = r->rd;
+    c.rv.rd_ext = r->rd_ext;
+    c.rv.base = (const char *)r->recs;
+    c.rv.row_stride = r->row_stride > 0 ? r->row_stride : (r->ext ? P : P + r->E);
+    if (r->ext) {
+        c.rv.ext = (const char *)r->ext;
+        c.rv.ext_stride = r->ext_stride > 0 ? r->ext_stride : r->E;
+        if (c.rv.row_stride < P || c.rv.ext_stride < r->E) return fail(ctx, AMPLI_E_INVALID, "records: row_stride < P or ext_stride < E");
+    } else {
+        c.rv.ext = c.rv.base + (size_t)P * rec_bytes(c.layout);
+        c.rv.ext_stride = c.rv.row_stride;
+        if (c.rv.row_stride < P + r->E) return fail(ctx, AMPLI_E_INVALID, "records: row_stride < P + E");
+    }
+    return AMPLI_OK;
+}
+
+// what every kernel reading a cohort needs of it: extras come with their index (`index`, called `index_name` in the message),
+// records 16-byte aligned (8-byte in the 24-byte layout)
+static int check_records(ampli_ctx *ctx, const DevCohort &co, const char *what, const uint32_t *index, const char *index_name)
+{
+    if (co.E > 0 && !index) return fail(ctx, AMPLI_E_INVALID, (std::string(what) + ": E > 0 needs " + index_name).c_str());
+    const uintptr_t am = co.layout == AMPLI_RECORDS_U24 ? 7 : 15;
+    if (((uintptr_t)co.rv.base & am) != 0 || (co.E > 0 && ((uintptr_t)co.rv.ext & am) != 0))
+        return fail(ctx, AMPLI_E_INVALID, (std::string(what) + ": recs must be 16-byte aligned (8-byte for the 24-byte layout)").c_str());
+    return AMPLI_OK;
+}
+
+// Launch dispatch: f(constant) for the run-time value, inside a generic lambda the template argument of a kernel.
+template <int V> using Const = std::integral_constant<int, V>;
+template <class F> static void with_layout(const int layout, F &&f) // every record layout
+{
+    if (layout == AMPLI_RECORDS_U24) f(Const<AMPLI_RECORDS_U24>{});
+    else if (layout == AMPLI_RECORDS_U16) f(Const<AMPLI_RECORDS_U16>{});
+    else f(Const<AMPLI_RECORDS_I32>{});
+}
+template <class F> static void with_bool(const bool b, F &&f)
+{
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+
+extern "C" int ampli_records_pack16(ampli_ctx *ctx, const int32_t *d_recs32, int64_t n_records, void *d_recs16, int32_t *d_overflow)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_recs32 || !d_recs16 || !d_overflow || n_records <= 0 || ((uintptr_t)d_recs32 & 15) || ((uintptr_t)d_recs16 & 15))
+        return fail(ctx, AMPLI_E_INVALID, "records_pack16: bad argument (16-byte aligned buffers, n_records > 0, overflow word)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(records_pack16_kernel, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, main_stream(ctx), (const int4 *)d_recs32,
+                       (long long)n_records, (uint4 *)d_recs16, d_overflow);
+    return check_launch(ctx, "records_pack16_kernel");
+}
+
+extern "C" int ampli_records_pack24(ampli_ctx *ctx, const int32_t *d_recs32, int64_t n_records, void *d_recs24, int32_t *d_overflow)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_recs32 || !d_recs24 || !d_overflow || n_records <= 0 || ((uintptr_t)d_recs32 & 15) || ((uintptr_t)d_recs24 & 7))
+        return fail(ctx, AMPLI_E_INVALID, "records_pack24: bad argument (aligned buffers, n_records > 0, overflow word)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipLaunchKernelGGL(records_pack24_kernel, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, main_stream(ctx), (const int4 *)d_recs32,
+                       (long long)n_records, (uint2 *)d_recs24, d_overflow);
+    return check_launch(ctx, "records_pack24_kernel");
+}
+
+// ==== error reduce: records -> accumulator table (or straight to an error table / exchange buffers) ====================================
 
 // ---------------------------------------------------------------------------
 // accumulator table layout
@@ -1173,7 +856,7 @@ __global__ __launch_bounds__(256) void error_reduce_kernel(
 
     // one sample row in registers + the next one in flight; every lane group walks its own chunk, the trip count
     // (chunk_len) is wave-uniform and rows past a group's chunk are loaded clamped and not visited
-    constexpr int RB = rec_bytes_of<LAY>();
+    constexpr int RB = rec_bytes(LAY);
     const size_t row_step = (size_t)rv.row_stride * RB; // bytes between the same position of consecutive samples
     const char *__restrict__ q = rv.base + ((size_t)min(s0, S - 1) * (size_t)rv.row_stride + (size_t)p) * RB;
     RawRec<LAY> nx = rec_load_at<LAY>(q);
@@ -1479,7 +1162,7 @@ __device__ __forceinline__ void compact_reduce_body(Red16Shared &sh, const RecVi
                                                     const float C, const int cov, int *__restrict__ flags, const AccPtrs &tab,
                                                     const FinOut &fin)
 {
-    constexpr int RB = rec_bytes_of<LAY>();
+    constexpr int RB = rec_bytes(LAY);
     constexpr bool DC = LAY != AMPLI_RECORDS_U16;
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -1596,6 +1279,355 @@ __global__ __launch_bounds__(256, 5) void error_reduce_u24_kernel(const RecView 
     compact_reduce_body<AMPLI_RECORDS_U24, DUP, TAB>(sh, rv, P, p_lo, p_hi, dup_off, S, chunk_len, C, cov, flags, tab, fin);
 }
 
+static int ensure_ws(ampli_ctx *ctx, size_t bytes)
+{
+    if (ctx->ws_bytes >= bytes) return AMPLI_OK;
+    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "workspace would have to grow while capturing: run the sequence once first");
+    if (ctx->ws) { HIP_TRY(ctx, hipStreamSynchronize(main_stream(ctx))); (void)hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_bytes = 0; }
+    if (hipMalloc(&ctx->ws, bytes) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "workspace hipMalloc failed");
+    ctx->ws_bytes = bytes;
+    return AMPLI_OK;
+}
+
+static AccPtrs to_ptrs(const ampli_acc_table *t)
+{
+    AccPtrs a;
+    a.snt = t->snt; a.srd = (long long *)t->srd; a.cnt = t->cnt; a.nrec = t->nrec; a.gm_n = t->gm_n;
+    a.gm_first = t->gm_first; a.gm_first_af = t->gm_first_af; a.gm_rest = t->gm_rest;
+    return a;
+}
+
+// the planes of a table carved from `base` at the offsets of acc_offsets (a partial or merged table of the workspace)
+static AccPtrs acc_ptrs(char *base, const size_t off[9])
+{
+    AccPtrs a;
+    a.snt = (double *)(base + off[0]); a.srd = (long long *)(base + off[1]); a.cnt = (int *)(base + off[2]);
+    a.nrec = (int *)(base + off[3]); a.gm_n = (int *)(base + off[4]); a.gm_first = (int *)(base + off[5]);
+    a.gm_first_af = (float *)(base + off[6]); a.gm_rest = (float *)(base + off[7]);
+    return a;
+}
+
+// the error table a finalize writes (rate and code required; thr, germ_val, germ_present and flags optional)
+static FinOut table_out(float *rate, uint8_t *code, float *thr, float *germ_val, uint8_t *germ_present, int32_t *flags)
+{
+    FinOut o = {};
+    o.rate = rate; o.code = code; o.thr = thr; o.germ_val = germ_val; o.germ_present = germ_present; o.flags = flags;
+    return o;
+}
+
+// the slice-major exchange buffers of a position-sliced merge: [n_slices][group][planes][L] sums and [n_slices][group][8][L]
+// germ-max pairs, of which this call fills batch grp_index (ampli_set_slice_group) in the context's format (ampli_set_slice_format)
+static FinOut slice_out(const ampli_ctx *ctx, const long long P, const int n_slices, double *d_sums, float *d_gm)
+{
+    FinOut o = {};
+    o.slice_len = ampli_slice_len(P, n_slices);
+    o.sl_group = ctx->grp_size;
+    o.sl_fmt = ctx->slice_fmt; o.sl_n = n_slices; o.sl_flags = ctx->d_flags;
+    o.sl_sums = d_sums + (size_t)ctx->grp_index * slice_planes(o.sl_fmt) * (size_t)o.slice_len;
+    o.sl_gm = d_gm + (size_t)ctx->grp_index * 8 * (size_t)o.slice_len;
+    return o;
+}
+
+// a bound table must be one buffer carved by ampli_acc_bind
+static bool acc_is_bound(const ampli_acc_table *t)
+{
+    if (!t || !t->snt || t->P <= 0) return false;
+    size_t off[9];
+    acc_offsets(t->P, off);
+    const AccPtrs carved = acc_ptrs((char *)t->snt, off), given = to_ptrs(t);
+    return memcmp(&carved, &given, sizeof(AccPtrs)) == 0;
+}
+
+// launched by error_reduce_impl after a cut along the samples (defined with their stages below)
+__global__ void acc_merge_kernel(char *, const char *, size_t, int, long long, size_t, size_t, size_t, size_t, size_t, size_t, size_t,
+                                 size_t, const char *);
+__global__ void acc_pack_kernel(AccPtrs, long long, double *);
+__global__ void acc_pack_sliced_kernel(AccPtrs, long long, FinOut);
+static int launch_finalize(ampli_ctx *ctx, const AccPtrs &t, long long P, float C, int cov, const FinOut &fo);
+
+// reduce (+ optional fused finalize).  d_acc may be NULL when fin.rate is set (the table is then not materialised
+// unless the sample axis has to be split across workgroups).
+static int error_reduce_impl(ampli_ctx *ctx, const DevCohort &co, int64_t P, int32_t first_sample, float C, int32_t cov,
+                             const ampli_acc_table *d_acc, const FinOut &fin)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    const int64_t E = co.E;
+    const int32_t S = co.n;
+    const uint32_t *d_dup_off = co.dup_off;
+    if (!co.rv.base || P <= 0 || E < 0 || S <= 0 || cov < 1 || (d_acc && (!acc_is_bound(d_acc) || d_acc->P != P)) || (!d_acc && !fin.rate && !fin.slice_len) || (fin.packed && !d_acc))
+        return fail(ctx, AMPLI_E_INVALID, "error_reduce: bad argument (P,S>0, cov>=1, table bound with ampli_acc_bind for the same P)");
+    if (fin.accumulate && !d_acc) return fail(ctx, AMPLI_E_INVALID, "error_reduce: accumulate needs the table");
+    { int rc = check_records(ctx, co, "error_reduce", d_dup_off, "dup_off"); if (rc) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+
+    // lane groups per wave: only for panels too small to fill the chip with 64-position waves (measured on c3:
+    // G = 2 / 4 cost 6 % / 11 % -- the narrower per-row segments outweigh the shorter tail)
+    const long long resident_waves = (long long)ctx->n_cu * 16;
+    const bool fast = !ctx->reduce_general && !co.rv.rd && !co.rv.rd_ext; // lines with their own RD column: the literal kernel
+    // the shape error_reduce_u16_kernel takes (below).  From one tile per CU on it beats every cut of the general kernel along
+    // lanes or samples (tools/sweep_tiles.py: 48 us against 62 at 768 tiles, 69 against 102 at 1280), so such a launch is not cut
+    const bool compact_shape = ctx->reduce_compact && fast && (!d_acc || fin.summary) && !fin.packed &&
+                               ((co.layout == AMPLI_RECORDS_U16 && S <= RED_WAVES * FAST_MAX_CHUNK) ||
+                                (co.layout == AMPLI_RECORDS_U24 && S <= RED_WAVES * COMPACT_MAX_REC_U24 && !ctx->reduce_compact_u16_only));
+    const bool compact_uncut = compact_shape && (P + 63) / 64 >= ctx->n_cu;
+    int G = ctx->reduce_groups;
+    if (G != 1 && G != 2 && G != 4) {
+        G = 1;
+        while (!compact_uncut && G < 4 && ((P + 64 / G - 1) / (64 / G)) * RED_WAVES < resident_waves && S / (RED_WAVES * 2 * G) >= 8) G *= 2;
+    }
+    const long long tiles = (P + 64 / G - 1) / (64 / G);
+    // sample splits: enough waves to fill the chip (>= ~24 waves per CU), each lane group with >= 8 samples
+    int splits = ctx->reduce_splits;
+    if (splits <= 0 && compact_uncut && G == 1) {
+        splits = 1;
+    } else if (splits <= 0) {
+        const long long want_waves = (long long)ctx->n_cu * 24;
+        splits = (int)((want_waves + tiles * RED_WAVES - 1) / (tiles * RED_WAVES));
+        const int max_splits = (S + RED_WAVES * G * 8 - 1) / (RED_WAVES * G * 8);
+        if (splits > max_splits) splits = max_splits;
+        if (splits < 1) splits = 1;
+    }
+    if (splits > S) splits = S;
+    if (fast) { // int32 partial sums: a lane takes at most FAST_MAX_CHUNK samples
+        const int need = (S + RED_WAVES * G * FAST_MAX_CHUNK - 1) / (RED_WAVES * G * FAST_MAX_CHUNK);
+        if (splits < need) splits = need;
+    }
+    const int chunks = splits * RED_WAVES * G;
+    const int chunk_len = (S + chunks - 1) / chunks;
+
+    size_t off[9];
+    acc_offsets(P, off);
+    char *out_base = d_acc ? (char *)d_acc->snt : nullptr;
+    size_t stride = 0;
+    FinOut kfin = fin; // what the reduce kernel itself finalises
+    if (splits > 1) {
+        // partial tables, one per split, plus one slot for the merged table when the caller did not ask for it
+        int rc = ensure_ws(ctx, off[8] * (size_t)(splits + 1));
+        if (rc) return rc;
+        out_base = (char *)ctx->ws;
+        stride = off[8];
+        kfin.rate = nullptr;
+        kfin.packed = nullptr; // packed after the merge, below
+        kfin.slice_len = 0;
+        kfin.accumulate = 0;   // folded in by the merge kernel, below
+    }
+    if (splits > 65535 || tiles > 0x7fffffffll) return fail(ctx, AMPLI_E_RANGE, "error_reduce: panel or sample count beyond the grid limits");
+    ctx->last_reduce_kernel = (compact_shape && G == 1 && splits == 1) ? (co.layout == AMPLI_RECORDS_U24 ? 2 : 1) : 0;
+    if (ctx->last_reduce_kernel) {
+        const AccPtrs tab = d_acc ? to_ptrs(d_acc) : AccPtrs{};
+        const int clen = (S + RED_WAVES - 1) / RED_WAVES;
+        const bool u24 = co.layout == AMPLI_RECORDS_U24; // the compact shape exists for the two packed layouts only
+        // the compact kernel over positions [lo, hi) on st: DUP skips the tiles dup_tiles_kernel listed, TAB writes the table
+        auto launch_compact = [&](const bool dup, hipStream_t st, const long long lo, const long long hi) {
+            with_bool(dup, [&](auto DUP) {
+                with_bool(d_acc != nullptr, [&](auto TAB) {
+                    const auto kernel = u24 ? error_reduce_u24_kernel<DUP, TAB> : error_reduce_u16_kernel<DUP, TAB>;
+                    hipLaunchKernelGGL(kernel, dim3((unsigned)((hi - lo + 63) / 64)), dim3(256), 0, st, co.rv, (long long)P, lo, hi, d_dup_off,
+                                       (int)S, clen, C, (int)cov, ctx->d_flags, tab, fin);
+                });
+            });
+        };
+        if (E > 0) {
+            // the tiles with a position listed more than once go to the general kernel (at most one such tile per extra slot)
+            hipStream_t st = main_stream(ctx);
+            const long long ntiles = (P + 63) / 64;
+            { int rc = ensure_ws(ctx, (size_t)(ntiles + 1) * sizeof(unsigned)); if (rc) return rc; }
+            unsigned *list = (unsigned *)ctx->ws;
+            HIP_TRY(ctx, hipMemsetAsync(list, 0, sizeof(unsigned), st));
+            hipLaunchKernelGGL(dup_tiles_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, st, d_dup_off, (long long)P, list);
+            launch_compact(true, st, 0, P);
+            { int rc = check_launch(ctx, "error_reduce_u16_kernel"); if (rc) return rc; }
+            const auto dup_kernel = u24 ? error_reduce_kernel<true, 1, AMPLI_RECORDS_U24> : error_reduce_kernel<true, 1, AMPLI_RECORDS_U16>;
+            hipLaunchKernelGGL(dup_kernel, dim3((unsigned)std::min<long long>(E, ntiles)), dim3(256), 0, st, co.rv, (long long)P, (long long)E,
+                               d_dup_off, (int)S, (int)first_sample, clen, C, (int)cov, d_acc ? (char *)d_acc->snt : (char *)nullptr, (size_t)0,
+                               off[0], off[1], off[2], off[3], off[4], off[5], off[6], off[7], ctx->d_flags, fin, (const unsigned *)list);
+            return check_launch(ctx, "error_reduce_kernel (tiles with positions listed more than once)");
+        }
+        if (ranges_apply(ctx, P)) { // position ranges on concurrent streams (ampli_set_ranges)
+            { int rc = ranges_fork(ctx, P); if (rc) return rc; }
+            long long cut[AMPLI_MAX_RANGES + 1];
+            range_cuts(P, ctx->n_ranges, cut);
+            for (int k = 0; k < ctx->n_ranges; ++k) launch_compact(false, lane_stream(ctx, k), cut[k], cut[k + 1]);
+            return check_launch(ctx, "error_reduce_u16_kernel");
+        }
+        launch_compact(false, main_stream(ctx), 0, P);
+        return check_launch(ctx, "error_reduce_u16_kernel");
+    }
+    const dim3 grid((unsigned)tiles, (unsigned)splits);
+    auto launch_general = [&](auto FAST, auto GV) {
+        with_layout(co.layout, [&](auto L) {
+            hipLaunchKernelGGL((error_reduce_kernel<FAST, GV, L>), grid, dim3(256), 0, main_stream(ctx), co.rv, (long long)P, (long long)E,
+                               d_dup_off, (int)S, (int)first_sample, chunk_len, C, (int)cov, out_base, stride, off[0], off[1], off[2], off[3],
+                               off[4], off[5], off[6], off[7], ctx->d_flags, kfin, (const unsigned *)nullptr);
+        });
+    };
+    with_bool(fast, [&](auto FAST) {
+        if (G == 4) launch_general(FAST, Const<4>{});
+        else if (G == 2) launch_general(FAST, Const<2>{});
+        else launch_general(FAST, Const<1>{});
+    });
+    int rc = check_launch(ctx, "error_reduce_kernel");
+    if (rc) return rc;
+    if (splits > 1) {
+        char *merged = d_acc ? (char *)d_acc->snt : (char *)ctx->ws + off[8] * (size_t)splits;
+        const AccPtrs t = acc_ptrs(merged, off);
+        hipLaunchKernelGGL(acc_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), merged,
+                           (const char *)ctx->ws, stride, splits, (long long)P, off[0], off[1], off[2], off[3], off[4], off[5],
+                           off[6], off[7], fin.accumulate ? (const char *)d_acc->snt : (const char *)nullptr);
+        rc = check_launch(ctx, "acc_merge_kernel");
+        if (rc) return rc;
+        if (fin.packed) {
+            hipLaunchKernelGGL(acc_pack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, (long long)P,
+                               fin.packed);
+            rc = check_launch(ctx, "acc_pack_kernel");
+            if (rc) return rc;
+        }
+        if (fin.slice_len) {
+            hipLaunchKernelGGL(acc_pack_sliced_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, (long long)P, fin);
+            rc = check_launch(ctx, "acc_pack_sliced_kernel");
+            if (rc) return rc;
+        }
+        if (fin.rate) rc = launch_finalize(ctx, t, P, C, cov, fin);
+    }
+    return rc;
+}
+
+extern "C" int ampli_error_reduce(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
+                                  int32_t S, int32_t first_sample, float C, int32_t cov, const ampli_acc_table *d_acc)
+{
+    if (!d_acc) return ctx ? fail(ctx, AMPLI_E_INVALID, "error_reduce: d_acc is required") : AMPLI_E_INVALID;
+    if (!ctx) return AMPLI_E_INVALID;
+    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, first_sample, C, cov, d_acc, FinOut{});
+}
+
+extern "C" int ampli_error_estimate(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
+                                    int32_t S, float C, int32_t cov, const ampli_acc_table *d_acc, float *d_rate,
+                                    uint8_t *d_code, float *d_thr, float *d_germ_val, uint8_t *d_germ_present,
+                                    int32_t *d_flags)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_rate || !d_code) return fail(ctx, AMPLI_E_INVALID, "error_estimate: rate and code outputs are required");
+    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, 0, C, cov, d_acc,
+                             table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags));
+}
+
+extern "C" int ampli_error_reduce_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, int32_t first_sample, float C, int32_t cov,
+                                          const ampli_acc_table *d_acc, int32_t accumulate, float *d_rate, uint8_t *d_code, float *d_thr,
+                                          float *d_germ_val, uint8_t *d_germ_present, int32_t *d_flags)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    DevCohort co;
+    { int rc = cohort_from_records(ctx, recs, P, co); if (rc) return rc; }
+    if ((d_rate != nullptr) != (d_code != nullptr)) return fail(ctx, AMPLI_E_INVALID, "error_reduce_records: rate and code come together");
+    FinOut fo = table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags);
+    fo.accumulate = (accumulate & AMPLI_REDUCE_ACCUMULATE) ? 1 : 0;
+    fo.summary = (accumulate & AMPLI_REDUCE_SUMMARY) ? 1 : 0;
+    return error_reduce_impl(ctx, co, P, first_sample, C, cov, d_acc, fo);
+}
+
+// the LAST chunk of a shard's streamed cohort: table (+) chunk straight into the slice-major exchange buffers (no table -> slices pass;
+// a shard whose cohort is one chunk needs no table at all)
+extern "C" int ampli_error_reduce_records_sliced(ampli_ctx *ctx, const ampli_records *recs, int64_t P, int32_t first_sample, float C, int32_t cov,
+                                                 const ampli_acc_table *d_acc, int32_t accumulate, int32_t n_slices, double *d_sums, float *d_gm)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_sums || !d_gm || n_slices < 1) return fail(ctx, AMPLI_E_INVALID, "error_reduce_records_sliced: exchange buffers and n_slices >= 1 are required");
+    DevCohort co;
+    { int rc = cohort_from_records(ctx, recs, P, co); if (rc) return rc; }
+    FinOut fo = slice_out(ctx, P, n_slices, d_sums, d_gm);
+    fo.accumulate = (accumulate & AMPLI_REDUCE_ACCUMULATE) ? 1 : 0;
+    fo.summary = (accumulate & AMPLI_REDUCE_SUMMARY) ? 1 : 0;
+    return error_reduce_impl(ctx, co, P, first_sample, C, cov, d_acc, fo);
+}
+
+extern "C" int ampli_error_reduce_packed(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
+                                         int32_t S, int32_t first_sample, float C, int32_t cov, const ampli_acc_table *d_acc,
+                                         double *d_packed)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_acc || !d_packed) return fail(ctx, AMPLI_E_INVALID, "error_reduce_packed: table and packed buffer are required");
+    FinOut fo = {};
+    fo.packed = d_packed;
+    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, first_sample, C, cov, d_acc, fo);
+}
+
+extern "C" int ampli_error_reduce_sliced(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
+                                         int32_t S, int32_t first_sample, float C, int32_t cov, int32_t n_slices,
+                                         double *d_sums, float *d_gm)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_sums || !d_gm || n_slices < 1) return fail(ctx, AMPLI_E_INVALID, "error_reduce_sliced: exchange buffers and n_slices >= 1 are required");
+    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, first_sample, C, cov, nullptr,
+                             slice_out(ctx, P, n_slices, d_sums, d_gm));
+}
+
+// ---------------------------------------------------------------------------
+// The threshold sums in the REFERENCE's own order (round 6), for cohorts outside the exactness envelope of DESIGN 4.2.
+// Inside it every partial sum of `sum = sum + X + float(RD)*float(C)` (EE:1597, 1599) is exact, so any order and association --
+// ours: sample shards, waves, chunks -- gives the reference's double.  Outside it (a coverage cut-off of a few reads with depths
+// in the millions) the double depends on the order the reference adds in: estimateThresholds walks `equal_range` of an
+// unordered_multimap (EE:1555, 1565), which libstdc++ fills so that equal keys come out in REVERSE insertion order -- the last
+// file of the visit order first, and within a file a position's later lines before its first one.  One lane per position walks
+// exactly that: samples of the chunk from last to first, extras from last to first, then the primary record; the double is
+// updated as the reference's expression associates, (sum + X) + (double)(float(RD) * float(C)).  A cohort in several chunks is
+// walked chunk by chunk from the LAST chunk to the first with the sums carried in the table (accumulate).  Only the eight sums
+// are produced: counts, depth sums (integers in a double: exact to 2^53) and the Germ_Max state do not depend on this order.
+// Speed is irrelevant (a rerun of a cohort the fast path flagged); positions are independent, so it is still one launch.
+// ---------------------------------------------------------------------------
+template <int LAY>
+__global__ __launch_bounds__(256) void error_sums_inorder_kernel(const RecView rv, const long long P, const long long E, const int n,
+                                                                 const unsigned *__restrict__ dup_off, const float C, const int cov,
+                                                                 double *__restrict__ snt, const int accumulate)
+{
+    constexpr int RB = rec_bytes(LAY);
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    LaneAcc a;
+    lane_acc_init(a);
+    if (accumulate) {
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            a.snt[0][nt] = snt[(0 * 4 + nt) * P + p];
+            a.snt[1][nt] = snt[(1 * 4 + nt) * P + p];
+        }
+    }
+    const unsigned e0 = dup_off ? dup_off[p] : 0u, e1 = dup_off ? dup_off[p + 1] : 0u;
+    for (int t = n - 1; t >= 0; --t) {
+        for (unsigned e = e1; e > e0; --e) { // the position's later lines of this file first
+            int4 r0, r1;
+            rec_decode<LAY>(rec_load_at<LAY>(rv.ext + ((size_t)t * (size_t)rv.ext_stride + (size_t)(e - 1)) * RB), r0, r1);
+            visit_record(a, r0, r1, t, C, cov, rv.rd_ext ? rv.rd_ext[(size_t)t * (size_t)E + (e - 1)] : AMPLI_ABSENT);
+        }
+        int4 r0, r1;
+        rec_decode<LAY>(rec_load_at<LAY>(rv.base + ((size_t)t * (size_t)rv.row_stride + (size_t)p) * RB), r0, r1);
+        visit_record(a, r0, r1, t, C, cov, rv.rd ? rv.rd[(size_t)t * (size_t)P + p] : AMPLI_ABSENT);
+    }
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        snt[(0 * 4 + nt) * P + p] = a.snt[0][nt];
+        snt[(1 * 4 + nt) * P + p] = a.snt[1][nt];
+    }
+}
+
+extern "C" int ampli_error_sums_inorder(ampli_ctx *ctx, const ampli_records *recs, int64_t P, float C, int32_t cov,
+                                        const ampli_acc_table *d_acc, int32_t accumulate)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!recs || P <= 0 || cov < 1 || !d_acc || !acc_is_bound(d_acc) || d_acc->P != P) return fail(ctx, AMPLI_E_INVALID, "error_sums_inorder: bad argument");
+    DevCohort co;
+    { int rc = cohort_from_records(ctx, recs, P, co); if (rc) return rc; }
+    if (co.n <= 0 || !co.rv.base) return fail(ctx, AMPLI_E_INVALID, "error_sums_inorder: empty cohort");
+    { int rc = check_records(ctx, co, "error_sums_inorder", co.dup_off, "dup_off"); if (rc) return rc; }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    with_layout(co.layout, [&](auto L) {
+        hipLaunchKernelGGL((error_sums_inorder_kernel<L>), dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), co.rv, (long long)P,
+                           (long long)co.E, (int)co.n, co.E > 0 ? co.dup_off : nullptr, C, (int)cov, d_acc->snt, accumulate ? 1 : 0);
+    });
+    return check_launch(ctx, "error_sums_inorder_kernel");
+}
+
+// ==== merges and slices: partial tables of several launches or GPUs -> one =============================================================
+
 // dst = parts[0] (+) parts[1] (+) ... in order; parts are tables at base + i*stride
 __global__ __launch_bounds__(256) void acc_merge_kernel(char *dst_base, const char *parts_base, const size_t part_stride,
                                                         const int nparts, const long long P, const size_t o0,
@@ -1684,59 +1716,6 @@ __global__ __launch_bounds__(256) void gm_merge_kernel(int *gm_n, int *gm_first,
         n += rn;
     }
     gm_n[i] = n; gm_first[i] = first; gm_first_af[i] = first_af; gm_rest[i] = rest;
-}
-
-// ---------------------------------------------------------------------------
-// error_finalize
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void error_finalize_kernel(AccPtrs t, const long long P, const float C, const int cov, FinOut o)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    LaneAcc a;
-    lane_acc_load(t, P, p, a);
-    finalize_lane(a, P, p, C, cov, o);
-}
-
-
-// ---------------------------------------------------------------------------
-// poisson_call: one lane per record, SAMPLES_PER_BLOCK tumour samples per
-// workgroup so the position's 8 thresholds + reference code are loaded once
-// and reused from registers.
-// ---------------------------------------------------------------------------
-// finalize straight from the merged pieces of a multi-GPU reduction: the all-reduced packed sums and the gathered
-// germ-max regions (folded here in rank order); no accumulator table is read or written.
-__global__ __launch_bounds__(256) void error_finalize_merged_kernel(const double *__restrict__ pk, const char *__restrict__ regions,
-                                                                    const size_t stride, const size_t ofa, const size_t orr,
-                                                                    const int nparts, const long long P, const float C,
-                                                                    const int cov, FinOut o)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    LaneAcc a;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        a.snt[0][nt] = pk[(0 * 4 + nt) * P + p];
-        a.snt[1][nt] = pk[(1 * 4 + nt) * P + p];
-        a.srd[0][nt] = (long long)pk[8 * P + (0 * 4 + nt) * P + p];
-        a.srd[1][nt] = (long long)pk[8 * P + (1 * 4 + nt) * P + p];
-        a.cnt[nt] = (int)pk[16 * P + nt * P + p];
-        int n = 0;
-        float rest = -INFINITY;
-        for (int k = 0; k < nparts; ++k) { // ordered fold of the shards' germ-max triples (as gm_merge_kernel)
-            const char *b = regions + (size_t)k * stride;
-            const long long i = nt * P + p;
-            const int rn = ((const int *)b)[i];
-            if (rn == 0) continue;
-            const float fa = ((const float *)(b + ofa))[i], rr = ((const float *)(b + orr))[i];
-            if (n == 0) rest = rr;
-            else { if (rest <= fa) rest = fa; if (rest <= rr) rest = rr; }
-            n += rn;
-        }
-        a.gm_n[nt] = n; a.gm_rest[nt] = rest; a.gm_first[nt] = 0; a.gm_first_af[nt] = 0.0f;
-    }
-    a.nrec = (int)pk[20 * P + p];
-    finalize_lane(a, P, p, C, cov, o);
 }
 
 // ---------------------------------------------------------------------------
@@ -1839,6 +1818,230 @@ __global__ __launch_bounds__(256) void acc_pack_sliced_kernel(AccPtrs t, const l
     lane_acc_store_sliced(o, p, a);
 }
 
+extern "C" int ampli_acc_merge(ampli_ctx *ctx, const ampli_acc_table *d_dst, const ampli_acc_table *d_parts, int32_t nparts)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_dst || !d_parts || nparts < 1 || nparts > 64) return fail(ctx, AMPLI_E_INVALID, "acc_merge: 1 <= nparts <= 64");
+    const int64_t P = d_dst->P;
+    for (int i = 0; i < nparts; ++i)
+        if (d_parts[i].P != P) return fail(ctx, AMPLI_E_INVALID, "acc_merge: part table P mismatch");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "acc_merge cannot be captured (it uploads a pointer list)");
+    { int rc = ensure_ws(ctx, sizeof(AccPtrs) * 64); if (rc) return rc; }
+    AccPtrs hp[64];
+    for (int i = 0; i < nparts; ++i) hp[i] = to_ptrs(&d_parts[i]);
+    // small synchronous upload of the pointer list (not on a captured path)
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws, hp, sizeof(AccPtrs) * nparts, hipMemcpyHostToDevice, main_stream(ctx)));
+    HIP_TRY(ctx, hipStreamSynchronize(main_stream(ctx)));
+    hipLaunchKernelGGL(acc_merge_ptr_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_dst),
+                       (const AccPtrs *)ctx->ws, (int)nparts, (long long)P);
+    return check_launch(ctx, "acc_merge_ptr_kernel");
+}
+
+extern "C" int64_t ampli_acc_packed_len(int64_t P) { return P > 0 ? 21 * P : 0; }
+
+extern "C" int ampli_acc_pack(ampli_ctx *ctx, const ampli_acc_table *d_acc, double *d_packed)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_acc || d_acc->P <= 0 || !d_packed) return fail(ctx, AMPLI_E_INVALID, "acc_pack: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const long long P = d_acc->P;
+    hipLaunchKernelGGL(acc_pack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P, d_packed);
+    return check_launch(ctx, "acc_pack_kernel");
+}
+
+extern "C" int ampli_acc_unpack(ampli_ctx *ctx, const double *d_packed, const ampli_acc_table *d_acc)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_acc || d_acc->P <= 0 || !d_packed) return fail(ctx, AMPLI_E_INVALID, "acc_unpack: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const long long P = d_acc->P;
+    hipLaunchKernelGGL(acc_unpack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P, d_packed);
+    return check_launch(ctx, "acc_unpack_kernel");
+}
+
+extern "C" int ampli_acc_regions(int64_t P, size_t *sum_bytes, size_t *gm_offset, size_t *gm_bytes)
+{
+    if (P <= 0) return AMPLI_E_INVALID;
+    size_t off[9];
+    acc_offsets(P, off);
+    if (sum_bytes) *sum_bytes = off[6]; // snt|srd|cnt|nrec|gm_n
+    if (gm_offset) *gm_offset = off[4];
+    if (gm_bytes) *gm_bytes = off[5] - off[4]; // gm_n|gm_first_af|gm_rest
+    return AMPLI_OK;
+}
+
+extern "C" int ampli_gm_merge(ampli_ctx *ctx, const ampli_acc_table *d_dst, const void *d_regions, int32_t nparts)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_dst || !d_regions || nparts < 1) return fail(ctx, AMPLI_E_INVALID, "gm_merge: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const long long P = d_dst->P;
+    size_t off[9];
+    acc_offsets(P, off);
+    hipLaunchKernelGGL(gm_merge_kernel, dim3((unsigned)((4 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), d_dst->gm_n,
+                       d_dst->gm_first, d_dst->gm_first_af, d_dst->gm_rest, (const char *)d_regions, off[5] - off[4],
+                       off[6] - off[4], off[7] - off[4], (int)nparts, P);
+    return check_launch(ctx, "gm_merge_kernel");
+}
+
+extern "C" int64_t ampli_slice_len(int64_t P, int32_t n_slices)
+{
+    if (P <= 0 || n_slices < 1) return 0;
+    const int64_t per = (P + n_slices - 1) / n_slices;
+    return (per + 63) / 64 * 64;
+}
+
+extern "C" int32_t ampli_slice_planes(int32_t format) { return slice_planes(format); }
+
+extern "C" int ampli_set_slice_format(ampli_ctx *ctx, int32_t format)
+{
+    if (!ctx || (format != AMPLI_SLICE_WIDE && format != AMPLI_SLICE_SLIM)) return AMPLI_E_INVALID;
+    ctx->slice_fmt = format;
+    return AMPLI_OK;
+}
+
+extern "C" int ampli_slice_bytes_fmt(int64_t P, int32_t n_slices, int32_t format, size_t *sums_bytes, size_t *gm_bytes, size_t *block_bytes)
+{
+    const int64_t L = ampli_slice_len(P, n_slices);
+    if (L <= 0 || (format != AMPLI_SLICE_WIDE && format != AMPLI_SLICE_SLIM)) return AMPLI_E_INVALID;
+    if (sums_bytes) *sums_bytes = (size_t)n_slices * (size_t)slice_planes(format) * (size_t)L * sizeof(double);
+    if (gm_bytes) *gm_bytes = (size_t)n_slices * 8 * (size_t)L * sizeof(float);
+    if (block_bytes) *block_bytes = slice_block_bytes(L);
+    return AMPLI_OK;
+}
+
+extern "C" int ampli_slice_bytes(int64_t P, int32_t n_slices, size_t *sums_bytes, size_t *gm_bytes, size_t *block_bytes)
+{
+    return ampli_slice_bytes_fmt(P, n_slices, AMPLI_SLICE_WIDE, sums_bytes, gm_bytes, block_bytes);
+}
+
+extern "C" int ampli_acc_to_slices(ampli_ctx *ctx, const ampli_acc_table *d_acc, int32_t n_slices, double *d_sums, float *d_gm)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_acc || !acc_is_bound(d_acc) || n_slices < 1 || !d_sums || !d_gm) return fail(ctx, AMPLI_E_INVALID, "acc_to_slices: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const long long P = d_acc->P;
+    hipLaunchKernelGGL(acc_pack_sliced_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P,
+                       slice_out(ctx, P, n_slices, d_sums, d_gm));
+    return check_launch(ctx, "acc_pack_sliced_kernel");
+}
+
+extern "C" int ampli_error_finalize_slice(ampli_ctx *ctx, int64_t P, int32_t n_slices, int32_t slice_index,
+                                          const double *d_sum_slice, const float *d_gm_recv, float C, int32_t cov, void *d_block)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (P <= 0 || n_slices < 1 || slice_index < 0 || slice_index >= n_slices || !d_sum_slice || !d_gm_recv || !d_block || cov < 1)
+        return fail(ctx, AMPLI_E_INVALID, "error_finalize_slice: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const long long L = ampli_slice_len(P, n_slices);
+    const size_t G = (size_t)ctx->grp_size, g = (size_t)ctx->grp_index; // [group][planes][L] sums, [n][group][8][L] pairs, [group][block] out
+    hipLaunchKernelGGL(error_finalize_slice_kernel, dim3((unsigned)((4 * L + 255) / 256)), dim3(256), 0, main_stream(ctx),
+                       d_sum_slice + g * (size_t)slice_planes(ctx->slice_fmt) * (size_t)L, d_gm_recv + g * 8 * (size_t)L, G * 8 * (size_t)L, (int)n_slices, L,
+                       (long long)slice_index * L, (long long)P, C, (int)cov, (char *)d_block + g * slice_block_bytes(L), ctx->slice_fmt);
+    return check_launch(ctx, "error_finalize_slice_kernel");
+}
+
+extern "C" int ampli_error_table_unslice(ampli_ctx *ctx, int64_t P, int32_t n_slices, const void *d_blocks, float *d_rate,
+                                         uint8_t *d_code, float *d_thr, float *d_germ_val, uint8_t *d_germ_present,
+                                         int32_t *d_flags)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (P <= 0 || n_slices < 1 || !d_blocks || !d_rate || !d_code) return fail(ctx, AMPLI_E_INVALID, "error_table_unslice: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const long long L = ampli_slice_len(P, n_slices);
+    hipLaunchKernelGGL(error_table_unslice_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx),
+                       (const char *)d_blocks + (size_t)ctx->grp_index * slice_block_bytes(L), (size_t)ctx->grp_size * slice_block_bytes(L),
+                       (int)n_slices, L, (long long)P, table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags));
+    return check_launch(ctx, "error_table_unslice_kernel");
+}
+
+// ==== finalize: accumulator table -> error table =======================================================================================
+
+__global__ __launch_bounds__(256) void error_finalize_kernel(AccPtrs t, const long long P, const float C, const int cov, FinOut o)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    LaneAcc a;
+    lane_acc_load(t, P, p, a);
+    finalize_lane(a, P, p, C, cov, o);
+}
+
+// finalize straight from the merged pieces of a multi-GPU reduction: the all-reduced packed sums and the gathered
+// germ-max regions (folded here in rank order); no accumulator table is read or written.
+__global__ __launch_bounds__(256) void error_finalize_merged_kernel(const double *__restrict__ pk, const char *__restrict__ regions,
+                                                                    const size_t stride, const size_t ofa, const size_t orr,
+                                                                    const int nparts, const long long P, const float C,
+                                                                    const int cov, FinOut o)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    LaneAcc a;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        a.snt[0][nt] = pk[(0 * 4 + nt) * P + p];
+        a.snt[1][nt] = pk[(1 * 4 + nt) * P + p];
+        a.srd[0][nt] = (long long)pk[8 * P + (0 * 4 + nt) * P + p];
+        a.srd[1][nt] = (long long)pk[8 * P + (1 * 4 + nt) * P + p];
+        a.cnt[nt] = (int)pk[16 * P + nt * P + p];
+        int n = 0;
+        float rest = -INFINITY;
+        for (int k = 0; k < nparts; ++k) { // ordered fold of the shards' germ-max triples (as gm_merge_kernel)
+            const char *b = regions + (size_t)k * stride;
+            const long long i = nt * P + p;
+            const int rn = ((const int *)b)[i];
+            if (rn == 0) continue;
+            const float fa = ((const float *)(b + ofa))[i], rr = ((const float *)(b + orr))[i];
+            if (n == 0) rest = rr;
+            else { if (rest <= fa) rest = fa; if (rest <= rr) rest = rr; }
+            n += rn;
+        }
+        a.gm_n[nt] = n; a.gm_rest[nt] = rest; a.gm_first[nt] = 0; a.gm_first_af[nt] = 0.0f;
+    }
+    a.nrec = (int)pk[20 * P + p];
+    finalize_lane(a, P, p, C, cov, o);
+}
+
+static int launch_finalize(ampli_ctx *ctx, const AccPtrs &t, long long P, float C, int cov, const FinOut &fo)
+{
+    hipLaunchKernelGGL(error_finalize_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, P, C, cov, fo);
+    return check_launch(ctx, "error_finalize_kernel");
+}
+
+extern "C" int ampli_error_finalize(ampli_ctx *ctx, const ampli_acc_table *d_acc, float C, int32_t cov, float *d_rate,
+                                    uint8_t *d_code, float *d_thr, float *d_germ_val, uint8_t *d_germ_present,
+                                    int32_t *d_flags)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!d_acc || d_acc->P <= 0 || !d_rate || !d_code || cov < 1) return fail(ctx, AMPLI_E_INVALID, "error_finalize: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    return launch_finalize(ctx, to_ptrs(d_acc), d_acc->P, C, (int)cov, table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags));
+}
+
+extern "C" int ampli_error_finalize_merged(ampli_ctx *ctx, int64_t P, const double *d_packed, const void *d_gm_regions,
+                                           int32_t nparts, float C, int32_t cov, float *d_rate, uint8_t *d_code, float *d_thr,
+                                           float *d_germ_val, uint8_t *d_germ_present, int32_t *d_flags)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (P <= 0 || !d_packed || !d_gm_regions || nparts < 1 || !d_rate || !d_code || cov < 1)
+        return fail(ctx, AMPLI_E_INVALID, "error_finalize_merged: bad argument");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    size_t off[9];
+    acc_offsets(P, off);
+    hipLaunchKernelGGL(error_finalize_merged_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), d_packed,
+                       (const char *)d_gm_regions, off[5] - off[4], off[6] - off[4], off[7] - off[4], (int)nparts, (long long)P, C,
+                       (int)cov, table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags));
+    return check_launch(ctx, "error_finalize_merged_kernel");
+}
+
+// ==== Poisson: tumour records + thresholds -> calls ====================================================================================
+
+// ---------------------------------------------------------------------------
+// poisson_call: one lane per record, SAMPLES_PER_BLOCK tumour samples per
+// workgroup so the position's 8 thresholds + reference code are loaded once
+// and reused from registers.
+// ---------------------------------------------------------------------------
+
 // Compact call list, sharded: a returning atomic on ONE word serialises at ~11 ns per add (about 90 per us chip-wide,
 // MI355X_MICROARCH.md "dequeue"), which at a few thousand calls per launch would bound the whole kernel.  The list is
 // therefore AMPLI_CALL_SHARDS independent segments, each with its own counter on its own 128-byte line; a workgroup
@@ -1883,7 +2086,7 @@ __global__ __launch_bounds__(256) void poisson_call_kernel(
     unsigned char *__restrict__ call_mask, ampli_call *__restrict__ calls, const long long capacity,
     unsigned long long *__restrict__ n_calls, double *__restrict__ qd, float *__restrict__ afd, const double *__restrict__ lgtab)
 {
-    constexpr int RB = rec_bytes_of<LAY>();
+    constexpr int RB = rec_bytes(LAY);
     const long long R = P + E;
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= R) return;
@@ -1994,7 +2197,7 @@ __global__ __launch_bounds__(256, 4) void poisson_full_kernel(
     unsigned char *__restrict__ call_mask, ampli_call *__restrict__ calls, const long long capacity,
     unsigned long long *__restrict__ n_calls, double *__restrict__ qd, const double *__restrict__ lgtab)
 {
-    constexpr int RB = rec_bytes_of<LAY>();
+    constexpr int RB = rec_bytes(LAY);
     __shared__ PfItem items[2][PF_LIST]; // [0] series, [1] long continued fractions; a full list sends its item back to be scored in place
     __shared__ double res[256 * 6];      // by owning thread and score slot (the three alternatives x two strands)
     __shared__ int n_list[2];
@@ -2180,7 +2383,7 @@ __global__ __launch_bounds__(256, 7) void poisson_stream_kernel(
 {
     // records [r_lo, r_hi) of every sample's R = P + E (the whole row, or one range of a context with position ranges: r_lo a
     // multiple of 64, the call list's shards [shard_lo, shard_lo + shard_n) are this launch's)
-    constexpr int RB = rec_bytes_of<LAY>();
+    constexpr int RB = rec_bytes(LAY);
     __shared__ PcItem stage[4][PC_STAGE];
     int staged = 0; // wave-uniform
     const int lane = threadIdx.x & 63;
@@ -2401,695 +2604,6 @@ __global__ void lgamma_table_kernel(double *t, const int n)
     if (i < n) t[i] = ampli_kf_lgamma((double)i);
 }
 
-__global__ void score_dense_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, const double *lgtab)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) q[i] = ampli_poisson_score_dense(k[i], rd[i], err[i], lgtab, AMPLI_LGTAB);
-}
-
-__global__ void score_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, double *pv)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (q) q[i] = ampli_poisson_score(k[i], rd[i], err[i]);
-    if (pv) pv[i] = err[i] == -1 ? -1.0 : ampli_poisson_p(k[i], rd[i], err[i]);
-}
-
-__global__ void roundtrip_batch_kernel(const float *in, const long long n, float *out)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = ampli_text_roundtrip(in[i]);
-}
-
-__global__ void synth_fill_kernel(int4 *recs, const long long P, const int n_samples, const int first_sample,
-                                  const unsigned long long seed, const int depth, const int tumour)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int s = blockIdx.y;
-    if (p >= P || s >= n_samples) return;
-    int rec[8];
-    ampli_synth_record(seed, (uint64_t)p, (uint64_t)(first_sample + s), depth, tumour, rec);
-    const size_t o = ((size_t)s * P + p) * 2;
-    recs[o] = make_int4(rec[0], rec[1], rec[2], rec[3]);
-    recs[o + 1] = make_int4(rec[4], rec[5], rec[6], rec[7]);
-}
-
-// 8 x int32 records -> 8 x uint16 records (AMPLI_ABSENT -> 0xFFFF); *overflow is raised for a count above 65534
-__global__ __launch_bounds__(256) void records_pack16_kernel(const int4 *__restrict__ in, const long long n, uint4 *__restrict__ out,
-                                                             int *__restrict__ overflow)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int4 a = in[i * 2], b = in[i * 2 + 1];
-    const bool absent = a.x == AMPLI_ABSENT;
-    const unsigned v[8] = {absent ? 0xFFFFu : (unsigned)a.x, (unsigned)a.y, (unsigned)a.z, (unsigned)a.w,
-                           (unsigned)b.x, (unsigned)b.y, (unsigned)b.z, (unsigned)b.w};
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bad |= (j == 0 && absent) ? false : v[j] > 65534u;
-    if (bad) atomicOr(overflow, 1);
-    out[i] = make_uint4((v[0] & 0xFFFFu) | (v[1] << 16), (v[2] & 0xFFFFu) | (v[3] << 16), (v[4] & 0xFFFFu) | (v[5] << 16),
-                        (v[6] & 0xFFFFu) | (v[7] << 16));
-}
-
-// 8 x int32 records -> 8 x 24-bit records (AMPLI_ABSENT -> 0xFFFFFF); *overflow is raised for a count above 2^24 - 2
-__global__ __launch_bounds__(256) void records_pack24_kernel(const int4 *__restrict__ in, const long long n, uint2 *__restrict__ out,
-                                                             int *__restrict__ overflow)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int4 a = in[i * 2], b = in[i * 2 + 1];
-    const bool absent = a.x == AMPLI_ABSENT;
-    const unsigned v[8] = {absent ? 0xFFFFFFu : (unsigned)a.x, (unsigned)a.y, (unsigned)a.z, (unsigned)a.w,
-                           (unsigned)b.x, (unsigned)b.y, (unsigned)b.z, (unsigned)b.w};
-    bool bad = false;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) bad |= (j == 0 && absent) ? false : v[j] > 0xFFFFFEu;
-    if (bad) atomicOr(overflow, 1);
-    unsigned w[6];
-#pragma unroll
-    for (int h = 0; h < 2; ++h) { // four 24-bit fields -> three dwords
-        const unsigned f0 = v[4 * h] & 0xFFFFFFu, f1 = v[4 * h + 1] & 0xFFFFFFu, f2 = v[4 * h + 2] & 0xFFFFFFu, f3 = v[4 * h + 3] & 0xFFFFFFu;
-        w[3 * h] = f0 | (f1 << 24);
-        w[3 * h + 1] = (f1 >> 8) | (f2 << 16);
-        w[3 * h + 2] = (f2 >> 16) | (f3 << 8);
-    }
-    out[i * 3] = make_uint2(w[0], w[1]);
-    out[i * 3 + 1] = make_uint2(w[2], w[3]);
-    out[i * 3 + 2] = make_uint2(w[4], w[5]);
-}
-
-__global__ void synth_ref_kernel(unsigned char *ref, const long long P, const unsigned long long seed)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < P) ref[p] = (unsigned char)ampli_synth_ref_base(seed, (uint64_t)p);
-}
-
-// ---------------------------------------------------------------------------
-// host entry points
-// ---------------------------------------------------------------------------
-static int ensure_ws(ampli_ctx *ctx, size_t bytes)
-{
-    if (ctx->ws_bytes >= bytes) return AMPLI_OK;
-    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "workspace would have to grow while capturing: run the sequence once first");
-    if (ctx->ws) { HIP_TRY(ctx, hipStreamSynchronize(main_stream(ctx))); (void)hipFree(ctx->ws); ctx->ws = nullptr; ctx->ws_bytes = 0; }
-    if (hipMalloc(&ctx->ws, bytes) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "workspace hipMalloc failed");
-    ctx->ws_bytes = bytes;
-    return AMPLI_OK;
-}
-
-// a bound table must be one buffer carved by ampli_acc_bind
-static bool acc_is_bound(const ampli_acc_table *t)
-{
-    if (!t || !t->snt || t->P <= 0) return false;
-    size_t off[9];
-    acc_offsets(t->P, off);
-    const char *b = (const char *)t->snt;
-    return (const char *)t->srd == b + off[1] && (const char *)t->cnt == b + off[2] && (const char *)t->nrec == b + off[3] &&
-           (const char *)t->gm_n == b + off[4] && (const char *)t->gm_first == b + off[5] &&
-           (const char *)t->gm_first_af == b + off[6] && (const char *)t->gm_rest == b + off[7];
-}
-
-static AccPtrs to_ptrs(const ampli_acc_table *t)
-{
-    AccPtrs a;
-    a.snt = t->snt; a.srd = (long long *)t->srd; a.cnt = t->cnt; a.nrec = t->nrec; a.gm_n = t->gm_n;
-    a.gm_first = t->gm_first; a.gm_first_af = t->gm_first_af; a.gm_rest = t->gm_rest;
-    return a;
-}
-
-static int launch_finalize(ampli_ctx *ctx, const AccPtrs &t, long long P, float C, int cov, const FinOut &fo)
-{
-    hipLaunchKernelGGL(error_finalize_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, P, C, cov, fo);
-    return check_launch(ctx, "error_finalize_kernel");
-}
-
-// what the kernels read: a cohort (or one chunk of a streamed one) resident on the device
-struct DevCohort {
-    RecView rv;
-    int layout;   // AMPLI_RECORDS_*
-    int n;        // samples
-    long long E;  // extra-occurrence slots per sample
-    const unsigned *dup_off; // [P+1]: extras of position p are e in [dup_off[p], dup_off[p+1])   (error_reduce)
-    const unsigned *ext_pos; // [E]: position of extra e                                          (poisson_call)
-};
-
-static size_t rec_bytes_rt(int layout) { return layout == AMPLI_RECORDS_U24 ? 24 : (layout == AMPLI_RECORDS_U16 ? 16 : 32); }
-
-// the dense interchange layout [n][P+E] in the context's record layout (the classic entry points)
-static DevCohort dense_cohort(const ampli_ctx *ctx, const void *d_recs, int64_t P, int64_t E, int n, const uint32_t *dup_off,
-                              const uint32_t *ext_pos)
-{
-    DevCohort c;
-    c.layout = ctx->rec_layout;
-    c.rv.base = (const char *)d_recs;
-    c.rv.row_stride = P + E;
-    c.rv.ext = (const char *)d_recs + (size_t)P * rec_bytes_rt(c.layout);
-    c.rv.ext_stride = P + E;
-    c.rv.rd = nullptr; c.rv.rd_ext = nullptr;
-    c.n = n; c.E = E; c.dup_off = dup_off; c.ext_pos = ext_pos;
-    return c;
-}
-
-static int cohort_from_records(ampli_ctx *ctx, const ampli_records *r, int64_t P, DevCohort &c)
-{
-    if (!r || !r->recs || r->n_samples <= 0 || r->E < 0) return fail(ctx, AMPLI_E_INVALID, "records: recs, n_samples > 0 and E >= 0 are required");
-    if (r->layout != AMPLI_RECORDS_I32 && r->layout != AMPLI_RECORDS_U16 && r->layout != AMPLI_RECORDS_U24)
-        return fail(ctx, AMPLI_E_INVALID, "records: unknown layout");
-    c.layout = r->layout;
-    c.n = r->n_samples;
-    c.E = r->E;
-    c.dup_off = r->dup_off; c.ext_pos = r->ext_pos;
-    c.rv.rd = r->rd;
-    c.rv.rd_ext = r->rd_ext;
-    c.rv.base = (const char *)r->recs;
-    c.rv.row_stride = r->row_stride > 0 ? r->row_stride : (r->ext ? P : P + r->E);
-    if (r->ext) {
-        c.rv.ext = (const char *)r->ext;
-        c.rv.ext_stride = r->ext_stride > 0 ? r->ext_stride : r->E;
-        if (c.rv.row_stride < P || c.rv.ext_stride < r->E) return fail(ctx, AMPLI_E_INVALID, "records: row_stride < P or ext_stride < E");
-    } else {
-        c.rv.ext = c.rv.base + (size_t)P * rec_bytes_rt(c.layout);
-        c.rv.ext_stride = c.rv.row_stride;
-        if (c.rv.row_stride < P + r->E) return fail(ctx, AMPLI_E_INVALID, "records: row_stride < P + E");
-    }
-    return AMPLI_OK;
-}
-
-// reduce (+ optional fused finalize).  d_acc may be NULL when fin.rate is set (the table is then not materialised
-// unless the sample axis has to be split across workgroups).
-static int error_reduce_impl(ampli_ctx *ctx, const DevCohort &co, int64_t P, int32_t first_sample, float C, int32_t cov,
-                             const ampli_acc_table *d_acc, const FinOut &fin)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    const int64_t E = co.E;
-    const int32_t S = co.n;
-    const uint32_t *d_dup_off = co.dup_off;
-    if (!co.rv.base || P <= 0 || E < 0 || S <= 0 || cov < 1 || (d_acc && (!acc_is_bound(d_acc) || d_acc->P != P)) || (!d_acc && !fin.rate && !fin.slice_len) || (fin.packed && !d_acc))
-        return fail(ctx, AMPLI_E_INVALID, "error_reduce: bad argument (P,S>0, cov>=1, table bound with ampli_acc_bind for the same P)");
-    if (fin.accumulate && !d_acc) return fail(ctx, AMPLI_E_INVALID, "error_reduce: accumulate needs the table");
-    if (E > 0 && !d_dup_off) return fail(ctx, AMPLI_E_INVALID, "error_reduce: E > 0 needs dup_off");
-    {
-        const uintptr_t am = co.layout == AMPLI_RECORDS_U24 ? 7 : 15;
-        if (((uintptr_t)co.rv.base & am) != 0 || (E > 0 && ((uintptr_t)co.rv.ext & am) != 0))
-            return fail(ctx, AMPLI_E_INVALID, "error_reduce: recs must be 16-byte aligned (8-byte for the 24-byte layout)");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-
-    // lane groups per wave: only for panels too small to fill the chip with 64-position waves (measured on c3:
-    // G = 2 / 4 cost 6 % / 11 % -- the narrower per-row segments outweigh the shorter tail)
-    const long long resident_waves = (long long)ctx->n_cu * 16;
-    const bool fast = !ctx->reduce_general && !co.rv.rd && !co.rv.rd_ext; // lines with their own RD column: the literal kernel
-    // the shape error_reduce_u16_kernel takes (below).  From one tile per CU on it beats every cut of the general kernel along
-    // lanes or samples (tools/sweep_tiles.py: 48 us against 62 at 768 tiles, 69 against 102 at 1280), so such a launch is not cut
-    const bool compact_shape = ctx->reduce_compact && fast && (!d_acc || fin.summary) && !fin.packed &&
-                               ((co.layout == AMPLI_RECORDS_U16 && S <= RED_WAVES * FAST_MAX_CHUNK) ||
-                                (co.layout == AMPLI_RECORDS_U24 && S <= RED_WAVES * COMPACT_MAX_REC_U24 && !ctx->reduce_compact_u16_only));
-    const bool compact_uncut = compact_shape && (P + 63) / 64 >= ctx->n_cu;
-    int G = ctx->reduce_groups;
-    if (G != 1 && G != 2 && G != 4) {
-        G = 1;
-        while (!compact_uncut && G < 4 && ((P + 64 / G - 1) / (64 / G)) * RED_WAVES < resident_waves && S / (RED_WAVES * 2 * G) >= 8) G *= 2;
-    }
-    const long long tiles = (P + 64 / G - 1) / (64 / G);
-    // sample splits: enough waves to fill the chip (>= ~24 waves per CU), each lane group with >= 8 samples
-    int splits = ctx->reduce_splits;
-    if (splits <= 0 && compact_uncut && G == 1) {
-        splits = 1;
-    } else if (splits <= 0) {
-        const long long want_waves = (long long)ctx->n_cu * 24;
-        splits = (int)((want_waves + tiles * RED_WAVES - 1) / (tiles * RED_WAVES));
-        const int max_splits = (S + RED_WAVES * G * 8 - 1) / (RED_WAVES * G * 8);
-        if (splits > max_splits) splits = max_splits;
-        if (splits < 1) splits = 1;
-    }
-    if (splits > S) splits = S;
-    if (fast) { // int32 partial sums: a lane takes at most FAST_MAX_CHUNK samples
-        const int need = (S + RED_WAVES * G * FAST_MAX_CHUNK - 1) / (RED_WAVES * G * FAST_MAX_CHUNK);
-        if (splits < need) splits = need;
-    }
-    const int chunks = splits * RED_WAVES * G;
-    const int chunk_len = (S + chunks - 1) / chunks;
-
-    size_t off[9];
-    acc_offsets(P, off);
-    char *out_base = d_acc ? (char *)d_acc->snt : nullptr;
-    size_t stride = 0;
-    FinOut kfin = fin; // what the reduce kernel itself finalises
-    if (splits > 1) {
-        // partial tables, one per split, plus one slot for the merged table when the caller did not ask for it
-        int rc = ensure_ws(ctx, off[8] * (size_t)(splits + 1));
-        if (rc) return rc;
-        out_base = (char *)ctx->ws;
-        stride = off[8];
-        kfin.rate = nullptr;
-        kfin.packed = nullptr; // packed after the merge, below
-        kfin.slice_len = 0;
-        kfin.accumulate = 0;   // folded in by the merge kernel, below
-    }
-    if (splits > 65535 || tiles > 0x7fffffffll) return fail(ctx, AMPLI_E_RANGE, "error_reduce: panel or sample count beyond the grid limits");
-    ctx->last_reduce_kernel = (compact_shape && G == 1 && splits == 1) ? (co.layout == AMPLI_RECORDS_U24 ? 2 : 1) : 0;
-    if (ctx->last_reduce_kernel) {
-        AccPtrs tab = {};
-        if (d_acc) tab = to_ptrs(d_acc);
-        const int clen = (S + RED_WAVES - 1) / RED_WAVES;
-#define AMPLI_LAUNCH_CK(KERNEL, DUPV, TABV, ST, LO, HI)                                                                                            \
-    hipLaunchKernelGGL((KERNEL<DUPV, TABV>), dim3((unsigned)(((HI) - (LO) + 63) / 64)), dim3(256), 0, ST, co.rv, (long long)P,                      \
-                       (long long)(LO), (long long)(HI), d_dup_off, (int)S, clen, C, (int)cov, ctx->d_flags, tab, fin)
-#define AMPLI_LAUNCH_U16(DUPV, TABV, ST, LO, HI)                                                                                                   \
-    do {                                                                                                                                           \
-        if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_CK(error_reduce_u24_kernel, DUPV, TABV, ST, LO, HI);                                      \
-        else AMPLI_LAUNCH_CK(error_reduce_u16_kernel, DUPV, TABV, ST, LO, HI);                                                                     \
-    } while (0)
-        if (E > 0) {
-            // the tiles with a position listed more than once go to the general kernel (at most one such tile per extra slot)
-            hipStream_t st = main_stream(ctx);
-            const long long ntiles = (P + 63) / 64;
-            int rcw = ensure_ws(ctx, (size_t)(ntiles + 1) * sizeof(unsigned));
-            if (rcw) return rcw;
-            unsigned *list = (unsigned *)ctx->ws;
-            HIP_TRY(ctx, hipMemsetAsync(list, 0, sizeof(unsigned), st));
-            hipLaunchKernelGGL(dup_tiles_kernel, dim3((unsigned)((ntiles + 255) / 256)), dim3(256), 0, st, d_dup_off, (long long)P, list);
-            if (d_acc) AMPLI_LAUNCH_U16(true, true, st, 0, P); else AMPLI_LAUNCH_U16(true, false, st, 0, P);
-            int rcc = check_launch(ctx, "error_reduce_u16_kernel");
-            if (rcc) return rcc;
-#define AMPLI_LAUNCH_DUPTILES(LV)                                                                                                                   \
-    hipLaunchKernelGGL((error_reduce_kernel<true, 1, LV>), dim3((unsigned)std::min<long long>(E, ntiles)), dim3(256), 0, st, co.rv, (long long)P,    \
-                       (long long)E, d_dup_off, (int)S, (int)first_sample, clen, C, (int)cov, d_acc ? (char *)d_acc->snt : (char *)nullptr, (size_t)0, \
-                       off[0], off[1], off[2], off[3], off[4], off[5], off[6], off[7], ctx->d_flags, fin, (const unsigned *)list)
-            if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_DUPTILES(AMPLI_RECORDS_U24); else AMPLI_LAUNCH_DUPTILES(AMPLI_RECORDS_U16);
-#undef AMPLI_LAUNCH_DUPTILES
-            return check_launch(ctx, "error_reduce_kernel (tiles with positions listed more than once)");
-        }
-        if (ranges_apply(ctx, P)) { // position ranges on concurrent streams (ampli_set_ranges)
-            int rcf = ranges_fork(ctx, P);
-            if (rcf) return rcf;
-            long long cut[AMPLI_MAX_RANGES + 1];
-            range_cuts(P, ctx->n_ranges, cut);
-            for (int k = 0; k < ctx->n_ranges; ++k) {
-                hipStream_t st = lane_stream(ctx, k);
-                if (d_acc) AMPLI_LAUNCH_U16(false, true, st, cut[k], cut[k + 1]); else AMPLI_LAUNCH_U16(false, false, st, cut[k], cut[k + 1]);
-            }
-            return check_launch(ctx, "error_reduce_u16_kernel");
-        }
-        hipStream_t st = main_stream(ctx);
-        if (d_acc) AMPLI_LAUNCH_U16(false, true, st, 0, P); else AMPLI_LAUNCH_U16(false, false, st, 0, P);
-#undef AMPLI_LAUNCH_U16
-#undef AMPLI_LAUNCH_CK
-        return check_launch(ctx, "error_reduce_u16_kernel");
-    }
-    dim3 grid((unsigned)tiles, (unsigned)splits);
-#define AMPLI_LAUNCH_REDUCE_L(FASTV, GV, UV)                                                                                      \
-    hipLaunchKernelGGL((error_reduce_kernel<FASTV, GV, UV>), grid, dim3(256), 0, main_stream(ctx), co.rv, (long long)P, \
-                       (long long)E, d_dup_off, (int)S, (int)first_sample, chunk_len, C, (int)cov, out_base, stride, off[0],  \
-                       off[1], off[2], off[3], off[4], off[5], off[6], off[7], ctx->d_flags, kfin, (const unsigned *)nullptr)
-#define AMPLI_LAUNCH_REDUCE(FASTV, GV)                           \
-    do {                                                         \
-        if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_REDUCE_L(FASTV, GV, AMPLI_RECORDS_U24);      \
-        else if (co.layout == AMPLI_RECORDS_U16) AMPLI_LAUNCH_REDUCE_L(FASTV, GV, AMPLI_RECORDS_U16); \
-        else AMPLI_LAUNCH_REDUCE_L(FASTV, GV, AMPLI_RECORDS_I32);                                           \
-    } while (0)
-    if (fast) {
-        if (G == 4) AMPLI_LAUNCH_REDUCE(true, 4);
-        else if (G == 2) AMPLI_LAUNCH_REDUCE(true, 2);
-        else AMPLI_LAUNCH_REDUCE(true, 1);
-    } else {
-        if (G == 4) AMPLI_LAUNCH_REDUCE(false, 4);
-        else if (G == 2) AMPLI_LAUNCH_REDUCE(false, 2);
-        else AMPLI_LAUNCH_REDUCE(false, 1);
-    }
-#undef AMPLI_LAUNCH_REDUCE
-#undef AMPLI_LAUNCH_REDUCE_L
-    int rc = check_launch(ctx, "error_reduce_kernel");
-    if (rc) return rc;
-    if (splits > 1) {
-        char *merged = d_acc ? (char *)d_acc->snt : (char *)ctx->ws + off[8] * (size_t)splits;
-        hipLaunchKernelGGL(acc_merge_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), merged,
-                           (const char *)ctx->ws, stride, splits, (long long)P, off[0], off[1], off[2], off[3], off[4], off[5],
-                           off[6], off[7], fin.accumulate ? (const char *)d_acc->snt : (const char *)nullptr);
-        rc = check_launch(ctx, "acc_merge_kernel");
-        if (rc) return rc;
-        if (fin.packed) {
-            hipLaunchKernelGGL(acc_pack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc),
-                               (long long)P, fin.packed);
-            rc = check_launch(ctx, "acc_pack_kernel");
-            if (rc) return rc;
-        }
-        if (fin.slice_len) {
-            AccPtrs t;
-            t.snt = (double *)(merged + off[0]); t.srd = (long long *)(merged + off[1]); t.cnt = (int *)(merged + off[2]);
-            t.nrec = (int *)(merged + off[3]); t.gm_n = (int *)(merged + off[4]); t.gm_first = (int *)(merged + off[5]);
-            t.gm_first_af = (float *)(merged + off[6]); t.gm_rest = (float *)(merged + off[7]);
-            hipLaunchKernelGGL(acc_pack_sliced_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, (long long)P, fin);
-            rc = check_launch(ctx, "acc_pack_sliced_kernel");
-            if (rc) return rc;
-        }
-        if (fin.rate) {
-            AccPtrs t;
-            t.snt = (double *)(merged + off[0]); t.srd = (long long *)(merged + off[1]); t.cnt = (int *)(merged + off[2]);
-            t.nrec = (int *)(merged + off[3]); t.gm_n = (int *)(merged + off[4]); t.gm_first = (int *)(merged + off[5]);
-            t.gm_first_af = (float *)(merged + off[6]); t.gm_rest = (float *)(merged + off[7]);
-            rc = launch_finalize(ctx, t, P, C, cov, fin);
-        }
-    }
-    return rc;
-}
-
-extern "C" int ampli_error_reduce(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
-                                  int32_t S, int32_t first_sample, float C, int32_t cov, const ampli_acc_table *d_acc)
-{
-    if (!d_acc) return ctx ? fail(ctx, AMPLI_E_INVALID, "error_reduce: d_acc is required") : AMPLI_E_INVALID;
-    if (!ctx) return AMPLI_E_INVALID;
-    FinOut none = {};
-    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, first_sample, C, cov, d_acc, none);
-}
-
-extern "C" int ampli_error_estimate(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
-                                    int32_t S, float C, int32_t cov, const ampli_acc_table *d_acc, float *d_rate,
-                                    uint8_t *d_code, float *d_thr, float *d_germ_val, uint8_t *d_germ_present,
-                                    int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_rate || !d_code) return fail(ctx, AMPLI_E_INVALID, "error_estimate: rate and code outputs are required");
-    FinOut fo = {};
-    fo.rate = d_rate; fo.code = d_code; fo.thr = d_thr; fo.germ_val = d_germ_val; fo.germ_present = d_germ_present; fo.flags = d_flags;
-    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, 0, C, cov, d_acc, fo);
-}
-
-extern "C" int ampli_error_reduce_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, int32_t first_sample, float C, int32_t cov,
-                                          const ampli_acc_table *d_acc, int32_t accumulate, float *d_rate, uint8_t *d_code, float *d_thr,
-                                          float *d_germ_val, uint8_t *d_germ_present, int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    DevCohort co;
-    int rc = cohort_from_records(ctx, recs, P, co);
-    if (rc) return rc;
-    if ((d_rate != nullptr) != (d_code != nullptr)) return fail(ctx, AMPLI_E_INVALID, "error_reduce_records: rate and code come together");
-    FinOut fo = {};
-    fo.rate = d_rate; fo.code = d_code; fo.thr = d_thr; fo.germ_val = d_germ_val; fo.germ_present = d_germ_present; fo.flags = d_flags;
-    fo.accumulate = (accumulate & AMPLI_REDUCE_ACCUMULATE) ? 1 : 0;
-    fo.summary = (accumulate & AMPLI_REDUCE_SUMMARY) ? 1 : 0;
-    return error_reduce_impl(ctx, co, P, first_sample, C, cov, d_acc, fo);
-}
-
-// the LAST chunk of a shard's streamed cohort: table (+) chunk straight into the slice-major exchange buffers (no table -> slices pass;
-// a shard whose cohort is one chunk needs no table at all)
-extern "C" int ampli_error_reduce_records_sliced(ampli_ctx *ctx, const ampli_records *recs, int64_t P, int32_t first_sample, float C, int32_t cov,
-                                                 const ampli_acc_table *d_acc, int32_t accumulate, int32_t n_slices, double *d_sums, float *d_gm)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_sums || !d_gm || n_slices < 1) return fail(ctx, AMPLI_E_INVALID, "error_reduce_records_sliced: exchange buffers and n_slices >= 1 are required");
-    DevCohort co;
-    int rc = cohort_from_records(ctx, recs, P, co);
-    if (rc) return rc;
-    FinOut fo = {};
-    fo.accumulate = (accumulate & AMPLI_REDUCE_ACCUMULATE) ? 1 : 0;
-    fo.summary = (accumulate & AMPLI_REDUCE_SUMMARY) ? 1 : 0;
-    fo.slice_len = ampli_slice_len(P, n_slices);
-    fo.sl_group = ctx->grp_size;
-    fo.sl_fmt = ctx->slice_fmt; fo.sl_n = n_slices; fo.sl_flags = ctx->d_flags;
-    fo.sl_sums = d_sums + (size_t)ctx->grp_index * slice_planes(fo.sl_fmt) * (size_t)fo.slice_len;
-    fo.sl_gm = d_gm + (size_t)ctx->grp_index * 8 * (size_t)fo.slice_len;
-    return error_reduce_impl(ctx, co, P, first_sample, C, cov, d_acc, fo);
-}
-
-extern "C" int ampli_error_reduce_packed(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
-                                         int32_t S, int32_t first_sample, float C, int32_t cov, const ampli_acc_table *d_acc,
-                                         double *d_packed)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || !d_packed) return fail(ctx, AMPLI_E_INVALID, "error_reduce_packed: table and packed buffer are required");
-    FinOut fo = {};
-    fo.packed = d_packed;
-    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, first_sample, C, cov, d_acc, fo);
-}
-
-extern "C" int ampli_error_finalize_merged(ampli_ctx *ctx, int64_t P, const double *d_packed, const void *d_gm_regions,
-                                           int32_t nparts, float C, int32_t cov, float *d_rate, uint8_t *d_code, float *d_thr,
-                                           float *d_germ_val, uint8_t *d_germ_present, int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (P <= 0 || !d_packed || !d_gm_regions || nparts < 1 || !d_rate || !d_code || cov < 1)
-        return fail(ctx, AMPLI_E_INVALID, "error_finalize_merged: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off[9];
-    acc_offsets(P, off);
-    FinOut fo = {};
-    fo.rate = d_rate; fo.code = d_code; fo.thr = d_thr; fo.germ_val = d_germ_val; fo.germ_present = d_germ_present; fo.flags = d_flags;
-    hipLaunchKernelGGL(error_finalize_merged_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), d_packed,
-                       (const char *)d_gm_regions, off[5] - off[4], off[6] - off[4], off[7] - off[4], (int)nparts, (long long)P, C,
-                       (int)cov, fo);
-    return check_launch(ctx, "error_finalize_merged_kernel");
-}
-
-extern "C" int64_t ampli_slice_len(int64_t P, int32_t n_slices)
-{
-    if (P <= 0 || n_slices < 1) return 0;
-    const int64_t per = (P + n_slices - 1) / n_slices;
-    return (per + 63) / 64 * 64;
-}
-
-extern "C" int32_t ampli_slice_planes(int32_t format) { return slice_planes(format); }
-
-extern "C" int ampli_set_slice_format(ampli_ctx *ctx, int32_t format)
-{
-    if (!ctx || (format != AMPLI_SLICE_WIDE && format != AMPLI_SLICE_SLIM)) return AMPLI_E_INVALID;
-    ctx->slice_fmt = format;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_slice_bytes_fmt(int64_t P, int32_t n_slices, int32_t format, size_t *sums_bytes, size_t *gm_bytes, size_t *block_bytes)
-{
-    const int64_t L = ampli_slice_len(P, n_slices);
-    if (L <= 0 || (format != AMPLI_SLICE_WIDE && format != AMPLI_SLICE_SLIM)) return AMPLI_E_INVALID;
-    if (sums_bytes) *sums_bytes = (size_t)n_slices * (size_t)slice_planes(format) * (size_t)L * sizeof(double);
-    if (gm_bytes) *gm_bytes = (size_t)n_slices * 8 * (size_t)L * sizeof(float);
-    if (block_bytes) *block_bytes = slice_block_bytes(L);
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_slice_bytes(int64_t P, int32_t n_slices, size_t *sums_bytes, size_t *gm_bytes, size_t *block_bytes)
-{
-    return ampli_slice_bytes_fmt(P, n_slices, AMPLI_SLICE_WIDE, sums_bytes, gm_bytes, block_bytes);
-}
-
-extern "C" int ampli_error_reduce_sliced(ampli_ctx *ctx, const int32_t *d_recs, int64_t P, int64_t E, const uint32_t *d_dup_off,
-                                         int32_t S, int32_t first_sample, float C, int32_t cov, int32_t n_slices,
-                                         double *d_sums, float *d_gm)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_sums || !d_gm || n_slices < 1) return fail(ctx, AMPLI_E_INVALID, "error_reduce_sliced: exchange buffers and n_slices >= 1 are required");
-    FinOut fo = {};
-    fo.slice_len = ampli_slice_len(P, n_slices);
-    fo.sl_group = ctx->grp_size; // buffers [n_slices][group][planes][L]; this call fills batch grp_index
-    fo.sl_fmt = ctx->slice_fmt; fo.sl_n = n_slices; fo.sl_flags = ctx->d_flags;
-    fo.sl_sums = d_sums + (size_t)ctx->grp_index * slice_planes(fo.sl_fmt) * (size_t)fo.slice_len;
-    fo.sl_gm = d_gm + (size_t)ctx->grp_index * 8 * (size_t)fo.slice_len;
-    return error_reduce_impl(ctx, dense_cohort(ctx, d_recs, P, E, S, d_dup_off, nullptr), P, first_sample, C, cov, nullptr, fo);
-}
-
-extern "C" int ampli_acc_to_slices(ampli_ctx *ctx, const ampli_acc_table *d_acc, int32_t n_slices, double *d_sums, float *d_gm)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || !acc_is_bound(d_acc) || n_slices < 1 || !d_sums || !d_gm) return fail(ctx, AMPLI_E_INVALID, "acc_to_slices: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_acc->P;
-    FinOut fo = {};
-    fo.slice_len = ampli_slice_len(P, n_slices);
-    fo.sl_group = ctx->grp_size;
-    fo.sl_fmt = ctx->slice_fmt; fo.sl_n = n_slices; fo.sl_flags = ctx->d_flags;
-    fo.sl_sums = d_sums + (size_t)ctx->grp_index * slice_planes(fo.sl_fmt) * (size_t)fo.slice_len;
-    fo.sl_gm = d_gm + (size_t)ctx->grp_index * 8 * (size_t)fo.slice_len;
-    hipLaunchKernelGGL(acc_pack_sliced_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P, fo);
-    return check_launch(ctx, "acc_pack_sliced_kernel");
-}
-
-extern "C" int ampli_error_finalize_slice(ampli_ctx *ctx, int64_t P, int32_t n_slices, int32_t slice_index,
-                                          const double *d_sum_slice, const float *d_gm_recv, float C, int32_t cov, void *d_block)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (P <= 0 || n_slices < 1 || slice_index < 0 || slice_index >= n_slices || !d_sum_slice || !d_gm_recv || !d_block || cov < 1)
-        return fail(ctx, AMPLI_E_INVALID, "error_finalize_slice: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long L = ampli_slice_len(P, n_slices);
-    const size_t G = (size_t)ctx->grp_size, g = (size_t)ctx->grp_index; // [group][planes][L] sums, [n][group][8][L] pairs, [group][block] out
-    hipLaunchKernelGGL(error_finalize_slice_kernel, dim3((unsigned)((4 * L + 255) / 256)), dim3(256), 0, main_stream(ctx),
-                       d_sum_slice + g * (size_t)slice_planes(ctx->slice_fmt) * (size_t)L, d_gm_recv + g * 8 * (size_t)L, G * 8 * (size_t)L, (int)n_slices, L,
-                       (long long)slice_index * L, (long long)P, C, (int)cov, (char *)d_block + g * slice_block_bytes(L), ctx->slice_fmt);
-    return check_launch(ctx, "error_finalize_slice_kernel");
-}
-
-extern "C" int ampli_error_table_unslice(ampli_ctx *ctx, int64_t P, int32_t n_slices, const void *d_blocks, float *d_rate,
-                                         uint8_t *d_code, float *d_thr, float *d_germ_val, uint8_t *d_germ_present,
-                                         int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (P <= 0 || n_slices < 1 || !d_blocks || !d_rate || !d_code) return fail(ctx, AMPLI_E_INVALID, "error_table_unslice: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    FinOut fo = {};
-    fo.rate = d_rate; fo.code = d_code; fo.thr = d_thr; fo.germ_val = d_germ_val; fo.germ_present = d_germ_present; fo.flags = d_flags;
-    const long long L = ampli_slice_len(P, n_slices);
-    hipLaunchKernelGGL(error_table_unslice_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx),
-                       (const char *)d_blocks + (size_t)ctx->grp_index * slice_block_bytes(L), (size_t)ctx->grp_size * slice_block_bytes(L),
-                       (int)n_slices, L, (long long)P, fo);
-    return check_launch(ctx, "error_table_unslice_kernel");
-}
-
-extern "C" int ampli_acc_merge(ampli_ctx *ctx, const ampli_acc_table *d_dst, const ampli_acc_table *d_parts, int32_t nparts)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_dst || !d_parts || nparts < 1 || nparts > 64) return fail(ctx, AMPLI_E_INVALID, "acc_merge: 1 <= nparts <= 64");
-    const int64_t P = d_dst->P;
-    for (int i = 0; i < nparts; ++i)
-        if (d_parts[i].P != P) return fail(ctx, AMPLI_E_INVALID, "acc_merge: part table P mismatch");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "acc_merge cannot be captured (it uploads a pointer list)");
-    int rc = ensure_ws(ctx, sizeof(AccPtrs) * 64);
-    if (rc) return rc;
-    AccPtrs hp[64];
-    for (int i = 0; i < nparts; ++i) hp[i] = to_ptrs(&d_parts[i]);
-    // small synchronous upload of the pointer list (not on a captured path)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws, hp, sizeof(AccPtrs) * nparts, hipMemcpyHostToDevice, main_stream(ctx)));
-    HIP_TRY(ctx, hipStreamSynchronize(main_stream(ctx)));
-    hipLaunchKernelGGL(acc_merge_ptr_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_dst),
-                       (const AccPtrs *)ctx->ws, (int)nparts, (long long)P);
-    return check_launch(ctx, "acc_merge_ptr_kernel");
-}
-
-extern "C" int64_t ampli_acc_packed_len(int64_t P) { return P > 0 ? 21 * P : 0; }
-
-extern "C" int ampli_acc_pack(ampli_ctx *ctx, const ampli_acc_table *d_acc, double *d_packed)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || d_acc->P <= 0 || !d_packed) return fail(ctx, AMPLI_E_INVALID, "acc_pack: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_acc->P;
-    hipLaunchKernelGGL(acc_pack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P, d_packed);
-    return check_launch(ctx, "acc_pack_kernel");
-}
-
-extern "C" int ampli_acc_unpack(ampli_ctx *ctx, const double *d_packed, const ampli_acc_table *d_acc)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || d_acc->P <= 0 || !d_packed) return fail(ctx, AMPLI_E_INVALID, "acc_unpack: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_acc->P;
-    hipLaunchKernelGGL(acc_unpack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P, d_packed);
-    return check_launch(ctx, "acc_unpack_kernel");
-}
-
-extern "C" int ampli_acc_regions(int64_t P, size_t *sum_bytes, size_t *gm_offset, size_t *gm_bytes)
-{
-    if (P <= 0) return AMPLI_E_INVALID;
-    size_t off[9];
-    acc_offsets(P, off);
-    if (sum_bytes) *sum_bytes = off[6]; // snt|srd|cnt|nrec|gm_n
-    if (gm_offset) *gm_offset = off[4];
-    if (gm_bytes) *gm_bytes = off[5] - off[4]; // gm_n|gm_first_af|gm_rest
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_gm_merge(ampli_ctx *ctx, const ampli_acc_table *d_dst, const void *d_regions, int32_t nparts)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_dst || !d_regions || nparts < 1) return fail(ctx, AMPLI_E_INVALID, "gm_merge: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_dst->P;
-    size_t off[9];
-    acc_offsets(P, off);
-    hipLaunchKernelGGL(gm_merge_kernel, dim3((unsigned)((4 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), d_dst->gm_n,
-                       d_dst->gm_first, d_dst->gm_first_af, d_dst->gm_rest, (const char *)d_regions, off[5] - off[4],
-                       off[6] - off[4], off[7] - off[4], (int)nparts, P);
-    return check_launch(ctx, "gm_merge_kernel");
-}
-
-// ---------------------------------------------------------------------------
-// The threshold sums in the REFERENCE's own order (round 6), for cohorts outside the exactness envelope of DESIGN 4.2.
-// Inside it every partial sum of `sum = sum + X + float(RD)*float(C)` (EE:1597, 1599) is exact, so any order and association --
-// ours: sample shards, waves, chunks -- gives the reference's double.  Outside it (a coverage cut-off of a few reads with depths
-// in the millions) the double depends on the order the reference adds in: estimateThresholds walks `equal_range` of an
-// unordered_multimap (EE:1555, 1565), which libstdc++ fills so that equal keys come out in REVERSE insertion order -- the last
-// file of the visit order first, and within a file a position's later lines before its first one.  One lane per position walks
-// exactly that: samples of the chunk from last to first, extras from last to first, then the primary record; the double is
-// updated as the reference's expression associates, (sum + X) + (double)(float(RD) * float(C)).  A cohort in several chunks is
-// walked chunk by chunk from the LAST chunk to the first with the sums carried in the table (accumulate).  Only the eight sums
-// are produced: counts, depth sums (integers in a double: exact to 2^53) and the Germ_Max state do not depend on this order.
-// Speed is irrelevant (a rerun of a cohort the fast path flagged); positions are independent, so it is still one launch.
-// ---------------------------------------------------------------------------
-template <int LAY>
-__global__ __launch_bounds__(256) void error_sums_inorder_kernel(const RecView rv, const long long P, const long long E, const int n,
-                                                                 const unsigned *__restrict__ dup_off, const float C, const int cov,
-                                                                 double *__restrict__ snt, const int accumulate)
-{
-    constexpr int RB = rec_bytes_of<LAY>();
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    LaneAcc a;
-    lane_acc_init(a);
-    if (accumulate) {
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            a.snt[0][nt] = snt[(0 * 4 + nt) * P + p];
-            a.snt[1][nt] = snt[(1 * 4 + nt) * P + p];
-        }
-    }
-    const unsigned e0 = dup_off ? dup_off[p] : 0u, e1 = dup_off ? dup_off[p + 1] : 0u;
-    for (int t = n - 1; t >= 0; --t) {
-        for (unsigned e = e1; e > e0; --e) { // the position's later lines of this file first
-            int4 r0, r1;
-            rec_decode<LAY>(rec_load_at<LAY>(rv.ext + ((size_t)t * (size_t)rv.ext_stride + (size_t)(e - 1)) * RB), r0, r1);
-            visit_record(a, r0, r1, t, C, cov, rv.rd_ext ? rv.rd_ext[(size_t)t * (size_t)E + (e - 1)] : AMPLI_ABSENT);
-        }
-        int4 r0, r1;
-        rec_decode<LAY>(rec_load_at<LAY>(rv.base + ((size_t)t * (size_t)rv.row_stride + (size_t)p) * RB), r0, r1);
-        visit_record(a, r0, r1, t, C, cov, rv.rd ? rv.rd[(size_t)t * (size_t)P + p] : AMPLI_ABSENT);
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        snt[(0 * 4 + nt) * P + p] = a.snt[0][nt];
-        snt[(1 * 4 + nt) * P + p] = a.snt[1][nt];
-    }
-}
-
-extern "C" int ampli_error_sums_inorder(ampli_ctx *ctx, const ampli_records *recs, int64_t P, float C, int32_t cov,
-                                        const ampli_acc_table *d_acc, int32_t accumulate)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!recs || P <= 0 || cov < 1 || !d_acc || !acc_is_bound(d_acc) || d_acc->P != P) return fail(ctx, AMPLI_E_INVALID, "error_sums_inorder: bad argument");
-    DevCohort co;
-    { int rc = cohort_from_records(ctx, recs, P, co); if (rc) return rc; }
-    if (co.n <= 0 || !co.rv.base) return fail(ctx, AMPLI_E_INVALID, "error_sums_inorder: empty cohort");
-    if (co.E > 0 && !co.dup_off) return fail(ctx, AMPLI_E_INVALID, "error_sums_inorder: E > 0 needs dup_off");
-    {
-        const uintptr_t am = co.layout == AMPLI_RECORDS_U24 ? 7 : 15;
-        if (((uintptr_t)co.rv.base & am) != 0 || (co.E > 0 && ((uintptr_t)co.rv.ext & am) != 0))
-            return fail(ctx, AMPLI_E_INVALID, "error_sums_inorder: recs must be 16-byte aligned (8-byte for the 24-byte layout)");
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const dim3 grid((unsigned)((P + 255) / 256));
-#define AMPLI_LAUNCH_INORDER(LV)                                                                                                  \
-    hipLaunchKernelGGL((error_sums_inorder_kernel<LV>), grid, dim3(256), 0, main_stream(ctx), co.rv, (long long)P, (long long)co.E, \
-                       (int)co.n, co.E > 0 ? co.dup_off : nullptr, C, (int)cov, d_acc->snt, accumulate ? 1 : 0)
-    if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_INORDER(AMPLI_RECORDS_U24);
-    else if (co.layout == AMPLI_RECORDS_U16) AMPLI_LAUNCH_INORDER(AMPLI_RECORDS_U16);
-    else AMPLI_LAUNCH_INORDER(AMPLI_RECORDS_I32);
-#undef AMPLI_LAUNCH_INORDER
-    return check_launch(ctx, "error_sums_inorder_kernel");
-}
-
-extern "C" int ampli_error_finalize(ampli_ctx *ctx, const ampli_acc_table *d_acc, float C, int32_t cov, float *d_rate,
-                                    uint8_t *d_code, float *d_thr, float *d_germ_val, uint8_t *d_germ_present,
-                                    int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || d_acc->P <= 0 || !d_rate || !d_code || cov < 1) return fail(ctx, AMPLI_E_INVALID, "error_finalize: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_acc->P;
-    FinOut fo = {};
-    fo.rate = d_rate; fo.code = d_code; fo.thr = d_thr; fo.germ_val = d_germ_val; fo.germ_present = d_germ_present; fo.flags = d_flags;
-    return launch_finalize(ctx, to_ptrs(d_acc), P, C, (int)cov, fo);
-}
-
 static int ensure_lgtab(ampli_ctx *ctx)
 {
     if (ctx->d_lgtab) return AMPLI_OK;
@@ -3161,19 +2675,14 @@ static int poisson_prefilter_launch(ampli_ctx *ctx, const int lane_k, hipStream_
     else
         Q.parity ^= 1;
     dim3 qgrid((unsigned)(tiles8 * gy));
-    const bool irr = co.rv.rd || co.rv.rd_ext;
-#define AMPLI_LAUNCH_STREAM_I(LV, IV)                                                                                            \
-    hipLaunchKernelGGL((poisson_stream_kernel<LV, IV>), qgrid, dim3(256), 0, st, co.rv, (long long)P,                             \
-                       (long long)E, d_ext_pos, (int)T, rpw, (unsigned)gy, d_thr, thr_L, thr_bb, d_ref_code, (int)cov,            \
-                       (PcItem *)Q.items, per, qn, d_call_mask, ctx->d_flags, d_n_calls, r_lo, r_hi, shard_lo, shard_n)
-#define AMPLI_LAUNCH_STREAM(LV) do { if (irr) AMPLI_LAUNCH_STREAM_I(LV, true); else AMPLI_LAUNCH_STREAM_I(LV, false); } while (0)
-    if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_STREAM(AMPLI_RECORDS_U24);
-    else if (co.layout == AMPLI_RECORDS_U16) AMPLI_LAUNCH_STREAM(AMPLI_RECORDS_U16);
-    else AMPLI_LAUNCH_STREAM(AMPLI_RECORDS_I32);
-#undef AMPLI_LAUNCH_STREAM_I
-#undef AMPLI_LAUNCH_STREAM
-    int rc = check_launch(ctx, "poisson_stream_kernel");
-    if (rc) return rc;
+    with_layout(co.layout, [&](auto L) {
+        with_bool(co.rv.rd || co.rv.rd_ext, [&](auto IRR) {
+            hipLaunchKernelGGL((poisson_stream_kernel<L, IRR>), qgrid, dim3(256), 0, st, co.rv, (long long)P, (long long)E, d_ext_pos, (int)T,
+                               rpw, (unsigned)gy, d_thr, thr_L, thr_bb, d_ref_code, (int)cov, (PcItem *)Q.items, per, qn, d_call_mask,
+                               ctx->d_flags, d_n_calls, r_lo, r_hi, shard_lo, shard_n);
+        });
+    });
+    { int rc = check_launch(ctx, "poisson_stream_kernel"); if (rc) return rc; }
     hipStream_t dstream = st;
     if (ctx->async_drain) { // let the drain run beside whatever the caller enqueues next (never with ranges)
         HIP_TRY(ctx, hipEventRecord(ctx->ev_stream_done, st));
@@ -3204,16 +2713,11 @@ static int poisson_call_impl(ampli_ctx *ctx, const DevCohort &co, int64_t P, con
     const uint32_t *d_ext_pos = co.ext_pos;
     if (!co.rv.base || P <= 0 || E < 0 || T <= 0 || !d_thr || !d_ref_code || !d_call_mask || cov < 1)
         return fail(ctx, AMPLI_E_INVALID, "poisson_call: bad argument");
-    if (E > 0 && !d_ext_pos) return fail(ctx, AMPLI_E_INVALID, "poisson_call: E > 0 needs ext_pos");
+    { int rc = check_records(ctx, co, "poisson_call", d_ext_pos, "ext_pos"); if (rc) return rc; }
     if (mode != AMPLI_POISSON_FULL && mode != AMPLI_POISSON_PREFILTER) return fail(ctx, AMPLI_E_INVALID, "poisson_call: bad mode");
     if (d_q && mode != AMPLI_POISSON_FULL) return fail(ctx, AMPLI_E_INVALID, "poisson_call: dense q needs AMPLI_POISSON_FULL");
     if (d_calls && (!d_n_calls || capacity < AMPLI_CALL_SHARDS)) return fail(ctx, AMPLI_E_INVALID, "poisson_call: call list needs n_calls and capacity >= AMPLI_CALL_SHARDS");
     if (d_n_calls && !d_calls) capacity = 0;
-    {
-        const uintptr_t am = co.layout == AMPLI_RECORDS_U24 ? 7 : 15;
-        if (((uintptr_t)co.rv.base & am) != 0 || (E > 0 && ((uintptr_t)co.rv.ext & am) != 0))
-            return fail(ctx, AMPLI_E_INVALID, "poisson_call: recs must be 16-byte aligned (8-byte for the 24-byte layout)");
-    }
     if (P + E >= (1ll << 30)) return fail(ctx, AMPLI_E_RANGE, "poisson_call: P + E must be below 2^30 records per sample");
     if ((T + PC_SAMPLES - 1) / PC_SAMPLES > 65535) return fail(ctx, AMPLI_E_RANGE, "poisson_call: more than 262140 tumour samples in one call (grid limit); split the cohort");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -3222,32 +2726,27 @@ static int poisson_call_impl(ampli_ctx *ctx, const DevCohort &co, int64_t P, con
     dim3 grid((unsigned)((R + 255) / 256), (unsigned)((T + PC_SAMPLES - 1) / PC_SAMPLES));
     if (d_n_calls && (mode == AMPLI_POISSON_FULL || d_af)) // the two-kernel path resets the counters in-kernel
         HIP_TRY(ctx, hipMemsetAsync(d_n_calls, 0, sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS, main_stream(ctx)));
-#define AMPLI_LAUNCH_PC(MODEV, UV)                                                                                              \
-    hipLaunchKernelGGL((poisson_call_kernel<MODEV, UV>), grid, dim3(256), 0, main_stream(ctx), co.rv, (long long)P,                  \
-                       (long long)E, d_ext_pos, (int)T, d_thr, thr_L, thr_bb, d_ref_code, (int)cov, d_call_mask, d_calls,       \
-                       (long long)capacity,                                                                                     \
-                       d_n_calls, d_q, d_af, (const double *)ctx->d_lgtab)
+    auto launch_in_place = [&](auto MODE) { // poisson_call_kernel: every record evaluated by its own lane
+        with_layout(co.layout, [&](auto L) {
+            hipLaunchKernelGGL((poisson_call_kernel<MODE, L>), grid, dim3(256), 0, main_stream(ctx), co.rv, (long long)P, (long long)E, d_ext_pos,
+                               (int)T, d_thr, thr_L, thr_bb, d_ref_code, (int)cov, d_call_mask, d_calls, (long long)capacity, d_n_calls, d_q,
+                               d_af, (const double *)ctx->d_lgtab);
+        });
+    };
     if (mode == AMPLI_POISSON_FULL && !d_af) { // all six scores of every record: light ones in place, heavy ones compacted per workgroup
         { int rcl = ensure_lgtab(ctx); if (rcl) return rcl; }
-#define AMPLI_LAUNCH_PF(UV)                                                                                                           \
-    hipLaunchKernelGGL((poisson_full_kernel<UV>), grid, dim3(256), 0, main_stream(ctx), co.rv, (long long)P, (long long)E, d_ext_pos, \
-                       (int)T, d_thr, thr_L, thr_bb, d_ref_code, (int)cov, d_call_mask, d_calls, (long long)capacity, d_n_calls, d_q, \
-                       (const double *)ctx->d_lgtab)
-        if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_PF(AMPLI_RECORDS_U24);
-        else if (co.layout == AMPLI_RECORDS_U16) AMPLI_LAUNCH_PF(AMPLI_RECORDS_U16);
-        else AMPLI_LAUNCH_PF(AMPLI_RECORDS_I32);
-#undef AMPLI_LAUNCH_PF
+        with_layout(co.layout, [&](auto L) {
+            hipLaunchKernelGGL((poisson_full_kernel<L>), grid, dim3(256), 0, main_stream(ctx), co.rv, (long long)P, (long long)E, d_ext_pos,
+                               (int)T, d_thr, thr_L, thr_bb, d_ref_code, (int)cov, d_call_mask, d_calls, (long long)capacity, d_n_calls, d_q,
+                               (const double *)ctx->d_lgtab);
+        });
         return check_launch(ctx, "poisson_full_kernel");
     }
     if (mode == AMPLI_POISSON_FULL) {
         { int rcl = ensure_lgtab(ctx); if (rcl) return rcl; }
-        if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_PC(AMPLI_POISSON_FULL, AMPLI_RECORDS_U24);
-        else if (co.layout == AMPLI_RECORDS_U16) AMPLI_LAUNCH_PC(AMPLI_POISSON_FULL, AMPLI_RECORDS_U16);
-        else AMPLI_LAUNCH_PC(AMPLI_POISSON_FULL, AMPLI_RECORDS_I32);
+        launch_in_place(Const<AMPLI_POISSON_FULL>{});
     } else if (d_af) { // dense VAFs are a validation output: literal per-lane kernel
-        if (co.layout == AMPLI_RECORDS_U24) AMPLI_LAUNCH_PC(AMPLI_POISSON_PREFILTER, AMPLI_RECORDS_U24);
-        else if (co.layout == AMPLI_RECORDS_U16) AMPLI_LAUNCH_PC(AMPLI_POISSON_PREFILTER, AMPLI_RECORDS_U16);
-        else AMPLI_LAUNCH_PC(AMPLI_POISSON_PREFILTER, AMPLI_RECORDS_I32);
+        launch_in_place(Const<AMPLI_POISSON_PREFILTER>{});
     } else {
         if (((uintptr_t)d_call_mask & 3) != 0) return fail(ctx, AMPLI_E_INVALID, "poisson_call: call_mask must be 4-byte aligned");
         if (ctx->async_drain && is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "asynchronous drain cannot be captured");
@@ -3289,8 +2788,7 @@ extern "C" int ampli_poisson_call_records(ampli_ctx *ctx, const ampli_records *t
 {
     if (!ctx) return AMPLI_E_INVALID;
     DevCohort co;
-    int rc = cohort_from_records(ctx, trecs, P, co);
-    if (rc) return rc;
+    { int rc = cohort_from_records(ctx, trecs, P, co); if (rc) return rc; }
     return poisson_call_impl(ctx, co, P, d_thr, 0, 0, d_ref_code, cov, mode, d_call_mask, d_calls, capacity, d_n_calls, d_q, d_af);
 }
 
@@ -3305,6 +2803,47 @@ extern "C" int ampli_poisson_call_blocks(ampli_ctx *ctx, const int32_t *d_trecs,
     d_blocks = (const char *)d_blocks + (size_t)ctx->grp_index * slice_block_bytes(L); // [n_slices][group][block]: this batch's blocks
     return poisson_call_impl(ctx, dense_cohort(ctx, d_trecs, P, E, T, nullptr, d_ext_pos), P, (const float *)d_blocks, L,
                              (size_t)ctx->grp_size * slice_block_bytes(L), d_ref_code, cov, mode, d_call_mask, d_calls, capacity, d_n_calls, d_q, d_af);
+}
+
+// ==== auxiliary and synthetic: scorer checks, synthetic panels =========================================================================
+
+__global__ void score_dense_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, const double *lgtab)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) q[i] = ampli_poisson_score_dense(k[i], rd[i], err[i], lgtab, AMPLI_LGTAB);
+}
+
+__global__ void score_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, double *pv)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    if (q) q[i] = ampli_poisson_score(k[i], rd[i], err[i]);
+    if (pv) pv[i] = err[i] == -1 ? -1.0 : ampli_poisson_p(k[i], rd[i], err[i]);
+}
+
+__global__ void roundtrip_batch_kernel(const float *in, const long long n, float *out)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = ampli_text_roundtrip(in[i]);
+}
+
+__global__ void synth_fill_kernel(int4 *recs, const long long P, const int n_samples, const int first_sample,
+                                  const unsigned long long seed, const int depth, const int tumour)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int s = blockIdx.y;
+    if (p >= P || s >= n_samples) return;
+    int rec[8];
+    ampli_synth_record(seed, (uint64_t)p, (uint64_t)(first_sample + s), depth, tumour, rec);
+    const size_t o = ((size_t)s * P + p) * 2;
+    recs[o] = make_int4(rec[0], rec[1], rec[2], rec[3]);
+    recs[o + 1] = make_int4(rec[4], rec[5], rec[6], rec[7]);
+}
+
+__global__ void synth_ref_kernel(unsigned char *ref, const long long P, const unsigned long long seed)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p < P) ref[p] = (unsigned char)ampli_synth_ref_base(seed, (uint64_t)p);
 }
 
 extern "C" int ampli_score_batch(ampli_ctx *ctx, const int32_t *d_k, const int32_t *d_rd, const float *d_err, int64_t n,
@@ -3343,28 +2882,6 @@ extern "C" int ampli_synth_fill(ampli_ctx *ctx, int32_t *d_recs, int64_t P, int3
     hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)n_samples), dim3(256), 0, main_stream(ctx),
                        (int4 *)d_recs, (long long)P, (int)n_samples, (int)first_sample, (unsigned long long)seed, (int)depth, (int)tumour);
     return check_launch(ctx, "synth_fill_kernel");
-}
-
-extern "C" int ampli_records_pack16(ampli_ctx *ctx, const int32_t *d_recs32, int64_t n_records, void *d_recs16, int32_t *d_overflow)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_recs32 || !d_recs16 || !d_overflow || n_records <= 0 || ((uintptr_t)d_recs32 & 15) || ((uintptr_t)d_recs16 & 15))
-        return fail(ctx, AMPLI_E_INVALID, "records_pack16: bad argument (16-byte aligned buffers, n_records > 0, overflow word)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(records_pack16_kernel, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, main_stream(ctx), (const int4 *)d_recs32,
-                       (long long)n_records, (uint4 *)d_recs16, d_overflow);
-    return check_launch(ctx, "records_pack16_kernel");
-}
-
-extern "C" int ampli_records_pack24(ampli_ctx *ctx, const int32_t *d_recs32, int64_t n_records, void *d_recs24, int32_t *d_overflow)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_recs32 || !d_recs24 || !d_overflow || n_records <= 0 || ((uintptr_t)d_recs32 & 15) || ((uintptr_t)d_recs24 & 7))
-        return fail(ctx, AMPLI_E_INVALID, "records_pack24: bad argument (aligned buffers, n_records > 0, overflow word)");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(records_pack24_kernel, dim3((unsigned)((n_records + 255) / 256)), dim3(256), 0, main_stream(ctx), (const int4 *)d_recs32,
-                       (long long)n_records, (uint2 *)d_recs24, d_overflow);
-    return check_launch(ctx, "records_pack24_kernel");
 }
 
 extern "C" int ampli_synth_ref(ampli_ctx *ctx, uint8_t *d_ref_code, int64_t P, uint64_t seed)
