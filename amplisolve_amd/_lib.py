@@ -36,6 +36,11 @@ class Call(C.Structure):
                 ("fw", i32), ("bw", i32), ("flags", i32)]
 
 
+class LooCall(C.Structure):
+    """mirror of ampli_loo_call"""
+    _fields_ = [("call", Call), ("thr_fw", f32), ("thr_bw", f32), ("code", i32), ("pad", i32)]
+
+
 class Records(C.Structure):
     """mirror of ampli_records: a cohort (or a chunk of a streamed one) on the device, described explicitly"""
     _fields_ = [("recs", vp), ("row_stride", i64), ("ext", vp), ("ext_stride", i64), ("E", i64), ("dup_off", vp),
@@ -123,12 +128,15 @@ HIP_SYMBOLS = {
     "ampli_error_sums_inorder": (C.c_int, [vp, C.POINTER(Records), i64, f32, i32, C.POINTER(AccTable), i32]),
     "ampli_error_reduce_records_sliced": (C.c_int, [vp, C.POINTER(Records), i64, i32, f32, i32, C.POINTER(AccTable), i32, i32, vp, vp]),
     "ampli_poisson_call_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, i32, vp, vp, i64, vp, vp, vp]),
+    "ampli_loo_call_records": (C.c_int, [vp, C.POINTER(Records), i64, C.POINTER(AccTable), f32, i32, i32, vp, i32, vp, vp, i64, vp, vp, vp,
+                                         vp, vp]),
     "ampli_graph_begin": (C.c_int, [vp]),
     "ampli_graph_end": (C.c_int, [vp, C.POINTER(vp)]),
     "ampli_graph_launch": (C.c_int, [vp, vp]),
     "ampli_graph_destroy": (C.c_int, [vp]),
     "ampli_set_async_drain": (C.c_int, [vp, i32]),
     "ampli_wait_calls": (C.c_int, [vp]),
+    "ampli_mem_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz)]),
 }
 
 class HostShard(C.Structure):

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, Records, hip_lib
+from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, LooCall, Records, hip_lib
 
 NT = "ACGT"
 POISSON_FULL = 0
@@ -321,6 +321,55 @@ class Context:
         self._check(self.lib.ampli_poisson_call_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), cov, mode, _ptr(call_mask),
                                                         _ptr(calls_buf), capacity, _ptr(n_calls), None, None))
         return dict(call_mask=call_mask, q=None, af=None, calls_buf=calls_buf, n_calls=n_calls, capacity=capacity)
+
+    def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
+                 mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,
+                 n_calls=None, callable_pos=None, callable_sample=None, flags=None):
+        """Leave-one-out calls of one resident chunk of the panel of normals (ampli_loo_call_records): every normal of the chunk
+        through the calling gate (calling cutoff call_cov) against the error table (C_value, cov) of the cohort without it.  acc holds
+        the WHOLE cohort's sums.  callable_pos [P] / callable_sample [n] are added to (zeroed here when not given); flags[0] gets bit 0
+        when a total is outside the exactness envelope.  dense_thr: also the S-1 thresholds, float32 [n, 2, 4, P]."""
+        import torch
+
+        n, R = rec.n_samples, P + rec.E
+        d = self.device
+        if call_mask is None:
+            call_mask = torch.empty(((n * R + 3) // 4 * 4,), dtype=torch.uint8, device=d)[: n * R].view(n, R)
+        if capacity > 0 and calls_buf is None:
+            calls_buf = torch.empty((capacity * C.sizeof(LooCall),), dtype=torch.uint8, device=d)
+        if capacity > 0:
+            capacity -= capacity % CALL_SHARDS
+        if capacity > 0 and n_calls is None:
+            n_calls = torch.zeros((CALL_COUNTER_WORDS,), dtype=torch.int64, device=d)
+        if callable_pos is None:
+            callable_pos = torch.zeros((P,), dtype=torch.int32, device=d)
+        if callable_sample is None:
+            callable_sample = torch.zeros((n,), dtype=torch.int32, device=d)
+        if flags is None:
+            flags = torch.zeros((1,), dtype=torch.int32, device=d)
+        thr_loo = torch.empty((n, 2, 4, P), dtype=torch.float32, device=d) if dense_thr else None
+        self._check(self.lib.ampli_loo_call_records(self.h, C.byref(rec), P, C.byref(acc.struct), C_value, cov, call_cov, _ptr(ref_code), mode,
+                                                    _ptr(call_mask), _ptr(calls_buf), capacity, _ptr(n_calls), _ptr(callable_pos),
+                                                    _ptr(callable_sample), _ptr(thr_loo), _ptr(flags)))
+        return dict(call_mask=call_mask, calls_buf=calls_buf, n_calls=n_calls, capacity=capacity, callable_pos=callable_pos,
+                    callable_sample=callable_sample, thr_loo=thr_loo, flags=flags)
+
+    def read_loo_calls(self, res):
+        """The leave-one-out call list on the host, sorted by (sample, record, alt): the fields of read_calls + thr_fw, thr_bw, code."""
+        import numpy as np
+
+        counts = res["n_calls"][::CALL_COUNTER_STRIDE].cpu().numpy()
+        per = res["capacity"] // CALL_SHARDS
+        if (counts > per).any():
+            raise AmpliError(f"call list segment overflowed: {int(counts.max())} > {per}; rerun with a larger capacity")
+        sz = C.sizeof(LooCall)
+        raw = b"".join(res["calls_buf"][k * per * sz: (k * per + int(counts[k])) * sz].cpu().numpy().tobytes() for k in range(CALL_SHARDS))
+        dt = np.dtype([("sample", "<i4"), ("record", "<i4"), ("alt", "<i4"), ("rd", "<i4"), ("q_fw", "<f8"),
+                       ("q_bw", "<f8"), ("af", "<f4"), ("af_fw", "<f4"), ("af_bw", "<f4"), ("k_fw", "<i4"), ("k_bw", "<i4"),
+                       ("fw", "<i4"), ("bw", "<i4"), ("flags", "<i4"), ("thr_fw", "<f4"), ("thr_bw", "<f4"), ("code", "<i4"), ("pad", "<i4")])
+        assert dt.itemsize == sz
+        a = np.frombuffer(raw, dtype=dt)
+        return a[np.lexsort((a["alt"], a["record"], a["sample"]))]
 
     def _new_error_table(self, P: int) -> ErrorTable:
         import torch

@@ -341,6 +341,26 @@ __device__ __forceinline__ void lane_acc_init(LaneAcc &a)
     a.nrec = 0;
 }
 
+// The threshold half of the record gate (EE:1595 + clones): bit nt set when the record's counts of nucleotide nt go into the
+// threshold sums -- covered on both strands and AF <= 0.05 on each strand, as an integer bound (ampli_math.h), or the literal fp
+// gates when `big` (an irregular line or RD >= 2^24: never for real panels).  visit_record and the leave-one-out kernel both
+// gate through here, so the table of the whole cohort and the S-1 tables subtracted from it cannot drift apart.
+__device__ __forceinline__ unsigned thr_gate(const int fw[4], const int bw[4], const int FW, const int BW, const bool covok, const bool big)
+{
+    const int lim_fw = ampli_af_limit(FW), lim_bw = ampli_af_limit(BW);
+    unsigned q = 0;
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+        bool g_fw = fw[nt] <= lim_fw, g_bw = bw[nt] <= lim_bw;
+        if (big) {
+            g_fw = ampli_af_gate_fp(fw[nt], FW);
+            g_bw = ampli_af_gate_fp(bw[nt], BW);
+        }
+        q |= (covok && g_fw && g_bw) ? 1u << nt : 0u;
+    }
+    return q;
+}
+
 // One record of one sample at this lane's position.  r0 = {Afw,Cfw,Gfw,Tfw}, r1 = {Ars,Crs,Grs,Trs}.
 // rd_col: the RD column of an irregular line (RD != A+C+G+T), AMPLI_ABSENT otherwise.
 __device__ __forceinline__ void visit_record(LaneAcc &a, const int4 r0, const int4 r1, const int sample,
@@ -359,20 +379,17 @@ __device__ __forceinline__ void visit_record(LaneAcc &a, const int4 r0, const in
 
     // AF <= 0.05 as an integer bound (ampli_math.h); fp form for counts beyond exact floats
     const bool big = irregular || RD >= AMPLI_COUNT_LIMIT; // the literal fp gates: any RD, also a negative or zero one
-    const int lim_fw = ampli_af_limit(FW), lim_bw = ampli_af_limit(BW), lim_rd = ampli_af_limit(RD);
+    const unsigned qual = thr_gate(fw, bw, FW, BW, covok, big);
+    const int lim_rd = ampli_af_limit(RD);
     // EE:1597,1599: float(RD_s)*float(C), an fp32 product widened to double
     const double prod_fw = (double)((float)FW * C);
     const double prod_bw = (double)((float)BW * C);
     const float rdf = (float)RD;
 #pragma unroll
     for (int nt = 0; nt < 4; ++nt) {
-        bool g_fw = fw[nt] <= lim_fw, g_bw = bw[nt] <= lim_bw, g_tot = (fw[nt] + bw[nt]) <= lim_rd;
-        if (big) { // never taken for real panels; keeps the literal semantics at >= 2^24 reads
-            g_fw = ampli_af_gate_fp(fw[nt], FW);
-            g_bw = ampli_af_gate_fp(bw[nt], BW);
-            g_tot = ampli_af_gate_fp(fw[nt] + bw[nt], RD);
-        }
-        if (covok && g_fw && g_bw) { // EE:1595
+        bool g_tot = (fw[nt] + bw[nt]) <= lim_rd;
+        if (big) g_tot = ampli_af_gate_fp(fw[nt] + bw[nt], RD); // never taken for real panels
+        if ((qual >> nt) & 1u) { // EE:1595
             a.snt[0][nt] = a.snt[0][nt] + (double)fw[nt] + prod_fw; // EE:1597
             a.srd[0][nt] += FW;                                     // EE:1598
             a.snt[1][nt] = a.snt[1][nt] + (double)bw[nt] + prod_bw; // EE:1599
@@ -560,22 +577,27 @@ __device__ __forceinline__ void lane_acc_store_gm(const AccPtrs &t, const long l
     }
 }
 
+// quorum, rates and NaN code of one (position, nucleotide) from its sums (EE:1659-1682): the code, 0 estimate, 1 below quorum,
+// 2 NaN; the rates are 0 unless the code is 0.  Shared by finalize_one and the leave-one-out kernel's S-1 tables.
+__device__ __forceinline__ unsigned char fin_rates(const double sfw, const double sbw, const long long dfw, const long long dbw, const int cnt,
+                                                   const int nrec, float &r_fw, float &r_bw)
+{
+    r_fw = 0.0f; r_bw = 0.0f;
+    if ((double)cnt < 0.338 * (double)nrec) return 1; // EE:1659
+    r_fw = (float)sfw / (float)(double)dfw; // EE:1679
+    r_bw = (float)sbw / (float)(double)dbw; // EE:1680
+    if (isnan(r_fw) || isnan(r_bw)) { r_fw = 0.0f; r_bw = 0.0f; return 2; } // EE:1682
+    return 0;
+}
+
 // one (position, nucleotide): returns true when a double sum left the exactness envelope
 __device__ __forceinline__ bool finalize_one(const int nt, const double sfw, const double sbw, const long long dfw, const long long dbw,
                                              const int cnt, const int nrec, const int gm_n, const float gm_rest, const long long P,
                                              const long long p, const double limit, const FinOut &o)
 {
     const long long i = nt * P + p, ifw = (0 * 4 + nt) * P + p, ibw = (1 * 4 + nt) * P + p;
-    float r_fw = 0.0f, r_bw = 0.0f;
-    unsigned char c;
-    if ((double)cnt < 0.338 * (double)nrec) { // EE:1659
-        c = 1;
-    } else {
-        r_fw = (float)sfw / (float)(double)dfw; // EE:1679
-        r_bw = (float)sbw / (float)(double)dbw; // EE:1680
-        if (isnan(r_fw) || isnan(r_bw)) { c = 2; r_fw = 0.0f; r_bw = 0.0f; } // EE:1682
-        else c = 0;
-    }
+    float r_fw, r_bw;
+    const unsigned char c = fin_rates(sfw, sbw, dfw, dbw, cnt, nrec, r_fw, r_bw);
     o.code[i] = c;
     o.rate[ifw] = r_fw;
     o.rate[ibw] = r_bw;
@@ -2333,7 +2355,7 @@ struct PcItem { // 40 bytes, self-contained: the drain kernel needs no second lo
     int k_fw, k_bw;   // alt reads per strand
     int FW, BW;       // strand depths
     int rd;           // RD column: d_fw = rd - BW (VC:895), AF = X / rd (VC:814)
-    float e_fw, e_bw; // effective errors (ampli_effective_err)
+    float e_fw, e_bw; // effective errors (ampli_effective_err); the leave-one-out kernel queues the raw thresholds of its S-1 table here
     int pad;
 };
 
@@ -2526,11 +2548,14 @@ __global__ __launch_bounds__(256, 7) void poisson_stream_kernel(
 
 // Two adjacent lanes per queued item, one per strand.  The scorer here is kf_gammaq's series branch in its
 // division-free form (ampli_kf_gammap_series_nodiv): a queued item has k > m on both strands or is no call.
-__global__ __launch_bounds__(256) void poisson_drain_kernel(
+// LOO (the leave-one-out drain): the item carries the raw thresholds of its S-1 table instead of the effective errors, and
+// the list entries are ampli_loo_call, which keep those thresholds for the host.
+template <bool LOO>
+__device__ __forceinline__ void drain_body(
     const PcItem *__restrict__ queue, const long long queue_per_shard, const unsigned long long *__restrict__ queue_n,
-    const long long R, unsigned *__restrict__ mask_words, ampli_call *__restrict__ calls, const long long capacity,
-    unsigned long long *__restrict__ n_calls, unsigned long long *__restrict__ next_queue_n, const unsigned shard_lo, const unsigned shard_n,
-    const double *__restrict__ lgtab)
+    const long long R, unsigned *__restrict__ mask_words, std::conditional_t<LOO, ampli_loo_call, ampli_call> *__restrict__ calls,
+    const long long capacity, unsigned long long *__restrict__ n_calls, unsigned long long *__restrict__ next_queue_n, const unsigned shard_lo,
+    const unsigned shard_n, const double *__restrict__ lgtab)
 {
     constexpr int IPB = 128; // items per workgroup pass
     // the counter array of the NEXT poisson_call (the other half of a double buffer; its last reader, the previous
@@ -2551,7 +2576,7 @@ __global__ __launch_bounds__(256) void poisson_drain_kernel(
         PcItem it = ib == (long long)blockIdx.y * IPB ? first : queue[(size_t)shard * queue_per_shard + (on ? i : ib)];
         const int k = strand ? it.k_bw : it.k_fw;
         const int d = strand ? it.BW : it.rd - it.BW; // VC:895-896
-        const float err = strand ? it.e_bw : it.e_fw;
+        const float err = LOO ? ampli_effective_err(strand ? it.e_bw : it.e_fw) : (strand ? it.e_bw : it.e_fw);
         // err_eff = +inf stands for err == -1 (Q = -888, VC:3844-3849); 0 was already replaced by 0.0010008f.
         // k <= m: the exact form of the prefilter bound (ampli_prefilter_nocall), Q < 5 -- no call whatever the value.
         const double m = (double)d * err; // VC:3864: double * float
@@ -2590,12 +2615,35 @@ __global__ __launch_bounds__(256) void poisson_drain_kernel(
                         ampli_call c;
                         call_fill(c, it.sample, it.record_alt & 0x3FFFFFFF, (it.record_alt >> 30) & 3, it.rd, qv, q_other, it.k_fw, it.k_bw, it.FW, it.BW,
                                   near_gate ? AMPLI_CALL_BORDERLINE : 0);
-                        calls[(size_t)cs * per + idx] = c;
+                        if constexpr (LOO) {
+                            ampli_loo_call lc;
+                            lc.call = c; lc.thr_fw = it.e_fw; lc.thr_bw = it.e_bw; lc.code = it.pad; lc.pad = 0;
+                            calls[(size_t)cs * per + idx] = lc;
+                        } else {
+                            calls[(size_t)cs * per + idx] = c;
+                        }
                     }
                 }
             }
         }
     }
+}
+
+__global__ __launch_bounds__(256) void poisson_drain_kernel(
+    const PcItem *__restrict__ queue, const long long queue_per_shard, const unsigned long long *__restrict__ queue_n,
+    const long long R, unsigned *__restrict__ mask_words, ampli_call *__restrict__ calls, const long long capacity,
+    unsigned long long *__restrict__ n_calls, unsigned long long *__restrict__ next_queue_n, const unsigned shard_lo, const unsigned shard_n,
+    const double *__restrict__ lgtab)
+{
+    drain_body<false>(queue, queue_per_shard, queue_n, R, mask_words, calls, capacity, n_calls, next_queue_n, shard_lo, shard_n, lgtab);
+}
+
+__global__ __launch_bounds__(256) void loo_drain_kernel(
+    const PcItem *__restrict__ queue, const long long queue_per_shard, const unsigned long long *__restrict__ queue_n,
+    const long long R, unsigned *__restrict__ mask_words, ampli_loo_call *__restrict__ calls, const long long capacity,
+    unsigned long long *__restrict__ n_calls, unsigned long long *__restrict__ next_queue_n, const double *__restrict__ lgtab)
+{
+    drain_body<true>(queue, queue_per_shard, queue_n, R, mask_words, calls, capacity, n_calls, next_queue_n, 0, AMPLI_CALL_SHARDS, lgtab);
 }
 
 __global__ void lgamma_table_kernel(double *t, const int n)
@@ -2611,6 +2659,37 @@ static int ensure_lgtab(ampli_ctx *ctx)
     if (hipMalloc((void **)&ctx->d_lgtab, sizeof(double) * AMPLI_LGTAB) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "lgamma table hipMalloc failed");
     hipLaunchKernelGGL(lgamma_table_kernel, dim3((AMPLI_LGTAB + 255) / 256), dim3(256), 0, main_stream(ctx), ctx->d_lgtab, AMPLI_LGTAB);
     return check_launch(ctx, "lgamma_table_kernel");
+}
+
+// The prefilter queue of a launch on `st`: at least `want` items (rounded up to whole shards), and the half of the double-buffered shard
+// counters this launch appends to (qn; the stream kernel finds it zeroed) and the half its drain resets for the next launch (qn_next)
+static int queue_prepare(ampli_ctx *ctx, AmpliQueue &Q, size_t want, hipStream_t st, long long &per, unsigned long long *&qn,
+                         unsigned long long *&qn_next)
+{
+    want = (want + AMPLI_CALL_SHARDS - 1) / AMPLI_CALL_SHARDS * AMPLI_CALL_SHARDS;
+    const bool capturing = is_capturing(ctx);
+    if ((Q.n_items < want || !Q.n) && capturing)
+        return fail(ctx, AMPLI_E_INVALID, "queue would have to be allocated while capturing: run the sequence once first");
+    if (Q.n_items < want) {
+        HIP_TRY(ctx, hipStreamSynchronize(st));
+        if (Q.items) (void)hipFree(Q.items);
+        Q.items = nullptr; Q.n_items = 0;
+        if (hipMalloc(&Q.items, want * sizeof(PcItem)) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "queue hipMalloc failed");
+        Q.n_items = want;
+    }
+    if (!Q.n) {
+        if (hipMalloc((void **)&Q.n, 2 * sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS) != hipSuccess)
+            return fail(ctx, AMPLI_E_NOMEM, "queue counter hipMalloc failed");
+        HIP_TRY(ctx, hipMemsetAsync(Q.n, 0, 2 * sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS, st));
+    }
+    per = (long long)(Q.n_items / AMPLI_CALL_SHARDS);
+    qn = Q.n + (size_t)(Q.parity & 1) * AMPLI_CALL_COUNTER_WORDS;
+    qn_next = Q.n + (size_t)((Q.parity + 1) & 1) * AMPLI_CALL_COUNTER_WORDS;
+    if (capturing) // a replayed graph cannot alternate halves: reset the half it uses with a memset node instead
+        HIP_TRY(ctx, hipMemsetAsync(qn, 0, sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS, st));
+    else
+        Q.parity ^= 1;
+    return AMPLI_OK;
 }
 
 // poisson_call, prefilter mode: poisson_stream_kernel + poisson_drain_kernel over the records [r_lo, r_hi) of every sample, on
@@ -2651,29 +2730,9 @@ static int poisson_prefilter_launch(ampli_ctx *ctx, const int lane_k, hipStream_
     size_t want = (size_t)std::max<long long>(1 << 16, (long long)T * Rk / 4);
     const size_t slack = (size_t)AMPLI_CALL_SHARDS * 256 * 3 * (size_t)rpw;
     if (ctx->queue_min_items) want = std::max(want, ctx->queue_min_items + slack);
-    want = (want + AMPLI_CALL_SHARDS - 1) / AMPLI_CALL_SHARDS * AMPLI_CALL_SHARDS;
-    const bool capturing = is_capturing(ctx);
-    if ((Q.n_items < want || !Q.n) && capturing)
-        return fail(ctx, AMPLI_E_INVALID, "queue would have to be allocated while capturing: run the sequence once first");
-    if (Q.n_items < want) {
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        if (Q.items) (void)hipFree(Q.items);
-        Q.items = nullptr; Q.n_items = 0;
-        if (hipMalloc(&Q.items, want * sizeof(PcItem)) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "queue hipMalloc failed");
-        Q.n_items = want;
-    }
-    if (!Q.n) {
-        if (hipMalloc((void **)&Q.n, 2 * sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS) != hipSuccess)
-            return fail(ctx, AMPLI_E_NOMEM, "queue counter hipMalloc failed");
-        HIP_TRY(ctx, hipMemsetAsync(Q.n, 0, 2 * sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS, st));
-    }
-    const long long per = (long long)(Q.n_items / AMPLI_CALL_SHARDS);
-    unsigned long long *qn = Q.n + (size_t)(Q.parity & 1) * AMPLI_CALL_COUNTER_WORDS;
-    unsigned long long *qn_next = Q.n + (size_t)((Q.parity + 1) & 1) * AMPLI_CALL_COUNTER_WORDS;
-    if (capturing) // a replayed graph cannot alternate halves: reset the half it uses with a memset node instead
-        HIP_TRY(ctx, hipMemsetAsync(qn, 0, sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS, st));
-    else
-        Q.parity ^= 1;
+    long long per;
+    unsigned long long *qn, *qn_next;
+    { int rcq = queue_prepare(ctx, Q, want, st, per, qn, qn_next); if (rcq) return rcq; }
     dim3 qgrid((unsigned)(tiles8 * gy));
     with_layout(co.layout, [&](auto L) {
         with_bool(co.rv.rd || co.rv.rd_ext, [&](auto IRR) {
@@ -2803,6 +2862,257 @@ extern "C" int ampli_poisson_call_blocks(ampli_ctx *ctx, const int32_t *d_trecs,
     d_blocks = (const char *)d_blocks + (size_t)ctx->grp_index * slice_block_bytes(L); // [n_slices][group][block]: this batch's blocks
     return poisson_call_impl(ctx, dense_cohort(ctx, d_trecs, P, E, T, nullptr, d_ext_pos), P, (const float *)d_blocks, L,
                              (size_t)ctx->grp_size * slice_block_bytes(L), d_ref_code, cov, mode, d_call_mask, d_calls, capacity, d_n_calls, d_q, d_af);
+}
+
+// ==== leave-one-out: what the panel of normals calls in itself =========================================================================
+
+// loo_stream_kernel<LAY,IRR>: for every normal s of a resident chunk and every position p, the calling gate of VC on
+// s's records at p against the thresholds the OTHER S-1 normals give.  One lane owns one position: it loads the whole
+// cohort's sums once (snt, srd, cnt, nrec: 148 B) and, for every row, subtracts the held-out sample's own contribution -- its
+// records at p that pass the threshold gate error_reduce used (thr_gate) -- and finalises that row's S-1 table in registers
+// (fin_rates, the text round trip).  Inside the exactness envelope every addend of snt is >= 0, so every partial sum of any subset
+// is bounded by the total and exact: the difference IS the S-1 sum, in whatever order the reference would have added it.  Outside
+// the envelope that fails: flag bit 0 (the caller refuses).
+// A workgroup = 4 waves over one 64-position tile, wave w taking rows w, w + 4, ...; the per-position callable count is summed over
+// the waves in LDS (no atomics), the per-sample one takes one reduction and one atomic per (wave, row).  Survivors of the prefilter
+// go onto poisson_call's queue as PcItems carrying the raw S-1 thresholds, and loo_drain_kernel scores them.
+struct LooRec {
+    int fw[4], bw[4];
+    int FW, BW, RD;
+    bool present, big;
+};
+
+template <int LAY, bool IRR>
+__device__ __forceinline__ LooRec loo_rec(const RecView &rv, const long long P, const long long E, const int s, const long long r)
+{
+    const RawRec<LAY> raw = r < P ? rec_load_at<LAY>(rv.base + ((size_t)s * (size_t)rv.row_stride + (size_t)r) * rec_bytes(LAY))
+                                  : rec_load_at<LAY>(rv.ext + ((size_t)s * (size_t)rv.ext_stride + (size_t)(r - P)) * rec_bytes(LAY));
+    int4 r0, r1;
+    rec_decode<LAY>(raw, r0, r1);
+    LooRec o;
+    o.fw[0] = r0.x; o.fw[1] = r0.y; o.fw[2] = r0.z; o.fw[3] = r0.w;
+    o.bw[0] = r1.x; o.bw[1] = r1.y; o.bw[2] = r1.z; o.bw[3] = r1.w;
+    o.FW = r0.x + r0.y + r0.z + r0.w; // EE:1175, VC:760
+    o.BW = r1.x + r1.y + r1.z + r1.w; // EE:1176, VC:761
+    o.RD = o.FW + o.BW;
+    bool irregular = false;
+    if (IRR) { // EE:1178-1181, VC:762-765: the line's own RD column
+        const int *rdp = r < P ? rv.rd : rv.rd_ext;
+        const int rdc = rdp ? rdp[r < P ? (size_t)s * P + r : (size_t)s * E + (r - P)] : AMPLI_ABSENT;
+        if (rdc != AMPLI_ABSENT) { o.RD = rdc; irregular = true; }
+    }
+    o.present = r0.x != AMPLI_ABSENT;
+    o.big = irregular || o.RD >= AMPLI_COUNT_LIMIT; // as visit_record
+    return o;
+}
+
+template <int LAY, bool IRR>
+__global__ __launch_bounds__(256) void loo_stream_kernel(
+    const RecView rv, const long long P, const long long E, const unsigned *__restrict__ dup_off, const int n, const AccPtrs acc,
+    const float C, const int cov, const int call_cov, const unsigned char *__restrict__ ref_code, const int prefilter,
+    PcItem *__restrict__ queue, const long long queue_per_shard, unsigned long long *__restrict__ queue_n,
+    unsigned long long *__restrict__ n_calls, int *__restrict__ callable_pos, int *__restrict__ callable_sample,
+    float *__restrict__ thr_loo, int *__restrict__ env_flags, int *__restrict__ ctx_flags)
+{
+    __shared__ PcItem stage[4][PC_STAGE];
+    __shared__ int lds_callable[4][64];
+    int staged = 0; // wave-uniform
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    // the call-list counters are reset here: only the drain, which starts after this kernel has finished, appends to the list
+    if (n_calls && blockIdx.x == 0 && threadIdx.x < AMPLI_CALL_SHARDS) n_calls[threadIdx.x * AMPLI_CALL_COUNTER_STRIDE] = 0ull;
+    const long long p_raw = (long long)blockIdx.x * 64 + lane;
+    const bool valid = p_raw < P;
+    const long long p = valid ? p_raw : P - 1;
+    double tsnt[2][4];
+    long long tsrd[2][4];
+    int tcnt[4];
+#pragma unroll
+    for (int nt = 0; nt < 4; ++nt) {
+#pragma unroll
+        for (int st = 0; st < 2; ++st) {
+            tsnt[st][nt] = acc.snt[(st * 4 + nt) * P + p];
+            tsrd[st][nt] = acc.srd[(st * 4 + nt) * P + p];
+        }
+        tcnt[nt] = acc.cnt[nt * P + p];
+    }
+    const int tnrec = acc.nrec[p];
+    const int ref = valid ? (int)ref_code[p] : 255;
+    const long long e0 = E > 0 ? (long long)dup_off[p] : 0;
+    const int n_ext = E > 0 && valid ? (int)(dup_off[p + 1] - dup_off[p]) : 0;
+    // the record loops below run n_ext_max + 1 times in EVERY lane: the queue staging inside them is wave-wide (ballots, the
+    // wave-uniform fill count of the stage), so no lane may leave them early; a lane past its own records visits nothing
+    int n_ext_max = n_ext;
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) n_ext_max = max(n_ext_max, __shfl_xor(n_ext_max, off));
+    if (env_flags && wave == 0) { // the totals' exactness envelope (finalize_one's test): outside it the differences below are not the S-1 sums
+        const double limit = envelope_limit(C, cov);
+        bool bad = false;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) bad |= !(tsnt[0][nt] < limit) || !(tsnt[1][nt] < limit);
+        if (valid && bad) atomicOr(env_flags, 1);
+    }
+    const unsigned shard = blockIdx.x % AMPLI_CALL_SHARDS;
+    int callable = 0; // this lane's callable records over this wave's rows
+    for (int s = wave; s < n; s += 4) {
+        // 1. the S-1 sums of (s, p): the totals minus s's records at p that pass the threshold gate
+        double snt[2][4];
+        long long srd[2][4];
+        int cnt[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+            snt[0][nt] = tsnt[0][nt]; snt[1][nt] = tsnt[1][nt];
+            srd[0][nt] = tsrd[0][nt]; srd[1][nt] = tsrd[1][nt];
+            cnt[nt] = tcnt[nt];
+        }
+        int m = 0;       // s's present records at p: nrec' = nrec - m
+        bool any_live = false;
+        for (int j = 0; j <= n_ext_max; ++j) { // the primary record, then the extras of p (record P + e0 + j - 1)
+            const bool has = j <= n_ext;
+            LooRec a = loo_rec<LAY, IRR>(rv, P, E, s, j == 0 || !has ? p : P + e0 + j - 1);
+            a.present &= has;
+            m += a.present ? 1 : 0;
+            const bool covok = a.present && a.FW >= cov && a.BW >= cov;
+            any_live |= valid && a.present && ref <= 3 && a.FW >= call_cov && a.BW >= call_cov;
+            const unsigned qual = thr_gate(a.fw, a.bw, a.FW, a.BW, covok, a.big);
+            if (qual) {
+                const double prod_fw = (double)((float)a.FW * C), prod_bw = (double)((float)a.BW * C); // EE:1597,1599
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) {
+                    if ((qual >> nt) & 1u) { // the addends of EE:1597-1606, taken out in the order they went in
+                        snt[0][nt] = snt[0][nt] - (double)a.fw[nt] - prod_fw;
+                        snt[1][nt] = snt[1][nt] - (double)a.bw[nt] - prod_bw;
+                        srd[0][nt] -= a.FW;
+                        srd[1][nt] -= a.BW;
+                        cnt[nt] -= 1;
+                    }
+                }
+            }
+        }
+        // 2. the S-1 table's thresholds: quorum, fp32 rate, NaN -> NONE, text round trip, 0.01 for NONE (finalize_one)
+        float thr[2][4] = {{0.01f, 0.01f, 0.01f, 0.01f}, {0.01f, 0.01f, 0.01f, 0.01f}}; // read only where a record is live
+        int tcode[4] = {1, 1, 1, 1};
+        if (any_live || thr_loo) {
+#pragma unroll
+            for (int nt = 0; nt < 4; ++nt) {
+                float r_fw, r_bw;
+                const unsigned char c = tcode[nt] = fin_rates(snt[0][nt], snt[1][nt], srd[0][nt], srd[1][nt], cnt[nt], tnrec - m, r_fw, r_bw);
+                thr[0][nt] = c ? 0.01f : ampli_text_roundtrip(r_fw); // EE:2680-2684 / EE:1704 -> VC:889-890
+                thr[1][nt] = c ? 0.01f : ampli_text_roundtrip(r_bw);
+                if (thr_loo && valid) {
+                    thr_loo[((size_t)s * 8 + nt) * P + p] = thr[0][nt];
+                    thr_loo[((size_t)s * 8 + 4 + nt) * P + p] = thr[1][nt];
+                }
+            }
+        }
+        // 3. VC's gate on each of s's records at p against those thresholds (poisson_stream_kernel's, per record)
+        int row_callable = 0;
+        for (int j = 0; j <= n_ext_max; ++j) {
+            const bool has = j <= n_ext;
+            const long long r = j == 0 || !has ? p : P + e0 + j - 1;
+            LooRec a = loo_rec<LAY, IRR>(rv, P, E, s, r);
+            a.present &= has;
+            const bool live = valid && a.present && ref <= 3 && a.FW >= call_cov && a.BW >= call_cov; // VC:898, VC:3290
+            row_callable += live ? 1 : 0;
+            const int d_fw = a.RD - a.BW, d_bw = a.BW; // VC:895-896
+            const bool exact = prefilter && (unsigned)a.RD < (unsigned)AMPLI_COUNT_LIMIT && a.FW >= 0 && a.BW >= 0 && d_fw >= 0;
+            const float c_fw = (float)d_fw * 0.999999f, c_bw = (float)d_bw * 0.999999f;
+            unsigned pushmask = 0;
+            if (live) {
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) { // ampli_prefilter_skip_f32: settles most pairs; what it does not skip is scored exactly
+                    const bool skip_fw = exact && (unsigned)a.fw[nt] < (unsigned)AMPLI_COUNT_LIMIT && (float)a.fw[nt] <= c_fw * ampli_effective_err(thr[0][nt]);
+                    const bool skip_bw = exact && (unsigned)a.bw[nt] < (unsigned)AMPLI_COUNT_LIMIT && (float)a.bw[nt] <= c_bw * ampli_effective_err(thr[1][nt]);
+                    if (nt != ref && !skip_fw && !skip_bw) pushmask |= 1u << nt;
+                }
+            }
+            if (__any(pushmask != 0)) {
+#pragma unroll
+                for (int nt = 0; nt < 4; ++nt) {
+                    const bool push = (pushmask >> nt) & 1;
+                    const unsigned long long bal = __ballot(push);
+                    if (bal) {
+                        const int k = __popcll(bal);
+                        if (staged + k > PC_STAGE) {
+                            pc_flush(stage[wave], staged, lane, queue, queue_per_shard, queue_n, shard, ctx_flags);
+                            staged = 0;
+                        }
+                        if (push) {
+                            PcItem it;
+                            it.sample = s; it.record_alt = (int)r | (nt << 30);
+                            it.k_fw = a.fw[nt]; it.k_bw = a.bw[nt]; it.FW = a.FW; it.BW = a.BW; it.rd = a.RD;
+                            it.e_fw = thr[0][nt]; it.e_bw = thr[1][nt]; it.pad = tcode[nt];
+                            stage[wave][staged + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0))] = it;
+                        }
+                        staged += k;
+                    }
+                }
+            }
+        }
+        callable += row_callable;
+        if (callable_sample) { // one reduction and one atomic per (wave, row)
+            int w = row_callable;
+#pragma unroll
+            for (int off = 32; off >= 1; off >>= 1) w += __shfl_xor(w, off);
+            if (lane == 0 && w) atomicAdd(&callable_sample[s], w);
+        }
+    }
+    if (staged) pc_flush(stage[wave], staged, lane, queue, queue_per_shard, queue_n, shard, ctx_flags);
+    if (callable_pos) {
+        lds_callable[wave][lane] = callable;
+        __syncthreads();
+        if (wave == 0 && valid) callable_pos[p] += lds_callable[0][lane] + lds_callable[1][lane] + lds_callable[2][lane] + lds_callable[3][lane];
+    }
+}
+
+extern "C" int ampli_loo_call_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_acc_table *d_acc, float C,
+                                      int32_t cov, int32_t call_cov, const uint8_t *d_ref_code, int32_t mode, uint8_t *d_call_mask,
+                                      ampli_loo_call *d_calls, int64_t capacity, unsigned long long *d_n_calls, int32_t *d_callable_pos,
+                                      int32_t *d_callable_sample, float *d_thr_loo, int32_t *d_flags)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    DevCohort co;
+    { int rc = cohort_from_records(ctx, recs, P, co); if (rc) return rc; }
+    if (P <= 0 || !d_ref_code || !d_call_mask || cov < 1 || call_cov < 1) return fail(ctx, AMPLI_E_INVALID, "loo_call: bad argument");
+    if (!acc_is_bound(d_acc) || d_acc->P != P) return fail(ctx, AMPLI_E_INVALID, "loo_call: d_acc must be an ampli_acc_bind table of P positions");
+    { int rc = check_records(ctx, co, "loo_call", co.dup_off, "dup_off"); if (rc) return rc; }
+    if (mode != AMPLI_POISSON_FULL && mode != AMPLI_POISSON_PREFILTER) return fail(ctx, AMPLI_E_INVALID, "loo_call: bad mode");
+    if (d_calls && (!d_n_calls || capacity < AMPLI_CALL_SHARDS)) return fail(ctx, AMPLI_E_INVALID, "loo_call: call list needs n_calls and capacity >= AMPLI_CALL_SHARDS");
+    if (d_n_calls && !d_calls) capacity = 0;
+    if (((uintptr_t)d_call_mask & 3) != 0) return fail(ctx, AMPLI_E_INVALID, "loo_call: call_mask must be 4-byte aligned");
+    const long long E = co.E, R = P + E;
+    const int n = co.n;
+    if (R >= (1ll << 30)) return fail(ctx, AMPLI_E_RANGE, "loo_call: P + E must be below 2^30 records per sample");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rcj = join_drain(ctx); if (rcj) return rcj; } // the queue and its counters are about to be reused
+    { int rcl = ensure_lgtab(ctx); if (rcl) return rcl; }
+    hipStream_t st = main_stream(ctx);
+    // all-scores mode queues every live (record, alt) pair: the drain's exact bound decides them all
+    // items go to shard blockIdx.x % AMPLI_CALL_SHARDS, one workgroup = one tile of 64 positions: a shard takes at most
+    // ceil(tiles / SHARDS) tiles' worth of pairs (3 alternatives of every record of the tile's positions, extras included), which is
+    // what the all-scores mode sizes for; ampli_set_queue_items raises either mode's size
+    const unsigned tiles = (unsigned)((P + 63) / 64);
+    const size_t shard_tiles = (tiles + AMPLI_CALL_SHARDS - 1) / AMPLI_CALL_SHARDS;
+    size_t want = mode == AMPLI_POISSON_FULL ? (size_t)AMPLI_CALL_SHARDS * shard_tiles * 3 * ((size_t)n * 64 + (size_t)n * (size_t)E)
+                                             : (size_t)std::max<long long>(1 << 16, (long long)n * R / 4);
+    if (ctx->queue_min_items) want = std::max(want, ctx->queue_min_items + (size_t)AMPLI_CALL_SHARDS * shard_tiles * 3 * 64 * (size_t)n);
+    long long per;
+    unsigned long long *qn, *qn_next;
+    { int rcq = queue_prepare(ctx, ctx->lanes[0].q, want, st, per, qn, qn_next); if (rcq) return rcq; }
+    HIP_TRY(ctx, hipMemsetAsync(d_call_mask, 0, ((size_t)n * (size_t)R + 3) / 4 * 4, st));
+    with_layout(co.layout, [&](auto L) {
+        with_bool(co.rv.rd || co.rv.rd_ext, [&](auto IRR) {
+            hipLaunchKernelGGL((loo_stream_kernel<L, IRR>), dim3(tiles), dim3(256), 0, st, co.rv, (long long)P, E, co.dup_off, n, to_ptrs(d_acc), C,
+                               (int)cov, (int)call_cov, d_ref_code, mode == AMPLI_POISSON_PREFILTER ? 1 : 0, (PcItem *)ctx->lanes[0].q.items, per, qn,
+                               d_n_calls, d_callable_pos, d_callable_sample, d_thr_loo, d_flags, ctx->d_flags);
+        });
+    });
+    { int rc = check_launch(ctx, "loo_stream_kernel"); if (rc) return rc; }
+    const unsigned dgy = (unsigned)(ctx->pc_drain_blocks > 0 ? ctx->pc_drain_blocks
+                                                             : std::min<long long>(1024, std::max<long long>(16, (long long)n * R / 300000)));
+    hipLaunchKernelGGL(loo_drain_kernel, dim3(AMPLI_CALL_SHARDS, dgy), dim3(256), 0, st, (const PcItem *)ctx->lanes[0].q.items, per, qn, (long long)R,
+                       (unsigned *)d_call_mask, d_calls, (long long)capacity, d_n_calls, qn_next, (const double *)ctx->d_lgtab);
+    return check_launch(ctx, "loo_drain_kernel");
 }
 
 // ==== auxiliary and synthetic: scorer checks, synthetic panels =========================================================================

@@ -458,6 +458,14 @@ extern "C" int ampli_set_queue_items(ampli_ctx *ctx, int64_t items)
     return AMPLI_OK;
 }
 
+extern "C" int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes)
+{
+    if (!ctx || !free_bytes || !total_bytes) return AMPLI_E_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipMemGetInfo(free_bytes, total_bytes));
+    return AMPLI_OK;
+}
+
 extern "C" int ampli_ctx_flags(ampli_ctx *ctx, int32_t *out, int32_t clear)
 {
     if (!ctx || !out) return AMPLI_E_INVALID;

@@ -55,6 +55,9 @@ struct HipApi {
                                        double *, float *);
     int (*last_reduce_kernel)(const ampli_ctx *);
     int (*error_sums_inorder)(ampli_ctx *, const ampli_records *, int64_t, float, int32_t, const ampli_acc_table *, int32_t);
+    int (*loo_call_records)(ampli_ctx *, const ampli_records *, int64_t, const ampli_acc_table *, float, int32_t, int32_t, const uint8_t *, int32_t,
+                            uint8_t *, ampli_loo_call *, int64_t, unsigned long long *, int32_t *, int32_t *, float *, int32_t *);
+    int (*mem_info)(ampli_ctx *, size_t *, size_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

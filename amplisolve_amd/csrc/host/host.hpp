@@ -211,6 +211,12 @@ void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 void finish_process(int status);
 int run_error_estimation(const EeArgs &a);
 int run_variant_calling(const VcArgs &a);
+// AmpliSolveLeaveOneOut (loo_main.cpp): C_value is one value or a comma-separated list; exit status 0 / 1
+struct LooArgs {
+    std::string panel_design, reference_genome, germline_dir, C_value = "0.002", coverage_cutoff = "100", calling_cutoff = "100", output_dir;
+    std::string refbases_file;
+};
+int run_leave_one_out(const LooArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

@@ -1,0 +1,42 @@
+// AmpliSolveLeaveOneOut -- the leave-one-out false-call check of a panel of normals, in the reference's key=value style.
+//   AmpliSolveLeaveOneOut panel_design=<bed> reference_genome=<fa> germline_dir=<dir> C_value=<f>[,<f>...] coverage_cutoff=<i>
+//                         calling_cutoff=<i> output_dir=<dir>
+// Exactly 7 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
+#include <clocale>
+#include <cstdio>
+#include <cstdlib>
+#include <iostream>
+
+#include "host.hpp"
+
+static std::string token(const char *arg, const char *key)
+{
+    char buf[4096];
+    buf[0] = 0;
+    std::string fmt = std::string(key) + "=%4000s";
+    sscanf(arg, fmt.c_str(), buf);
+    return buf;
+}
+
+int main(int argc, char **argv)
+{
+    setlocale(LC_ALL, "");
+    if (argc != 8) {
+        std::cout << "Usage:\n\tAmpliSolveLeaveOneOut panel_design=<bed> reference_genome=<fasta> germline_dir=<dir> C_value=<float>[,<float>...] "
+                     "coverage_cutoff=<int> calling_cutoff=<int> output_dir=<dir>\n\tAll arguments are required, in this order." << std::endl;
+        return 1;
+    }
+    ampli::LooArgs a;
+    a.panel_design = token(argv[1], "panel_design");
+    a.reference_genome = token(argv[2], "reference_genome");
+    a.germline_dir = token(argv[3], "germline_dir");
+    a.C_value = token(argv[4], "C_value");
+    a.coverage_cutoff = token(argv[5], "coverage_cutoff");
+    a.calling_cutoff = token(argv[6], "calling_cutoff");
+    a.output_dir = token(argv[7], "output_dir");
+    if (const char *e = getenv("AMPLISOLVE_REFBASES_FILE")) a.refbases_file = e;
+    const int rc = ampli::run_leave_one_out(a);
+    std::cout.flush();
+    ampli::finish_process(rc ? 1 : 0);
+    return rc ? 1 : 0;
+}

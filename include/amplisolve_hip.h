@@ -411,6 +411,41 @@ int ampli_poisson_call_records(ampli_ctx *ctx, const ampli_records *trecs, int64
                                const uint8_t *d_ref_code, int32_t coverage_cutoff, int32_t mode, uint8_t *d_call_mask,
                                ampli_call *d_calls, int64_t capacity, unsigned long long *d_n_calls, double *d_q, float *d_af);
 
+/*
+ * loo_call -- the leave-one-out check of the panel of normals: for every normal s of the chunk `recs` and every
+ * position p, the calling gate of VC (poisson_call's: VC:752-898, VC:3290) on s's records at p (primary and extra occurrences)
+ * against the thresholds of the error table that the cohort WITHOUT s gives (EE with C and coverage_cutoff over the other S-1
+ * normals), with calling_cutoff as VC's coverage_cutoff.  What a normal is called for is a false call of the noise model.
+ *   d_acc           the WHOLE cohort's accumulator table, reduced with the SAME C and coverage_cutoff as given here
+ *                   (ampli_error_reduce_records over every chunk; AMPLI_REDUCE_SUMMARY is enough: snt / srd / cnt / nrec are exact;
+ *                   a table of other parameters gives wrong thresholds and is not detected); the S-1 sums are the totals minus s's own contribution, which is
+ *                   exact inside the exactness envelope only: *d_flags is OR-ed with 1 when a total is outside it (then the
+ *                   results are not the reference's; the caller must refuse)
+ *   recs            one resident chunk of that cohort (any layout, dup_off required when E > 0; rd / rd_ext as for error_reduce);
+ *                   call once per chunk.  Samples are chunk-local everywhere below.
+ *   d_call_mask     [n][P + E] uint8, bit a = alt a called at that record (4-byte aligned; cleared by the call)
+ *   d_calls / capacity / d_n_calls   the compact list as for ampli_poisson_call, entries ampli_loo_call
+ *   d_callable_pos  int32 [P], optional, ADDED to: records of the chunk at p with ref in ACGT, FW >= and BW >= calling_cutoff
+ *   d_callable_sample int32 [n], optional, ADDED to: the same per sample
+ *   d_thr_loo       float [n][2][4][P], optional dense S-1 thresholds (the text round trip; 0.01 where the estimate is missing)
+ *   mode            AMPLI_POISSON_PREFILTER, or AMPLI_POISSON_FULL: every live pair scored by the drain's exact bound (same outputs)
+ * The queue is poisson_call's: AMPLI_FLAG_QUEUE_OVERFLOW as there; ampli_set_queue_items or AMPLI_POISSON_FULL (sized for every
+ * live pair of the worst shard) recover.
+ */
+typedef struct ampli_loo_call {
+    ampli_call call;      /* as poisson_call's list entry; call.sample = the held-out row of the chunk */
+    float thr_fw, thr_bw; /* the S-1 table's threshold of the pair's (position, alt): what VC would read back from the table text */
+    int32_t code;         /* that table cell's code: 0 estimate (the text is %f of the rate), 1 below quorum, 2 NaN (the text is 0.01) */
+    int32_t pad;
+} ampli_loo_call;         /* 80 bytes */
+int ampli_loo_call_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_acc_table *d_acc, float C,
+                           int32_t coverage_cutoff, int32_t calling_cutoff, const uint8_t *d_ref_code, int32_t mode,
+                           uint8_t *d_call_mask, ampli_loo_call *d_calls, int64_t capacity, unsigned long long *d_n_calls,
+                           int32_t *d_callable_pos, int32_t *d_callable_sample, float *d_thr_loo, int32_t *d_flags);
+
+/* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
+int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);
+
 /* Asynchronous drain (opt-in).  In prefilter mode poisson_call is two kernels; the second (the dense drain of the
  * queued survivors) is one fp64 scorer chain long and independent of what the caller enqueues next.  With
  * ampli_set_async_drain(ctx, 1) it runs on a side stream of the context: the call mask, the call list and
