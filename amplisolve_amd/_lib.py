@@ -137,6 +137,8 @@ HIP_SYMBOLS = {
     "ampli_set_async_drain": (C.c_int, [vp, i32]),
     "ampli_wait_calls": (C.c_int, [vp]),
     "ampli_mem_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz)]),
+    "ampli_limit_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, vp, i32, vp, vp, vp]),
+    "ampli_limit_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), i32]),
 }
 
 class HostShard(C.Structure):
@@ -200,6 +202,8 @@ HOST_SYMBOLS = {
     "ampli_host_fisher": (C.c_double, [C.c_int] * 4),
     "ampli_host_fisher_direct": (C.c_double, [C.c_int] * 4),
     "ampli_host_guard_score": (C.c_double, [i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]),
+    "ampli_host_limit_reads": (i32, [i32, f32, i32]),
+    "ampli_host_limit_search": (i32, [i32, f32, i32, C.POINTER(i32)]),
 }
 
 _hip = None

@@ -17,6 +17,10 @@ POISSON_PREFILTER = 1
 CALL_SHARDS = 32            # AMPLI_CALL_SHARDS
 CALL_COUNTER_STRIDE = 16    # AMPLI_CALL_COUNTER_STRIDE
 CALL_COUNTER_WORDS = CALL_SHARDS * CALL_COUNTER_STRIDE
+# AMPLI_LIMIT_* of include/amplisolve_hip.h (Context.detection_limits)
+LIMIT_OK, LIMIT_REF, LIMIT_NOREF, LIMIT_LOWDEPTH, LIMIT_NOESTIMATE, LIMIT_UNREACHABLE, LIMIT_ABSENT = range(7)
+LIMIT_CALLED, LIMIT_RECHECK = 0x40, 0x80
+LIMIT_COUNTERS = 6
 
 
 def _ptr(t):
@@ -321,6 +325,31 @@ class Context:
         self._check(self.lib.ampli_poisson_call_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), cov, mode, _ptr(call_mask),
                                                         _ptr(calls_buf), capacity, _ptr(n_calls), None, None))
         return dict(call_mask=call_mask, q=None, af=None, calls_buf=calls_buf, n_calls=n_calls, capacity=capacity)
+
+    def detection_limits(self, rec: Records, P: int, thr, ref_code, cov: int = 100, levels=(), counts=None):
+        """Detection limits of the calling gate for one resident chunk (ampli_limit_records): per record and base the smallest
+        alternative counts (forward, reverse) with which the gate would pass on that line's own depths.  Returns min_reads int32
+        [n, P + E, 4, 2], status uint8 [n, P + E, 4] (LIMIT_* in bits 0-2, LIMIT_CALLED, LIMIT_RECHECK: to be settled with
+        ampli_host_limit_reads) and counts int64 [n, 6 + len(levels)] (added to when given): lines without a reference base, pairs OK /
+        LOWDEPTH / NOESTIMATE / UNREACHABLE / RECHECK, and per level the OK pairs with MinAF <= level."""
+        import torch
+
+        n, R = rec.n_samples, P + rec.E
+        d = self.device
+        lv = torch.tensor([float(x) for x in levels], dtype=torch.float32, device=d) if len(levels) else None
+        min_reads = torch.empty((n, R, 4, 2), dtype=torch.int32, device=d)
+        status = torch.empty((n, R, 4), dtype=torch.uint8, device=d)
+        if counts is None:
+            counts = torch.zeros((n, LIMIT_COUNTERS + len(levels)), dtype=torch.int64, device=d)
+        self._check(self.lib.ampli_limit_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), cov, _ptr(lv), len(levels), _ptr(min_reads),
+                                                 _ptr(status), _ptr(counts)))
+        return dict(min_reads=min_reads, status=status, counts=counts)
+
+    def limit_stats(self, reset: bool = False):
+        """(strands searched, scorer evaluations, the most evaluations of one strand) of this context's detection_limits calls"""
+        out = (C.c_uint64 * 3)()
+        self._check(self.lib.ampli_limit_stats(self.h, out, int(reset)))
+        return int(out[0]), int(out[1]), int(out[2])
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

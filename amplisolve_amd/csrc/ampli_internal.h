@@ -63,6 +63,8 @@ struct ampli_ctx {
     int pc_rows_per_wave = 0, pc_drain_blocks = 0;
     // kf_lgamma at the integers 0 .. AMPLI_LGTAB - 1, filled by the device's own ampli_kf_lgamma (the all-scores mode's scorer)
     double *d_lgtab = nullptr;
+    // limit_records' scorer evaluations: strands searched, evaluations, the most of one strand (ampli_limit_stats)
+    unsigned long long *d_limit_stats = nullptr;
 };
 // 65537 entries (512 KB, L2-resident): every count a uint16 record can hold, + 1 for the drain's kf_lgamma(k + 1).  (4096 until round 6:
 // a wave of the drain in which ONE lane carries a count beyond the table -- a heterozygous site at 10 000 x -- runs the Lanczos form, 8

@@ -358,4 +358,87 @@ AMPLI_FN int ampli_prefilter_skip_f32(int32_t k, int32_t rd, float err_eff)
     return (float)k <= c * err_eff;
 }
 
+// ---------------------------------------------------------------------------
+// Detection limit of the calling gate: the smallest count k in 1 .. bound of one strand with Q(k, depth, thr) >= 5
+// (VC:898 with VC:3834-3884), found without scanning from k = 1:
+//   * nothing passes at k <= m = depth * thr (ampli_prefilter_nocall's bound), so the walk starts at floor(m) + 1 or, for larger
+//     means up to AMPLI_LIMIT_SEED_MAX_M, at floor(m + 0.4 sqrt(m + 1)) -- the first passing count was never seen below
+//     m + 0.45 sqrt(m + 1) there (tests/test_limit_host.py re-asserts both on random strands).  For much larger means the 99-term
+//     cap of the series (VC:3783) cuts p short and the first passing count comes back to floor(m) + 1: no seed there;
+//   * every candidate lies above m, i.e. on the series branch of kf_gammaq (VC:3728): ampli_drain_p evaluates it;
+//   * the answer k is only given with its bracket: Q(k) >= 5 and (k == 1 or k - 1 <= m or Q(k - 1) < 5), every Q decided outside
+//     the band of AMPLI_LIMIT_BAND around the gate.  A seed that turns out to pass walks DOWN until the bracket closes.
+// Whatever this arithmetic cannot decide -- a Q inside the band, a mean that is not a positive finite number, a walk longer than
+// AMPLI_LIMIT_MAX_EVALS -- is AMPLI_LIMK_RECHECK: the host settles it with the literal scan (ampli_host_limit_reads).
+// One ampli_limit_step is ONE scorer evaluation, so that a kernel can run the steps of several strands in a single loop.
+// ---------------------------------------------------------------------------
+#define AMPLI_LIMIT_BAND 1e-6           // = AMPLI_CALL_GATE_EPS of include/amplisolve_hip.h
+#define AMPLI_LIMIT_MAX_EVALS 128       // the longest walk seen on 200 000 random strands is 26 evaluations from floor(m) + 1
+#define AMPLI_LIMK_PENDING (-3)        // the search goes on
+#define AMPLI_LIMK_RECHECK (-2)        // not decided here
+#define AMPLI_LIMK_NOESTIMATE (-1)     // thr == -1: Q = -888 for every count (VC:3844-3849)
+#define AMPLI_LIMK_UNREACHABLE 0       // no count in 1 .. bound passes
+#define AMPLI_LIMIT_SEED 0.4
+#define AMPLI_LIMIT_SEED_MAX_M 1024.0   // beyond: the series is cut at 99 terms long before it converges and the first passing count falls back towards m
+
+typedef struct {
+    double m;      // depth * thr (VC:3864)
+    int32_t k;     // the candidate
+    int32_t bound; // the strand's reads: no more than these can be alternative
+    int32_t below; // k - 1 is known not to pass (k == 1, k - 1 <= m, or evaluated)
+    int32_t down;  // k has passed: the evaluation in hand is the bracket check of k - 1
+    int32_t evals;
+    int32_t res;   // AMPLI_LIMIT_* or the smallest passing count
+} ampli_limit_search;
+
+AMPLI_FN void ampli_limit_init(ampli_limit_search *s, int32_t depth, float thr, int32_t bound)
+{
+    s->m = 0; s->k = 0; s->bound = bound; s->below = 1; s->down = 0; s->evals = 0; s->res = AMPLI_LIMK_PENDING;
+    if (thr == -1) { s->res = AMPLI_LIMK_NOESTIMATE; return; }
+    if (thr == 0) thr = 0.0010008f;                                      // VC:3852-3856
+    if (depth <= 0 || bound < 1) { s->res = AMPLI_LIMK_UNREACHABLE; return; }
+    const double m = (double)depth * thr;                                // VC:3864: double * float
+    if (!(m > 0 && m < 2147483000.0)) { s->res = AMPLI_LIMK_RECHECK; return; } // negative, NaN, infinite or beyond an int count
+    s->m = m;
+    const int32_t k0 = (int32_t)floor(m) + 1;
+    if (k0 > bound) { s->res = AMPLI_LIMK_UNREACHABLE; return; }        // every k <= bound is <= m
+    int32_t k = m <= AMPLI_LIMIT_SEED_MAX_M ? (int32_t)floor(m + AMPLI_LIMIT_SEED * sqrt(m + 1.)) : k0;
+    if (k < k0) k = k0;
+    if (k > bound) k = bound;
+    s->k = k;
+    s->below = k == k0;                                                  // k - 1 = floor(m) <= m (k0 == 1: k == 1)
+}
+
+AMPLI_FN void ampli_limit_step(ampli_limit_search *s, const double *lgtab, int ntab)
+{
+    const int32_t kk = s->down ? s->k - 1 : s->k;                        // m < kk always
+    const double q = ampli_q_from_p(ampli_drain_p(kk, s->m, lgtab, ntab));
+    ++s->evals;
+    if (!(q < 5.0 - AMPLI_LIMIT_BAND) && !(q >= 5.0 + AMPLI_LIMIT_BAND)) { s->res = AMPLI_LIMK_RECHECK; return; } // in the band, or NaN
+    const int pass = q >= 5.0;
+    if (s->down) {
+        if (!pass) { s->res = s->k; return; }
+        --s->k;                                                          // the seed was above the limit: one down
+        if ((double)(s->k - 1) <= s->m) { s->res = s->k; return; }       // also k == 1
+    } else if (pass) {
+        if (s->below) { s->res = s->k; return; }
+        s->down = 1;
+    } else {
+        s->below = 1;
+        if (s->k >= s->bound) { s->res = AMPLI_LIMK_UNREACHABLE; return; }
+        ++s->k;
+    }
+    if (s->evals >= AMPLI_LIMIT_MAX_EVALS) s->res = AMPLI_LIMK_RECHECK;
+}
+
+// the whole search of one strand (host, tests, and lanes that own a single strand)
+AMPLI_FN int32_t ampli_limit_reads(int32_t depth, float thr, int32_t bound, const double *lgtab, int ntab, int32_t *evals)
+{
+    ampli_limit_search s;
+    ampli_limit_init(&s, depth, thr, bound);
+    while (s.res == AMPLI_LIMK_PENDING) ampli_limit_step(&s, lgtab, ntab);
+    if (evals) *evals = s.evals;
+    return s.res;
+}
+
 #endif

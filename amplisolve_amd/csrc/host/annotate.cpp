@@ -34,6 +34,31 @@ long double score_reference_sequence(int k, int rd, float err)
     return Q;
 }
 
+// The detection limit of one strand, literally: every count from 1 upwards through the reference's operation sequence.
+// This is the definition; the device's search (ampli_limit_reads of ampli_math.h) has to land on the same count or say RECHECK.
+int limit_reads_literal(int depth, float thr, int bound)
+{
+    if (thr == -1) return -1;
+    if (depth <= 0) return 0;
+    for (int k = 1; k <= bound; ++k)
+        if (score_reference_sequence(k, depth, thr) >= 5) return k;
+    return 0;
+}
+
+PairLimit limit_pair_literal(const int32_t rec[8], int rd, int nt, float thr_fw, float thr_bw, int cov)
+{
+    PairLimit out{AMPLI_LIMIT_OK, 0, 0, false};
+    const int FW = rec[0] + rec[1] + rec[2] + rec[3], BW = rec[4] + rec[5] + rec[6] + rec[7]; // VC:760-761
+    if (FW < cov || BW < cov) { out.status = AMPLI_LIMIT_LOWDEPTH; return out; }                // VC:898
+    out.called = score_reference_sequence(rec[nt], rd - BW, thr_fw) >= 5 && score_reference_sequence(rec[4 + nt], BW, thr_bw) >= 5;
+    if (thr_fw == -1 || thr_bw == -1) { out.status = AMPLI_LIMIT_NOESTIMATE; return out; }
+    const int mf = limit_reads_literal(rd - BW, thr_fw, FW); // VC:895: forward depth is RD - RD_reverse
+    const int mb = mf > 0 ? limit_reads_literal(BW, thr_bw, BW) : 0;
+    if (mf <= 0 || mb <= 0) { out.status = AMPLI_LIMIT_UNREACHABLE; return out; }
+    out.min_fw = mf; out.min_bw = mb;
+    return out;
+}
+
 // Two-sided Fisher exact test as VC:3797-3814 forms it: N = a+b+c+d, r = a+c, n = c+d, sum of the
 // hypergeometric pmf over all k whose probability does not exceed that of the observed k = c.
 // The reference takes the pmf from Boost.Math (absent here, not vendored by the reference): this is an own

@@ -569,6 +569,8 @@ void ring_free(void *&p, bool &pinned)
 
 } // namespace
 
+void record_unpack(int layout, const char *src, int32_t rec[8]) { get_record(layout, src, rec); }
+
 // ---------------------------------------------------------------------------------------------------------
 // ChunkStream: the cohort as a sequence of chunks of consecutive samples, parsed by a producer thread (+ workers)
 // into a small ring of pinned buffers while the consumer uploads / reduces the previous chunk.

@@ -58,6 +58,8 @@ struct HipApi {
     int (*loo_call_records)(ampli_ctx *, const ampli_records *, int64_t, const ampli_acc_table *, float, int32_t, int32_t, const uint8_t *, int32_t,
                             uint8_t *, ampli_loo_call *, int64_t, unsigned long long *, int32_t *, int32_t *, float *, int32_t *);
     int (*mem_info)(ampli_ctx *, size_t *, size_t *);
+    int (*limit_records)(ampli_ctx *, const ampli_records *, int64_t, const float *, const uint8_t *, int32_t, const float *, int32_t, int32_t *,
+                         uint8_t *, int64_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

@@ -158,6 +158,7 @@ std::vector<std::pair<std::string, std::string>> shard_of_files(const std::vecto
                                                                 int shard_count, int *first);
 size_t record_bytes(int layout);
 void fill_absent(int layout, char *dst, size_t n_records);
+void record_unpack(int layout, const char *src, int32_t rec[8]); // one packed record -> the eight int32 counts (absent: rec[0] = AMPLI_ABSENT)
 // shard_index / shard_count: keep only that contiguous range of the visit order (multi-process runs)
 void cohort_load(const Panel &panel, const std::string &dir, const std::string &list_file, int n_threads, bool keep_line_no,
                  bool print_irregular, Cohort &out, int shard_index = 0, int shard_count = 1);
@@ -217,10 +218,21 @@ struct LooArgs {
     std::string refbases_file;
 };
 int run_leave_one_out(const LooArgs &a);
+// AmpliSolveDetectionLimit (dl_main.cpp): levels is one allele fraction or a comma-separated list of up to 8; exit status 0 / 1
+struct DlArgs {
+    std::string error_file, tumour_dir, output_dir, coverage_cutoff = "100", levels;
+};
+int run_detection_limits(const DlArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)
 long double score_reference_sequence(int k, int rd, float err);                 // VC:3834-3884, for calls within rounding of a gate
+// detection limit of one strand by the literal scan: the smallest k in 1 .. bound with score_reference_sequence(k, depth,
+// thr) >= 5, scanning upwards from k = 1; -1 when thr == -1 (no estimate), 0 when there is none (also depth <= 0)
+int limit_reads_literal(int depth, float thr, int bound);
+// one (line, base) pair by the literal scan and the gate on the observed counts: status AMPLI_LIMIT_*, min reads (0 unless OK)
+struct PairLimit { int status, min_fw, min_bw; bool called; };
+PairLimit limit_pair_literal(const int32_t rec[8], int rd, int nt, float thr_fw, float thr_bw, int cov);
 std::string kmer_down(const Panel &p, const std::string &chrom, int pos);       // VC:3307-3458
 std::string kmer_up(const Panel &p, const std::string &chrom, int pos);         // VC:3461-3613
 int homopolymer_test(const std::string &down, const std::string &up, char sub); // VC:3615-3718

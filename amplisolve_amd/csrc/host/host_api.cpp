@@ -2,6 +2,7 @@
 #include <cstring>
 
 #include "../../../include/amplisolve_host.h"
+#include "../ampli_math.h"
 #include "host.hpp"
 
 using namespace ampli;
@@ -257,6 +258,13 @@ extern "C" double ampli_host_guard_score(int32_t k, int32_t rd, float err, int32
     if (ge5) *ge5 = q >= 5 ? 1 : 0;   // the comparisons of VC:898 / VC:1023, in long double like the reference's
     if (lt20) *lt20 = q < 20 ? 1 : 0;
     return (double)q;
+}
+
+extern "C" int32_t ampli_host_limit_reads(int32_t depth, float thr, int32_t bound) { return limit_reads_literal(depth, thr, bound); }
+
+extern "C" int32_t ampli_host_limit_search(int32_t depth, float thr, int32_t bound, int32_t *evals)
+{
+    return ampli_limit_reads(depth, thr, bound, nullptr, 0, evals);
 }
 
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)

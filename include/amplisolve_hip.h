@@ -443,6 +443,41 @@ int ampli_loo_call_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P,
                            uint8_t *d_call_mask, ampli_loo_call *d_calls, int64_t capacity, unsigned long long *d_n_calls,
                            int32_t *d_callable_pos, int32_t *d_callable_sample, float *d_thr_loo, int32_t *d_flags);
 
+/*
+ * limit_records -- per-sample detection limits of the calling gate.  For every record of the chunk `trecs` (any layout,
+ * ext_pos required when E > 0, rd / rd_ext as for poisson_call) and every base nt other than the position's reference base: the
+ * smallest alternative counts (forward, reverse) with which the gate of VC:898 -- FW >= and BW >= coverage_cutoff,
+ * Q(k_fw, RD - BW, thr_fw) >= 5 and Q(k_bw, BW, thr_bw) >= 5 -- would pass on that line's own depths, each strand's count bounded
+ * by the strand's reads.  Asynchronous on the context's stream.
+ *   d_thr        float [2][4][P] as for ampli_poisson_call;  d_ref_code uint8 [P]
+ *   d_levels     float [n_levels], 0 <= n_levels <= AMPLI_LIMIT_MAX_LEVELS (may be NULL when n_levels == 0)
+ *   d_min_reads  int32 [n][P + E][4][2] (fw, bw), 8-byte aligned; 0 unless the status is OK
+ *   d_status     uint8 [n][P + E][4]: AMPLI_LIMIT_* below in bits 0-2; AMPLI_LIMIT_CALLED: the gate passes on the observed counts
+ *                (ampli_poisson_call's mask bit); AMPLI_LIMIT_RECHECK: the device's arithmetic does not decide this cell (a score
+ *                within AMPLI_CALL_GATE_EPS of the gate, a strand mean that is not a positive finite number): status, counts and the
+ *                called bit of the cell are to be settled by the host (ampli_host_limit_reads); its other bits are 0
+ *   d_counts     int64 [n][6 + n_levels], ADDED to: lines with a reference code > 3 | pairs OK | LOWDEPTH | NOESTIMATE |
+ *                UNREACHABLE | RECHECK (counted nowhere else) | per level: OK pairs with MinAF = float(min_fw + min_bw) / float(RD)
+ *                <= level
+ */
+#define AMPLI_LIMIT_OK 0          /* both strands have a smallest passing count */
+#define AMPLI_LIMIT_REF 1         /* the position's reference base */
+#define AMPLI_LIMIT_NOREF 2       /* the reference code is not A, C, G or T: the line gives no pairs (VC:3290) */
+#define AMPLI_LIMIT_LOWDEPTH 3    /* FW < coverage_cutoff or BW < coverage_cutoff */
+#define AMPLI_LIMIT_NOESTIMATE 4  /* a strand's threshold is -1 (Q = -888, VC:3844-3849) */
+#define AMPLI_LIMIT_UNREACHABLE 5 /* not even every read of a strand would pass */
+#define AMPLI_LIMIT_ABSENT 6      /* the sample has no such line */
+#define AMPLI_LIMIT_CALLED 0x40
+#define AMPLI_LIMIT_RECHECK 0x80
+#define AMPLI_LIMIT_MAX_LEVELS 8
+#define AMPLI_LIMIT_COUNTERS 6
+int ampli_limit_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, const float *d_thr, const uint8_t *d_ref_code,
+                        int32_t coverage_cutoff, const float *d_levels, int32_t n_levels, int32_t *d_min_reads, uint8_t *d_status,
+                        int64_t *d_counts);
+/* scorer evaluations of the context's limit_records launches so far: out[0] strands searched, out[1] evaluations (bracket checks
+ * included), out[2] the most evaluations of one strand; reset != 0 clears them.  Synchronises the stream. */
+int ampli_limit_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset);
+
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);
 

@@ -163,6 +163,15 @@ int ampli_host_bam_scan(const char *bam, int32_t threads, int64_t *stats);
  * VC:898 / VC:1023 made in long double */
 double ampli_host_guard_score(int32_t k, int32_t rd, float err, int32_t *ge5, int32_t *lt20);
 
+/* Detection limit of the calling gate for one strand, the literal definition: the smallest k in 1 .. bound with
+ * Q(k, depth, thr) >= 5 in the reference's own operation sequence (as ampli_host_guard_score), scanning upwards from k = 1.
+ * Returns -1 when thr == -1 (no estimate), 0 when no such k exists (also for depth <= 0).  Settles the cells ampli_limit_records
+ * marks AMPLI_LIMIT_RECHECK. */
+int32_t ampli_host_limit_reads(int32_t depth, float thr, int32_t bound);
+/* the same count by the search the kernel runs (csrc/ampli_math.h: seeded walk and bracket check, fp64 with the host's libm), or -2
+ * where that arithmetic does not decide (the kernel's RECHECK); *evals (optional) = scorer evaluations spent */
+int32_t ampli_host_limit_search(int32_t depth, float thr, int32_t bound, int32_t *evals);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
