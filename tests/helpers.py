@@ -219,9 +219,11 @@ def write_bam(path, refs, reads, rng=None, max_block=60000, level=6, corrupt_blo
     return len(raw)
 
 
-def random_amplicon_reads(rng, refs, amplicons, n_reads, read_len=(60, 140)):
+def random_amplicon_reads(rng, refs, amplicons, n_reads, read_len=(60, 140), name_len=None, odd_ops=0.0, unplaced=0.0):
     """Reads in the style of amplicon sequencing: every read of an amplicon starts near its start; soft clips, insertions,
-    deletions, reverse strands, filtered flags, low qualities and N bases are all drawn."""
+    deletions, reverse strands, filtered flags, low qualities and N bases are all drawn.  Drawn only when asked for (the defaults
+    leave the stream of random numbers as it was): name_len = (lo, hi): read names of lo..hi bytes, the NUL included; odd_ops: the
+    share of reads that also get padding, zero-length operations and a leading hard clip; unplaced: the share of reads with pos -1."""
     reads = []
     for _ in range(n_reads):
         ref_id, start, end = amplicons[int(rng.integers(len(amplicons)))]
@@ -247,6 +249,11 @@ def random_amplicon_reads(rng, refs, amplicons, n_reads, read_len=(60, 140)):
             cigar.append(("S", int(rng.integers(1, 8))))
         if rng.random() < 0.1:
             cigar.append(("H", 5))
+        if odd_ops and rng.random() < odd_ops:
+            at = int(rng.integers(1, len(cigar) + 1))
+            cigar[at:at] = [("P", int(rng.integers(0, 4))), ("MIDNSHP=X"[int(rng.integers(9))], 0)]
+            if cigar[0][0] != "H" and rng.random() < 0.5:
+                cigar.insert(0, ("H", int(rng.integers(0, 9))))
         qlen = sum(n for op, n in cigar if op in "MIS=X")
         seq = "".join(rng.choice(list("ACGT"), size=qlen))
         if rng.random() < 0.2:
@@ -258,6 +265,10 @@ def random_amplicon_reads(rng, refs, amplicons, n_reads, read_len=(60, 140)):
                 flag |= bit
         reads.append(dict(ref_id=ref_id if rng.random() > 0.01 else -1, pos=pos, mapq=int(rng.choice([0, 5, 19, 20, 21, 40, 60])), flag=flag, cigar=cigar, seq=seq,
                           qual=[int(x) for x in rng.choice([2, 10, 19, 20, 21, 30, 40], size=qlen)]))
+        if name_len:
+            reads[-1]["name"] = "q" * (int(rng.integers(name_len[0], name_len[1] + 1)) - 1)
+        if unplaced and rng.random() < unplaced:
+            reads[-1]["pos"] = -1
     reads.sort(key=lambda r: (r["ref_id"] if r["ref_id"] >= 0 else 1 << 30, r["pos"]))
     return reads
 

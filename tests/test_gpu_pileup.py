@@ -9,6 +9,7 @@ import pytest
 
 from oracle import pileup_oracle as po
 from tests import helpers
+from tests import pileup_model
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -127,7 +128,7 @@ def test_long_reads_take_the_unstaged_walk(tmp_path):
                        capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stdout + r.stderr
     refs, recs = po.read_bam(tmp_path / "L.bam")
-    assert sum(len(x["seq"]) for x in recs[:256]) > 56 * 1024
+    assert sum(len(x["seq"]) for x in recs[:256]) > pileup_model.geometry().stage
     want = po.aseq_text(lines, po.pileup(refs, recs, [(c, p) for c, p, *_ in lines], 20, 20), 1)
     assert (tmp_path / "L.PILEUP.ASEQ").read_text() == want
 
