@@ -847,7 +847,7 @@ Chunk *ChunkStream::next()
         if (im->failed) throw im->err;
         return nullptr;
     }
-    // The consumers map ring slot k to device buffer k mod kDevSlots (pipeline.cpp) and that is only safe because a chunk is uploaded,
+    // The consumers map ring slot k to device buffer k mod kDevSlots (pipeline.hpp) and that is only safe because a chunk is uploaded,
     // consumed and waited for before the next one is taken: checked here rather than assumed.
     if (im->outstanding != 0) throw Error{AMPLI_E_INVALID, "ChunkStream::next(): the previous chunk was not released (its device buffers would be overwritten)"};
     const int slot = im->ready.front();

@@ -172,7 +172,7 @@ void panel_from_error_table(const std::string &path, const std::string &dummy_vc
 // ---- hip_loader.cpp ----
 struct HipApi; // function pointers of libamplisolve_hip.so
 const HipApi *hip_api(std::string *why = nullptr); // nullptr when the library cannot be loaded
-// ---- pipeline.cpp ----
+// ---- pipeline.cpp (what the commands share; its internal declarations: pipeline.hpp) ----
 // one process per GPU without Python: this process is shard `rank` of `world`, the exchange steps go over RCCL
 // (ampli_comm_* of include/amplisolve_hip.h); rank 0 publishes the communicator id in id_file
 struct NativeDist {
@@ -182,6 +182,9 @@ struct NativeDist {
 };
 // AMPLISOLVE_WORLD_SIZE / AMPLISOLVE_RANK / AMPLISOLVE_ID_FILE / AMPLISOLVE_RCCL_TIMEOUT (the executables' multi-GPU mode)
 NativeDist native_dist_from_env(const std::string &output_dir);
+// threads for a loop over n independent rows: one per `grain` rows, at most 16 and the machine's own, capped by AMPLISOLVE_THREADS
+int row_threads(size_t n, size_t grain);
+// the arguments of run_error_estimation (run_ee.cpp) and run_variant_calling (run_vc.cpp)
 struct EeArgs {
     std::string panel_design, reference_genome, germline_dir, output_dir;
     std::string C_value = "0.002", coverage_cutoff = "100", default_error = "0.01";
@@ -196,7 +199,8 @@ struct VcArgs {
     NativeDist native;
     bool process_ends = false;
 };
-// computeCounts (bam.cpp): one BAM file -> <out_dir>/<name>.PILEUP.ASEQ
+// ---- bam.cpp ----
+// computeCounts: one BAM file -> <out_dir>/<name>.PILEUP.ASEQ
 struct CcArgs {
     std::string vcf, bam, out_dir;
     int threads = 4, mbq = 20, mrq = 20, mdc = 20; // Execution_examples.md:46 recommends 20-20-20
@@ -206,10 +210,12 @@ struct CcArgs {
 int run_compute_counts(const CcArgs &a);
 // BGZF + BAM structure only (no GPU): stats[4] = alignment records, uncompressed bytes, references, malformed records
 void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
+// ---- pipeline.cpp ----
 // End of a command line: all outputs are written and closed.  Flushes stdio / iostreams and leaves with _exit(status), i.e.
 // without the static destructors and atexit handlers of the HIP runtime (queue / signal / pool teardown that only serves a
 // process that lives on; the driver reclaims everything at exit either way).  AMPLISOLVE_EXIT=orderly returns instead.
 void finish_process(int status);
+// ---- run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp ----
 int run_error_estimation(const EeArgs &a);
 int run_variant_calling(const VcArgs &a);
 // AmpliSolveLeaveOneOut (loo_main.cpp): C_value is one value or a comma-separated list; exit status 0 / 1

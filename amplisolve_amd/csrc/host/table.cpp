@@ -102,8 +102,7 @@ void write_error_table(const Panel &panel, const float *rate, const uint8_t *cod
 {
     const int64_t P = panel.P();
     const size_t n = panel.walk.size();
-    int n_threads = (int)std::min<size_t>(std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency())), std::max<size_t>(1, n / 4096));
-    if (const char *e = getenv("AMPLISOLVE_THREADS")) n_threads = std::max(1, std::min(n_threads, atoi(e)));
+    const int n_threads = row_threads(n, 4096);
     size_t longest_chrom = 0, longest_ref = 0;
     for (auto &c : panel.chroms) longest_chrom = std::max(longest_chrom, c.size());
     for (auto &r : panel.ref_base) longest_ref = std::max(longest_ref, r.size());
@@ -229,8 +228,7 @@ void panel_from_error_table(const std::string &path, const std::string &dummy_vc
     };
     const double tt1 = PhaseClock::now();
     std::vector<Parsed> rows(n_lines);
-    int n_threads = (int)std::min<size_t>(std::min<size_t>(16, std::max(1u, std::thread::hardware_concurrency())), std::max<size_t>(1, n_lines / 4096));
-    if (const char *e = getenv("AMPLISOLVE_THREADS")) n_threads = std::max(1, std::min(n_threads, atoi(e)));
+    const int n_threads = row_threads(n_lines, 4096);
     auto is_space = [](char ch) { return ch == ' ' || ch == '\t' || ch == '\r' || ch == '\n' || ch == '\v' || ch == '\f'; };
     auto work = [&](int t) { // tokenising + strtof are the expensive part of a row and independent of every other row
         const size_t i0 = n_lines * (size_t)t / (size_t)n_threads, i1 = n_lines * (size_t)(t + 1) / (size_t)n_threads;
