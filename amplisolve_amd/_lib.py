@@ -139,6 +139,8 @@ HIP_SYMBOLS = {
     "ampli_mem_info": (C.c_int, [vp, C.POINTER(sz), C.POINTER(sz)]),
     "ampli_limit_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, vp, i32, vp, vp, vp]),
     "ampli_limit_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), i32]),
+    "ampli_power_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, vp, i32, f32, vp, vp, vp]),
+    "ampli_power_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), i32]),
 }
 
 class HostShard(C.Structure):
@@ -204,6 +206,8 @@ HOST_SYMBOLS = {
     "ampli_host_guard_score": (C.c_double, [i32, i32, f32, C.POINTER(i32), C.POINTER(i32)]),
     "ampli_host_limit_reads": (i32, [i32, f32, i32]),
     "ampli_host_limit_search": (i32, [i32, f32, i32, C.POINTER(i32)]),
+    "ampli_host_binom_tail": (C.c_double, [i32, i32, C.c_double, C.POINTER(i32)]),
+    "ampli_host_power_pair": (C.c_int, [i32, i32, i32, i32, C.POINTER(f32), i32, f32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
 }
 
 _hip = None

@@ -351,6 +351,32 @@ class Context:
         self._check(self.lib.ampli_limit_stats(self.h, out, int(reset)))
         return int(out[0]), int(out[1]), int(out[2])
 
+    def detection_power(self, rec: Records, P: int, min_reads, status, levels=(), confidence: float = 0.95, counts=None, want_power: bool = True,
+                        want_lod: bool = True):
+        """Detection power and limit of detection for one resident chunk (ampli_power_records).  min_reads / status as detection_limits
+        returns them, the RECHECK cells settled.  Returns power float32 [n, P + E, 4, len(levels)] (the probability that a variant at
+        that allele fraction passes the gate; None with want_power=False), lod float32 [n, P + E, 4] (the allele fraction called with
+        probability `confidence`, in [0.5, 0.99]; None with want_lod=False) -- both 0 in every cell that is not OK -- and counts int64
+        [n, 1 + len(levels)] (added to when given): OK pairs, and per level the OK pairs with power >= confidence."""
+        import torch
+
+        n, R = rec.n_samples, P + rec.E
+        d = self.device
+        lv = torch.tensor([float(x) for x in levels], dtype=torch.float32, device=d) if len(levels) else None
+        power = torch.empty((n, R, 4, len(levels)), dtype=torch.float32, device=d) if want_power else None
+        lod = torch.empty((n, R, 4), dtype=torch.float32, device=d) if want_lod else None
+        if counts is None:
+            counts = torch.zeros((n, 1 + len(levels)), dtype=torch.int64, device=d)
+        self._check(self.lib.ampli_power_records(self.h, C.byref(rec), P, _ptr(min_reads), _ptr(status), _ptr(lv), len(levels), confidence,
+                                                 _ptr(power), _ptr(lod), _ptr(counts)))
+        return dict(power=power, lod=lod, counts=counts)
+
+    def power_stats(self, reset: bool = False):
+        """(tails evaluated, pmf terms summed, the most terms of one tail) of this context's detection_power calls"""
+        out = (C.c_uint64 * 3)()
+        self._check(self.lib.ampli_power_stats(self.h, out, int(reset)))
+        return int(out[0]), int(out[1]), int(out[2])
+
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,
                  n_calls=None, callable_pos=None, callable_sample=None, flags=None):

@@ -3,7 +3,7 @@
   lib/libamplisolve_hip.so   HIP kernels + C ABI (include/amplisolve_hip.h), hipcc --offload-arch=gfx950
   lib/libamplisolve_host.so  C++ host: BED / ASEQ / error-table parsers, SoA packer, writers (include/amplisolve_host.h)
   bin/AmpliSolveErrorEstimation, bin/AmpliSolveVariantCalling   the two drop-in command lines
-  bin/AmpliSolveLeaveOneOut, bin/AmpliSolveDetectionLimit       the project's own command lines
+  bin/AmpliSolveLeaveOneOut, bin/AmpliSolveDetectionLimit, bin/AmpliSolveDetectionPower   the project's own command lines
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the CPU-only container too.
 """
@@ -72,7 +72,8 @@ def build_host(force: bool = False) -> str:
     if force or _newer(HOST_LIB, deps):
         _run(["g++", *CXX_FLAGS, "-shared", "-o", HOST_LIB, *srcs, "-ldl", "-lz"])
     for exe, main in (("AmpliSolveErrorEstimation", "ee_main.cpp"), ("AmpliSolveVariantCalling", "vc_main.cpp"), ("computeCounts", "cc_main.cpp"),
-                      ("AmpliSolveLeaveOneOut", "loo_main.cpp"), ("AmpliSolveDetectionLimit", "dl_main.cpp")):
+                      ("AmpliSolveLeaveOneOut", "loo_main.cpp"), ("AmpliSolveDetectionLimit", "dl_main.cpp"),
+                      ("AmpliSolveDetectionPower", "dp_main.cpp")):
         msrc = os.path.join(hdir, main)
         out = os.path.join(BIN, exe)
         if os.path.exists(msrc) and (force or _newer(out, deps + [msrc, HOST_LIB])):

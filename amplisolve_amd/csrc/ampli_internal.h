@@ -65,6 +65,8 @@ struct ampli_ctx {
     double *d_lgtab = nullptr;
     // limit_records' scorer evaluations: strands searched, evaluations, the most of one strand (ampli_limit_stats)
     unsigned long long *d_limit_stats = nullptr;
+    // power_records' work: tails evaluated, pmf terms summed, the most terms of one tail (ampli_power_stats)
+    unsigned long long *d_power_stats = nullptr;
 };
 // 65537 entries (512 KB, L2-resident): every count a uint16 record can hold, + 1 for the drain's kf_lgamma(k + 1).  (4096 until round 6:
 // a wave of the drain in which ONE lane carries a count beyond the table -- a heterozygous site at 10 000 x -- runs the Lanczos form, 8

@@ -216,11 +216,12 @@ static int cohort_from_records(ampli_ctx *ctx, const ampli_records *r, int64_t P
     return AMPLI_OK;
 }
 
-// what every kernel reading a cohort needs of it: extras come with their index (`index`, called `index_name` in the message),
+// what every kernel reading a cohort needs of it: extras come with their index (`index`, called `index_name` in the message;
+// index_name == nullptr: the kernel needs no index of the extras and none is asked for),
 // records 16-byte aligned (8-byte in the 24-byte layout)
 static int check_records(ampli_ctx *ctx, const DevCohort &co, const char *what, const uint32_t *index, const char *index_name)
 {
-    if (co.E > 0 && !index) return fail(ctx, AMPLI_E_INVALID, (std::string(what) + ": E > 0 needs " + index_name).c_str());
+    if (co.E > 0 && !index && index_name) return fail(ctx, AMPLI_E_INVALID, (std::string(what) + ": E > 0 needs " + index_name).c_str());
     const uintptr_t am = co.layout == AMPLI_RECORDS_U24 ? 7 : 15;
     if (((uintptr_t)co.rv.base & am) != 0 || (co.E > 0 && ((uintptr_t)co.rv.ext & am) != 0))
         return fail(ctx, AMPLI_E_INVALID, (std::string(what) + ": recs must be 16-byte aligned (8-byte for the 24-byte layout)").c_str());
@@ -3307,6 +3308,160 @@ extern "C" int ampli_limit_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset)
     hipStream_t st = main_stream(ctx);
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_limit_stats, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
     if (reset) HIP_TRY(ctx, hipMemsetAsync(ctx->d_limit_stats, 0, 3 * sizeof(unsigned long long), st));
+    HIP_TRY(ctx, hipStreamSynchronize(st));
+    return AMPLI_OK;
+}
+
+// ==== detection power: the probability that the gate passes at given allele fractions, and the fraction at which it reaches a confidence =
+
+// limit_power_kernel<LAY>: one lane per cell (record, base), a workgroup = 4 waves over 64 records of one sample, so the
+// lanes of a wave hold 64 consecutive cells: the LoD store is one contiguous run of floats; a level's power store has a stride of
+// n_levels floats between neighbouring lanes and is issued where the lane finishes that level.  A lane whose cell is OK owes two
+// binomial tails per level and two per step of the root search, each a closed-form first term and a sum of a few to a few thousand
+// further ones (ampli_math.h).  A wave lasts as long as its longest lane, so the lane runs ONE loop whose body is one unit of that work
+// (ampli_power_advance: a tail's start if one is due, one run of AMPLI_TAIL_RUN terms, the change of strand when the run ends the tail)
+// and walks through its levels and its search inside it.  Lanes whose tails all fit one run stay in step, tail by tail; a lane with a
+// longer tail falls behind by a trip per further run, and from then on a trip of the wave pays the start of some lanes AND the run of
+// others.  Nothing is indexed at run time but global memory: no scratch.  Counters as limit_pairs_kernel: one ballot per counter and
+// wave, summed in LDS, one atomic per workgroup and non-zero counter; the work counters are summed in 64 bits from the wave on (a lane's
+// own stay below 2^32: at most 208 tails of at most 2^19 terms).
+constexpr int PWR_RECS = 64, PWR_THREADS = 4 * PWR_RECS;
+
+template <int LAY>
+__global__ __launch_bounds__(PWR_THREADS) void limit_power_kernel(
+    const RecView rv, const long long P, const long long E, const int2 *__restrict__ min_reads, const unsigned char *__restrict__ status,
+    const float *__restrict__ levels, const int n_levels, const double conf, float *__restrict__ power, float *__restrict__ lod,
+    unsigned long long *__restrict__ counts, unsigned long long *__restrict__ stats)
+{
+    constexpr int RB = rec_bytes(LAY);
+    __shared__ unsigned cnt[1 + AMPLI_POWER_MAX_LEVELS];
+    __shared__ unsigned long long ev[3]; // tails, terms, the most terms of one tail
+    const int tid = threadIdx.x;
+    if (tid < 1 + AMPLI_POWER_MAX_LEVELS) cnt[tid] = 0;
+    if (tid < 3) ev[tid] = 0;
+    __syncthreads();
+    const long long R = P + E;
+    const int rl = tid >> 2, nt = tid & 3;
+    const long long r = (long long)blockIdx.x * PWR_RECS + rl;
+    const int t = blockIdx.y;
+    const bool in_range = r < R; // lanes past the end keep company at the barrier
+    const size_t cell = ((size_t)t * (size_t)R + (size_t)(in_range ? r : 0)) * 4 + nt;
+    bool ok = false;
+    unsigned pass = 0; // bit l: power(levels[l]) >= conf
+    float lod_out = 0.0f;
+    unsigned n_tails = 0, n_terms = 0, max_terms = 0;
+    if (in_range) {
+        const unsigned st = status[cell];
+        int FW = 0, BW = 0;
+        int2 mr = make_int2(0, 0);
+        if ((st & (7u | AMPLI_LIMIT_RECHECK)) == AMPLI_LIMIT_OK) {
+            mr = min_reads[cell];
+            const char *q = r < P ? rv.base + ((size_t)t * (size_t)rv.row_stride + (size_t)r) * RB
+                                  : rv.ext + ((size_t)t * (size_t)rv.ext_stride + (size_t)(r - P)) * RB;
+            int4 r0, r1;
+            rec_decode<LAY>(rec_load_at<LAY>(q), r0, r1);
+            if (r0.x != AMPLI_ABSENT) {
+                FW = r0.x + r0.y + r0.z + r0.w; // VC:760
+                BW = r1.x + r1.y + r1.z + r1.w; // VC:761
+            }
+            ok = mr.x >= 1 && mr.y >= 1 && mr.x <= FW && mr.y <= BW;
+        }
+        if (ok) {
+            ampli_power_eval e;
+            ampli_lod_search s;
+            ampli_power_begin(&e, FW, mr.x, BW, mr.y);
+            int l = 0; // the level in hand; n_levels: the root search
+            bool go = true;
+            if (n_levels > 0) ampli_power_at(&e, (double)levels[0]);
+            else if (lod) ampli_power_at(&e, ampli_lod_begin(&s, FW, mr.x, BW, mr.y, conf));
+            else go = false;
+            while (go) {
+                if (!ampli_power_advance(&e)) continue;
+                if (l < n_levels) {
+                    if (power) power[cell * (size_t)n_levels + l] = (float)e.pw;
+                    pass |= (e.pw >= conf ? 1u : 0u) << l;
+                    ++l;
+                    if (l < n_levels) ampli_power_at(&e, (double)levels[l]);
+                    else if (lod) ampli_power_at(&e, ampli_lod_begin(&s, FW, mr.x, BW, mr.y, conf));
+                    else go = false;
+                } else {
+                    const double v = ampli_lod_update(&s, e.pw, e.dpw);
+                    if (s.done) { lod_out = (float)v; go = false; }
+                    else ampli_power_at(&e, v);
+                }
+            }
+            n_tails = e.n_tails; n_terms = e.n_terms; max_terms = e.max_terms;
+        } else if (power) {
+            for (int l = 0; l < n_levels; ++l) power[cell * (size_t)n_levels + l] = 0.0f;
+        }
+        if (lod) lod[cell] = lod_out;
+    }
+    const bool lane0 = (tid & 63) == 0;
+    auto tally = [&](const int slot, const bool pred) { // one LDS add per wave
+        const unsigned n = (unsigned)__popcll(__ballot(pred));
+        if (lane0 && n) atomicAdd(&cnt[slot], n);
+    };
+    tally(0, ok);
+    for (int l = 0; l < n_levels; ++l) tally(1 + l, (pass >> l) & 1u);
+    unsigned long long w_tails = n_tails, w_terms = n_terms, w_max = max_terms;
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) {
+        w_tails += __shfl_xor(w_tails, d);
+        w_terms += __shfl_xor(w_terms, d);
+        w_max = max(w_max, __shfl_xor(w_max, d));
+    }
+    if (lane0 && w_tails) { atomicAdd(&ev[0], w_tails); atomicAdd(&ev[1], w_terms); atomicMax(&ev[2], w_max); }
+    __syncthreads();
+    const int nc = 1 + n_levels;
+    if (tid < nc && cnt[tid]) atomicAdd(&counts[(size_t)t * nc + tid], (unsigned long long)cnt[tid]);
+    if (tid == 0 && ev[0]) { atomicAdd(&stats[0], ev[0]); atomicAdd(&stats[1], ev[1]); atomicMax(&stats[2], ev[2]); }
+}
+
+static int ensure_power_stats(ampli_ctx *ctx)
+{
+    if (ctx->d_power_stats) return AMPLI_OK;
+    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "the power counters would have to be allocated while capturing: run the sequence once first");
+    if (hipMalloc((void **)&ctx->d_power_stats, 3 * sizeof(unsigned long long)) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "power counters hipMalloc failed");
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_power_stats, 0, 3 * sizeof(unsigned long long), main_stream(ctx)));
+    return AMPLI_OK;
+}
+
+extern "C" int ampli_power_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, const int32_t *d_min_reads, const uint8_t *d_status,
+                                   const float *d_levels, int32_t n_levels, float confidence, float *d_power, float *d_lod, int64_t *d_counts)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!trecs || P <= 0 || !d_min_reads || !d_status || !d_counts || n_levels < 0 || n_levels > AMPLI_POWER_MAX_LEVELS || (n_levels > 0 && !d_levels) ||
+        !(confidence >= 0.5f && confidence <= 0.99f))
+        return fail(ctx, AMPLI_E_INVALID, "power_records: bad argument (records, P > 0, min_reads, status and counts are required; n_levels 0 .. 8, with "
+                                          "d_levels when it is not 0; confidence in [0.5, 0.99])");
+    DevCohort co;
+    { int rc = cohort_from_records(ctx, trecs, P, co); if (rc) return rc; }
+    { int rc = check_records(ctx, co, "power_records", nullptr, nullptr); if (rc) return rc; } // a cell needs its record only: no index of the extras
+    if (((uintptr_t)d_min_reads & 7) != 0 || ((uintptr_t)d_counts & 7) != 0)
+        return fail(ctx, AMPLI_E_INVALID, "power_records: min_reads and counts must be 8-byte aligned");
+    const long long E = co.E, R = P + E;
+    if (R >= (1ll << 30)) return fail(ctx, AMPLI_E_RANGE, "power_records: P + E must be below 2^30 records per sample");
+    if (co.n > 65535) return fail(ctx, AMPLI_E_RANGE, "power_records: more than 65535 samples in one call (grid limit); split the cohort");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rcs = ensure_power_stats(ctx); if (rcs) return rcs; }
+    const dim3 grid((unsigned)((R + PWR_RECS - 1) / PWR_RECS), (unsigned)co.n);
+    with_layout(co.layout, [&](auto L) {
+        hipLaunchKernelGGL((limit_power_kernel<L>), grid, dim3(PWR_THREADS), 0, main_stream(ctx), co.rv, (long long)P, E, (const int2 *)d_min_reads, d_status,
+                           d_levels, (int)n_levels, (double)confidence, d_power, d_lod, (unsigned long long *)d_counts, ctx->d_power_stats);
+    });
+    return check_launch(ctx, "limit_power_kernel");
+}
+
+extern "C" int ampli_power_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset)
+{
+    if (!ctx) return AMPLI_E_INVALID;
+    if (!out) return fail(ctx, AMPLI_E_INVALID, "power_stats: out is required");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    out[0] = out[1] = out[2] = 0;
+    if (!ctx->d_power_stats) return AMPLI_OK;
+    hipStream_t st = main_stream(ctx);
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_power_stats, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
+    if (reset) HIP_TRY(ctx, hipMemsetAsync(ctx->d_power_stats, 0, 3 * sizeof(unsigned long long), st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     return AMPLI_OK;
 }

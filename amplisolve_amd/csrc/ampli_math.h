@@ -441,4 +441,235 @@ AMPLI_FN int32_t ampli_limit_reads(int32_t depth, float thr, int32_t bound, cons
     return s.res;
 }
 
+// ---------------------------------------------------------------------------
+// Detection power: the probability that a variant at allele fraction v gives at least k alternative reads among the n
+// reads of a strand, tail(n, k, v) = P[Bin(n, v) >= k], in fp64 for n up to 2^31, and the allele fraction at which both strands
+// together reach a confidence c.
+//   * One term of the pmf is formed in closed form -- the saddle-point form, whose large parts cancel analytically:
+//       ln pmf(j) = 1/2 ln(n / (2 pi j (n - j))) + d(n) - d(j) - d(n - j) - D(j),   D(j) = n KL(j/n || v),
+//     d(x) = ln x! - ((x + 1/2) ln x - x + 1/2 ln 2 pi), the error of Stirling's formula.  (lgamma differences are useless here: at
+//     2^30 one lgamma carries an absolute error of 4e-6, whichever function computes it.)
+//   * D(j) is also Chernoff's exponent: P[X >= k] <= exp(-D(k)) for k >= n v and P[X <= k - 1] <= exp(-D(k - 1)) for k - 1 <= n v.
+//     Beyond AMPLI_TAIL_CUT = 20 the tail is within e^-20 = 2.1e-9 of 0 or of 1 and is returned as that: no sum.
+//   * Otherwise the pmf is summed AWAY from the mean with the term recurrence, from k upwards when k > n v, else from k - 1 downwards
+//     (the complement).  The ratio of consecutive terms is below one from the first step and falls from step to step, so what is left
+//     after a term t with next ratio r is below t r / (1 - r): the sum ends once that is below AMPLI_TAIL_EPS.  That happens within
+//     about 6.7 standard deviations of the mean; with the cut above no sum starts farther than 6.4 from it on the other side, but sums
+//     never cross the mean, so a tail costs at most AMPLI_TAIL_TERMS(n v (1 - v)) terms (asserted in tests/test_power_host.py).
+// One ampli_tail_step is a short run of terms, so that a kernel can run the tails of a lane in a single loop (as ampli_limit_step).
+// ---------------------------------------------------------------------------
+#define AMPLI_TAIL_CUT 20.0
+#define AMPLI_TAIL_EPS 1e-11
+#define AMPLI_TAIL_RUN 8                 // terms per ampli_tail_step
+#define AMPLI_TAIL_MAX_TERMS (1 << 19)   // never reached for n < 2^31 (8 sqrt(2^31 / 4) + 64 = 185 000): the loop's own bound
+#define AMPLI_TAIL_TERMS(var) (8.0 * sqrt(var) + 64.0)
+
+// d(x) for an integer x >= 1: the asymptotic series from 16 on (next term 1 / (1188 x^9) < 2e-14), below it from x! itself
+AMPLI_FN double ampli_stirling_err(double x)
+{
+    if (x >= 16.0) {
+        const double r = 1.0 / (x * x);
+        return (1.0 / 12 - (1.0 / 360 - (1.0 / 1260 - 1.0 / 1680 * r) * r) * r) / x;
+    }
+    double f = 1.0;
+    for (double i = 2.0; i <= x; i += 1.0) f *= i; // 15! < 2^53: exact
+    return log(f) - ((x + 0.5) * log(x) - x + 0.918938533204672742);
+}
+
+// x ln(x / m) + m - x >= 0 for x >= 0, m > 0: m ((1 + t) log1p(t) - t) with t = (x - m) / m; the rounding error is ~1e-16 |x - m|
+AMPLI_FN double ampli_bd0(double x, double m)
+{
+    if (x <= 0.0) return m;
+    const double t = (x - m) / m;
+    return m * ((1.0 + t) * log1p(t) - t);
+}
+
+// ln pmf(j) of Bin(n, v) for 0 <= j <= n, 0 < v < 1; *dev = D(j)
+AMPLI_FN double ampli_binom_logpmf(double n, double j, double v, double *dev)
+{
+    if (j <= 0.0) { const double d = -n * log1p(-v); *dev = d; return -d; }
+    if (j >= n) { const double d = -n * log(v); *dev = d; return -d; }
+    const double D = ampli_bd0(j, n * v) + ampli_bd0(n - j, n * (1.0 - v));
+    *dev = D;
+    return 0.5 * log(n / (6.283185307179586477 * j * (n - j))) + ampli_stirling_err(n) - ampli_stirling_err(j) - ampli_stirling_err(n - j) - D;
+}
+
+typedef struct {
+    double n, j;     // reads; index of the latest term
+    double t, sum;   // the latest term; the terms so far
+    double odds;     // v / (1 - v) going up, its inverse going down
+    double pmf_k;    // pmf(k): d tail / d ln v = k pmf(k)
+    double res;      // the tail, once live == 0
+    int32_t up;      // the sum is the tail (from k upwards) / its complement (from k - 1 downwards)
+    int32_t terms;   // pmf terms formed, the first one included
+    int32_t live;
+} ampli_tail_sum;
+
+AMPLI_FN void ampli_tail_init(ampli_tail_sum *s, int32_t n_reads, int32_t k, double v)
+{
+    s->terms = 0; s->live = 0; s->pmf_k = 0; s->up = 1; s->n = (double)n_reads; s->j = 0; s->t = 0; s->sum = 0; s->odds = 0;
+    if (k > n_reads || !(v > 0.0)) { s->res = 0.0; return; }
+    if (k <= 0 || v >= 1.0) { s->res = 1.0; return; }
+    const double n = (double)n_reads, kk = (double)k, o = v / (1.0 - v);
+    double D;
+    s->terms = 1;
+    if (kk > n * v) {
+        const double p = exp(ampli_binom_logpmf(n, kk, v, &D));
+        s->pmf_k = p;
+        if (D > AMPLI_TAIL_CUT) { s->res = 0.0; return; }
+        s->j = kk; s->t = s->sum = p; s->odds = o; s->up = 1;
+    } else {
+        const double p = exp(ampli_binom_logpmf(n, kk - 1.0, v, &D));
+        s->pmf_k = p * ((n - kk + 1.0) / kk) * o;
+        if (D > AMPLI_TAIL_CUT) { s->res = 1.0; return; }
+        s->j = kk - 1.0; s->t = s->sum = p; s->odds = 1.0 / o; s->up = 0;
+    }
+    s->live = 1;
+}
+
+AMPLI_FN void ampli_tail_step(ampli_tail_sum *s)
+{
+    double j = s->j, t = s->t, sum = s->sum;
+    const double n = s->n, o = s->odds;
+    int live = 1, terms = s->terms;
+    for (int i = 0; i < AMPLI_TAIL_RUN; ++i) {
+        // the ratio to the next term away from the mean; 0 at the end of the support
+        const double r = s->up ? (n - j) / (j + 1.0) * o : j / (n - j + 1.0) * o;
+        if (!(t * r >= AMPLI_TAIL_EPS * (1.0 - r)) || terms >= AMPLI_TAIL_MAX_TERMS) { live = 0; break; }
+        t *= r;
+        sum += t;
+        j += s->up ? 1.0 : -1.0;
+        ++terms;
+    }
+    s->j = j; s->t = t; s->sum = sum; s->terms = terms; s->live = live;
+    if (!live) s->res = s->up ? (sum < 1.0 ? sum : 1.0) : (sum < 1.0 ? 1.0 - sum : 0.0);
+}
+
+// tail(n, k, v); *terms (optional) = pmf terms formed, *pmf_k (optional) = pmf(k)
+AMPLI_FN double ampli_binom_tail(int32_t n, int32_t k, double v, int32_t *terms, double *pmf_k)
+{
+    ampli_tail_sum s;
+    ampli_tail_init(&s, n, k, v);
+    while (s.live) ampli_tail_step(&s);
+    if (terms) *terms = s.terms;
+    if (pmf_k) *pmf_k = s.pmf_k;
+    return s.res;
+}
+
+// power(v) = tail(FW, k_fw, v) tail(BW, k_bw, v) and its derivative in ln v, one unit of work per ampli_power_advance: a tail's start
+// (if it is due), one run of its terms and, when that run ends the tail, the change of strand.  A tail of up to AMPLI_TAIL_RUN + 1 terms
+// is therefore ONE unit; a longer one takes one more unit per further run.  Returns 1 when pw / dpw are those of v.
+typedef struct {
+    ampli_tail_sum ts;
+    double v, tail_fw, d_fw; // d_fw = k_fw pmf(k_fw)
+    double pw, dpw;
+    int32_t FW, BW, k_fw, k_bw;
+    int32_t strand, start;
+    uint32_t n_tails, n_terms, max_terms; // of every tail since ampli_power_begin
+} ampli_power_eval;
+
+AMPLI_FN void ampli_power_begin(ampli_power_eval *e, int32_t FW, int32_t k_fw, int32_t BW, int32_t k_bw)
+{
+    e->FW = FW; e->BW = BW; e->k_fw = k_fw; e->k_bw = k_bw;
+    e->v = 0; e->tail_fw = 0; e->d_fw = 0; e->pw = 0; e->dpw = 0; e->strand = 0; e->start = 0;
+    e->n_tails = e->n_terms = e->max_terms = 0;
+    e->ts.live = 0;
+}
+
+AMPLI_FN void ampli_power_at(ampli_power_eval *e, double v)
+{
+    e->v = v; e->strand = 0; e->start = 1;
+}
+
+AMPLI_FN int ampli_power_advance(ampli_power_eval *e)
+{
+    if (e->start) {
+        ampli_tail_init(&e->ts, e->strand ? e->BW : e->FW, e->strand ? e->k_bw : e->k_fw, e->v);
+        e->start = 0;
+    }
+    if (e->ts.live) {
+        ampli_tail_step(&e->ts);
+        if (e->ts.live) return 0;
+    }
+    ++e->n_tails;
+    e->n_terms += (uint32_t)e->ts.terms;
+    if ((uint32_t)e->ts.terms > e->max_terms) e->max_terms = (uint32_t)e->ts.terms;
+    if (e->strand == 0) {
+        e->tail_fw = e->ts.res; e->d_fw = (double)e->k_fw * e->ts.pmf_k;
+        e->strand = 1; e->start = 1;
+        return 0;
+    }
+    e->pw = e->tail_fw * e->ts.res;
+    e->dpw = e->d_fw * e->ts.res + e->tail_fw * ((double)e->k_bw * e->ts.pmf_k);
+    return 1;
+}
+
+// LoD(c): the root of power(v) = c in x = ln v by Newton's step, kept inside a bracket [lo, hi] with power(e^lo) < c <= power(e^hi)
+// and replaced by a bisection when it leaves the bracket or does not halve the step (rtsafe).  The bracket starts at [ln 1e-12, 0]:
+// power(1) = 1, and power(1e-12) <= P[X >= 1] <= 2^31 1e-12 < 0.5.  The search ends once |power - c| <= AMPLI_LOD_FTOL -- with d power /
+// d ln v >= 0.046 at the root for c <= 0.99 that is 2.2e-7 of ln v -- or once the bracket is narrower than AMPLI_LOD_XTOL, and after
+// AMPLI_LOD_MAX_ITERS evaluations at the latest (35 bisections close the bracket; a Newton step in between at most doubles that).
+#define AMPLI_LOD_FTOL 1e-8
+#define AMPLI_LOD_XTOL 1e-9
+#define AMPLI_LOD_MAX_ITERS 96
+
+typedef struct {
+    double lo, hi, x, dx, dx_old, c;
+    int32_t iters, done;
+} ampli_lod_search;
+
+// returns the first allele fraction to evaluate: where the more demanding strand expects its minimum reads and a standard deviation more
+AMPLI_FN double ampli_lod_begin(ampli_lod_search *s, int32_t FW, int32_t k_fw, int32_t BW, int32_t k_bw, double c)
+{
+    s->lo = -27.631021115928547; s->hi = 0.0; s->c = c; s->iters = 0; s->done = 0;
+    const double a = ((double)k_fw + sqrt((double)k_fw)) / (double)FW, b = ((double)k_bw + sqrt((double)k_bw)) / (double)BW;
+    double v = a > b ? a : b;
+    if (!(v < 0.99)) v = 0.99;
+    s->x = log(v);
+    s->dx = s->dx_old = s->hi - s->lo;
+    return v;
+}
+
+// power and its derivative at e^x are in: returns the next allele fraction, or sets done (the LoD is then e^x)
+AMPLI_FN double ampli_lod_update(ampli_lod_search *s, double pw, double dpw)
+{
+    const double f = pw - s->c;
+    ++s->iters;
+    if (f < 0.0) s->lo = s->x; else s->hi = s->x;
+    if (fabs(f) <= AMPLI_LOD_FTOL || s->iters >= AMPLI_LOD_MAX_ITERS) { s->done = 1; return exp(s->x); }
+    if (s->hi - s->lo <= AMPLI_LOD_XTOL) { s->done = 1; s->x = 0.5 * (s->lo + s->hi); return exp(s->x); }
+    double xn = s->x - f / dpw;
+    if (!(dpw > 0.0) || !(xn > s->lo && xn < s->hi) || fabs(2.0 * f) > fabs(s->dx_old * dpw)) xn = 0.5 * (s->lo + s->hi);
+    s->dx_old = s->dx;
+    s->dx = xn - s->x;
+    s->x = xn;
+    return exp(xn);
+}
+
+// the whole of one pair (host, tests): power[l] at levels[l], *lod = LoD(c) when lod is not NULL; stats[3] (optional) += tails, terms, max
+AMPLI_FN void ampli_power_lod(int32_t FW, int32_t k_fw, int32_t BW, int32_t k_bw, const float *levels, int32_t n_levels, double c,
+                              double *power, double *lod, int32_t *iters, uint64_t *stats)
+{
+    ampli_power_eval e;
+    ampli_power_begin(&e, FW, k_fw, BW, k_bw);
+    for (int l = 0; l < n_levels; ++l) {
+        ampli_power_at(&e, (double)levels[l]);
+        while (!ampli_power_advance(&e)) {}
+        power[l] = e.pw;
+    }
+    if (iters) *iters = 0;
+    if (lod) {
+        ampli_lod_search s;
+        double v = ampli_lod_begin(&s, FW, k_fw, BW, k_bw, c);
+        while (!s.done) {
+            ampli_power_at(&e, v);
+            while (!ampli_power_advance(&e)) {}
+            v = ampli_lod_update(&s, e.pw, e.dpw);
+        }
+        *lod = v;
+        if (iters) *iters = s.iters;
+    }
+    if (stats) { stats[0] += e.n_tails; stats[1] += e.n_terms; if (e.max_terms > stats[2]) stats[2] = e.max_terms; }
+}
+
 #endif

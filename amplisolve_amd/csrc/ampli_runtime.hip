@@ -89,6 +89,7 @@ extern "C" void ampli_ctx_destroy(ampli_ctx *ctx)
     if (ctx->ev_fork) (void)hipEventDestroy(ctx->ev_fork);
     if (ctx->d_lgtab) (void)hipFree(ctx->d_lgtab);
     if (ctx->d_limit_stats) (void)hipFree(ctx->d_limit_stats);
+    if (ctx->d_power_stats) (void)hipFree(ctx->d_power_stats);
     if (ctx->side) { (void)hipStreamSynchronize(ctx->side); (void)hipStreamDestroy(ctx->side); }
     if (ctx->ev_stream_done) (void)hipEventDestroy(ctx->ev_stream_done);
     if (ctx->ev_drain_done) (void)hipEventDestroy(ctx->ev_drain_done);

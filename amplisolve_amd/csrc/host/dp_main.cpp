@@ -1,0 +1,40 @@
+// AmpliSolveDetectionPower -- detection power at given allele fractions and the limit of detection per (line, base) pair,
+// in the reference's key=value style.
+//   AmpliSolveDetectionPower errorFile=<table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<int> levels=<f>[,<f>...] confidence=<f>
+// Exactly 6 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
+#include <clocale>
+#include <cstdio>
+#include <cstdlib>
+#include <iostream>
+
+#include "host.hpp"
+
+static std::string token(const char *arg, const char *key)
+{
+    char buf[4096];
+    buf[0] = 0;
+    std::string fmt = std::string(key) + "=%4000s";
+    sscanf(arg, fmt.c_str(), buf);
+    return buf;
+}
+
+int main(int argc, char **argv)
+{
+    setlocale(LC_ALL, "");
+    if (argc != 7) {
+        std::cout << "Usage:\n\tAmpliSolveDetectionPower errorFile=<error table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<int> "
+                     "levels=<float>[,<float>...] confidence=<0.5 .. 0.99>\n\tAll arguments are required, in this order." << std::endl;
+        return 1;
+    }
+    ampli::DpArgs a;
+    a.error_file = token(argv[1], "errorFile");
+    a.tumour_dir = token(argv[2], "tumour_dir");
+    a.output_dir = token(argv[3], "output_dir");
+    a.coverage_cutoff = token(argv[4], "coverage_cutoff");
+    a.levels = token(argv[5], "levels");
+    a.confidence = token(argv[6], "confidence");
+    const int rc = ampli::run_detection_power(a);
+    std::cout.flush();
+    ampli::finish_process(rc ? 1 : 0);
+    return rc ? 1 : 0;
+}

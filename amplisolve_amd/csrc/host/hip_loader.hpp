@@ -60,6 +60,9 @@ struct HipApi {
     int (*mem_info)(ampli_ctx *, size_t *, size_t *);
     int (*limit_records)(ampli_ctx *, const ampli_records *, int64_t, const float *, const uint8_t *, int32_t, const float *, int32_t, int32_t *,
                          uint8_t *, int64_t *);
+    int (*power_records)(ampli_ctx *, const ampli_records *, int64_t, const int32_t *, const uint8_t *, const float *, int32_t, float, float *, float *,
+                         int64_t *);
+    int (*power_stats)(ampli_ctx *, uint64_t *, int32_t);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

@@ -215,7 +215,7 @@ void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // without the static destructors and atexit handlers of the HIP runtime (queue / signal / pool teardown that only serves a
 // process that lives on; the driver reclaims everything at exit either way).  AMPLISOLVE_EXIT=orderly returns instead.
 void finish_process(int status);
-// ---- run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp ----
+// ---- run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp ----
 int run_error_estimation(const EeArgs &a);
 int run_variant_calling(const VcArgs &a);
 // AmpliSolveLeaveOneOut (loo_main.cpp): C_value is one value or a comma-separated list; exit status 0 / 1
@@ -229,6 +229,11 @@ struct DlArgs {
     std::string error_file, tumour_dir, output_dir, coverage_cutoff = "100", levels;
 };
 int run_detection_limits(const DlArgs &a);
+// AmpliSolveDetectionPower (dp_main.cpp): levels as above, confidence a probability in [0.5, 0.99]; exit status 0 / 1
+struct DpArgs {
+    std::string error_file, tumour_dir, output_dir, coverage_cutoff = "100", levels, confidence = "0.95";
+};
+int run_detection_power(const DpArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

@@ -267,6 +267,20 @@ extern "C" int32_t ampli_host_limit_search(int32_t depth, float thr, int32_t bou
     return ampli_limit_reads(depth, thr, bound, nullptr, 0, evals);
 }
 
+extern "C" double ampli_host_binom_tail(int32_t n, int32_t k, double v, int32_t *terms) { return ampli_binom_tail(n, k, v, terms, nullptr); }
+
+extern "C" int ampli_host_power_pair(int32_t FW, int32_t min_fw, int32_t BW, int32_t min_bw, const float *levels, int32_t n_levels, float confidence,
+                                     double *power, double *lod, int32_t *iters)
+{
+    if (n_levels < 0 || n_levels > AMPLI_POWER_MAX_LEVELS || (n_levels > 0 && (!levels || !power)) || !(confidence >= 0.5f && confidence <= 0.99f) ||
+        min_fw < 1 || min_bw < 1 || min_fw > FW || min_bw > BW) {
+        g_err = "power_pair: bad argument (1 <= min reads <= the strand's reads, 0 .. 8 levels, confidence in [0.5, 0.99])";
+        return AMPLI_E_INVALID;
+    }
+    ampli_power_lod(FW, min_fw, BW, min_bw, levels, n_levels, (double)confidence, power, lod, iters, nullptr);
+    return 0;
+}
+
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)
 {
     try {

@@ -478,6 +478,30 @@ int ampli_limit_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, c
  * included), out[2] the most evaluations of one strand; reset != 0 clears them.  Synchronises the stream. */
 int ampli_limit_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset);
 
+/*
+ * power_records -- detection power and limit of detection of the calling gate.  For every cell (sample, record, base) of
+ * the chunk `trecs` whose status is AMPLI_LIMIT_OK (AMPLI_LIMIT_RECHECK clear; AMPLI_LIMIT_CALLED is ignored) with minimum reads
+ * 1 <= min_fw <= FW and 1 <= min_bw <= BW (FW, BW: the sums of the record's four forward / reverse counts):
+ *   power(v) = P[Bin(FW, v) >= min_fw] * P[Bin(BW, v) >= min_bw]   -- a variant at allele fraction v turns each read of a strand into an
+ *              alternative read independently, the depths stay as they are, background alternative reads are ignored (a lower bound)
+ *   LoD      = the v in (0, 1] with power(v) = confidence
+ * Every other cell gets power 0 and LoD 0 and is counted nowhere.  Asynchronous on the context's stream.
+ *   d_min_reads int32 [n][P + E][4][2], d_status uint8 [n][P + E][4]: as ampli_limit_records writes them, RECHECK cells settled by the host
+ *   d_levels    float [n_levels] allele fractions, 0 <= n_levels <= AMPLI_POWER_MAX_LEVELS (may be NULL when n_levels == 0)
+ *   confidence  in [0.5, 0.99] (the stopping rule of the root search is sized for this range)
+ *   d_power     float [n][P + E][4][n_levels], may be NULL;  d_lod float [n][P + E][4], may be NULL (then no root is searched)
+ *   d_counts    int64 [n][1 + n_levels], 8-byte aligned, ADDED to: OK pairs | per level: OK pairs with power(level) >= confidence, compared
+ *               in double before the power is rounded to float
+ * The values are fp64 sums formed with the device's exp / log: within 1e-6 of the definition (tests/power_model.py), the LoD within
+ * 1e-4 relative; not bit-identical between libm versions or with ampli_host_power_pair.
+ */
+#define AMPLI_POWER_MAX_LEVELS 8
+int ampli_power_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, const int32_t *d_min_reads, const uint8_t *d_status,
+                        const float *d_levels, int32_t n_levels, float confidence, float *d_power, float *d_lod, int64_t *d_counts);
+/* work of the context's power_records launches so far: out[0] tails evaluated, out[1] pmf terms summed, out[2] the most terms of one
+ * tail; reset != 0 clears them.  Synchronises the stream. */
+int ampli_power_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset);
+
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);
 

@@ -172,6 +172,15 @@ int32_t ampli_host_limit_reads(int32_t depth, float thr, int32_t bound);
  * where that arithmetic does not decide (the kernel's RECHECK); *evals (optional) = scorer evaluations spent */
 int32_t ampli_host_limit_search(int32_t depth, float thr, int32_t bound, int32_t *evals);
 
+/* Detection power, the code of csrc/ampli_math.h that limit_power_kernel runs, compiled for the host.
+ * ampli_host_binom_tail: P[Bin(n, v) >= k] in fp64; *terms (optional) = pmf terms formed (0: decided without a sum).
+ * ampli_host_power_pair: one OK pair -- power[l] = tail(FW, min_fw, levels[l]) * tail(BW, min_bw, levels[l]) and, when lod is not NULL,
+ * *lod = the allele fraction at which the power is `confidence` (*iters, optional: evaluations of the root search).  Returns 0, or
+ * AMPLI_E_INVALID unless 1 <= min reads <= the strand's reads, n_levels in 0 .. 8 and confidence in [0.5, 0.99]. */
+double ampli_host_binom_tail(int32_t n, int32_t k, double v, int32_t *terms);
+int ampli_host_power_pair(int32_t FW, int32_t min_fw, int32_t BW, int32_t min_bw, const float *levels, int32_t n_levels, float confidence,
+                          double *power, double *lod, int32_t *iters);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
