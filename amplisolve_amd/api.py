@@ -379,11 +379,12 @@ class Context:
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,
-                 n_calls=None, callable_pos=None, callable_sample=None, flags=None):
+                 n_calls=None, callable_pos=None, callable_sample=None, flags=None, thr_loo=None):
         """Leave-one-out calls of one resident chunk of the panel of normals (ampli_loo_call_records): every normal of the chunk
         through the calling gate (calling cutoff call_cov) against the error table (C_value, cov) of the cohort without it.  acc holds
         the WHOLE cohort's sums.  callable_pos [P] / callable_sample [n] are added to (zeroed here when not given); flags[0] gets bit 0
-        when a total is outside the exactness envelope.  dense_thr: also the S-1 thresholds, float32 [n, 2, 4, P]."""
+        when a total is outside the exactness envelope.  dense_thr: also the S-1 thresholds, float32 [n, 2, 4, P] (into thr_loo when
+        the caller brings the buffer)."""
         import torch
 
         n, R = rec.n_samples, P + rec.E
@@ -402,7 +403,8 @@ class Context:
             callable_sample = torch.zeros((n,), dtype=torch.int32, device=d)
         if flags is None:
             flags = torch.zeros((1,), dtype=torch.int32, device=d)
-        thr_loo = torch.empty((n, 2, 4, P), dtype=torch.float32, device=d) if dense_thr else None
+        if thr_loo is None and dense_thr:
+            thr_loo = torch.empty((n, 2, 4, P), dtype=torch.float32, device=d)
         self._check(self.lib.ampli_loo_call_records(self.h, C.byref(rec), P, C.byref(acc.struct), C_value, cov, call_cov, _ptr(ref_code), mode,
                                                     _ptr(call_mask), _ptr(calls_buf), capacity, _ptr(n_calls), _ptr(callable_pos),
                                                     _ptr(callable_sample), _ptr(thr_loo), _ptr(flags)))
@@ -531,9 +533,10 @@ class Context:
 
     def poisson_call(self, trecs, P: int, thr, ref_code, cov: int = 100, mode: int = POISSON_PREFILTER, E: int = 0,
                      ext_pos=None, call_mask=None, capacity: int = 0, dense_q: bool = False, dense_af: bool = False,
-                     calls_buf=None, n_calls=None, blocks_of: int = 0):
+                     calls_buf=None, n_calls=None, blocks_of: int = 0, q=None, af=None):
         """thr: float32 [2, 4, P] thresholds -- or, with blocks_of = n > 0, the all-gathered blocks of an n-slice
-        position-sliced merge (ampli_poisson_call_blocks: thresholds are read straight from the blocks)."""
+        position-sliced merge (ampli_poisson_call_blocks: thresholds are read straight from the blocks).  q / af: the caller's own
+        buffers for the dense scores (float64 [T, R, 4, 2]) and VAFs (float32 [T, R, 4, 3]) instead of dense_q / dense_af."""
         import torch
 
         assert trecs.dtype == self._rec_dtype() and trecs.is_cuda and trecs.is_contiguous()
@@ -543,8 +546,10 @@ class Context:
         d = self.device
         if call_mask is None:
             call_mask = torch.empty(((T * R + 3) // 4 * 4,), dtype=torch.uint8, device=d)[: T * R].view(T, R)
-        q = torch.empty((T, R, 4, 2), dtype=torch.float64, device=d) if dense_q else None
-        af = torch.empty((T, R, 4, 3), dtype=torch.float32, device=d) if dense_af else None
+        if q is None and dense_q:
+            q = torch.empty((T, R, 4, 2), dtype=torch.float64, device=d)
+        if af is None and dense_af:
+            af = torch.empty((T, R, 4, 3), dtype=torch.float32, device=d)
         if capacity > 0 and calls_buf is None:
             calls_buf = torch.empty((capacity * C.sizeof(Call),), dtype=torch.uint8, device=d)
         if capacity > 0:

@@ -2663,6 +2663,12 @@ static int ensure_lgtab(ampli_ctx *ctx)
     return check_launch(ctx, "lgamma_table_kernel");
 }
 
+// the shard counters of one half of the queue's double buffer back to zero (captured passes only, below)
+__global__ void queue_counters_reset_kernel(unsigned long long *__restrict__ qn)
+{
+    qn[threadIdx.x * AMPLI_CALL_COUNTER_STRIDE] = 0ull;
+}
+
 // The prefilter queue of a launch on `st`: at least `want` items (rounded up to whole shards), and the half of the double-buffered shard
 // counters this launch appends to (qn; the stream kernel finds it zeroed) and the half its drain resets for the next launch (qn_next)
 static int queue_prepare(ampli_ctx *ctx, AmpliQueue &Q, size_t want, hipStream_t st, long long &per, unsigned long long *&qn,
@@ -2687,8 +2693,13 @@ static int queue_prepare(ampli_ctx *ctx, AmpliQueue &Q, size_t want, hipStream_t
     per = (long long)(Q.n_items / AMPLI_CALL_SHARDS);
     qn = Q.n + (size_t)(Q.parity & 1) * AMPLI_CALL_COUNTER_WORDS;
     qn_next = Q.n + (size_t)((Q.parity + 1) & 1) * AMPLI_CALL_COUNTER_WORDS;
-    if (capturing) // a replayed graph cannot alternate halves: reset the half it uses with a memset node instead
-        HIP_TRY(ctx, hipMemsetAsync(qn, 0, sizeof(unsigned long long) * AMPLI_CALL_COUNTER_WORDS, st));
+    if (capturing) { // a replayed graph cannot alternate halves: reset the half it uses with a node of its own instead.  A KERNEL node: behind a
+        // memset node the stream kernel of a replay found counters that were not zero -- AMPLI_FLAG_QUEUE_OVERFLOW from the second or third
+        // replay on with a handful of items queued, and once a call listed twice (tests/test_gpu_output_contracts.py, the hipGraph case)
+        hipLaunchKernelGGL(queue_counters_reset_kernel, dim3(1), dim3(AMPLI_CALL_SHARDS), 0, st, qn);
+        int rcz = check_launch(ctx, "queue_counters_reset_kernel");
+        if (rcz) return rcz;
+    }
     else
         Q.parity ^= 1;
     return AMPLI_OK;

@@ -69,6 +69,36 @@ extern "C" {
                                    * RCCL on this device: the process MUST end now -- print, flush, _exit(1); do not destroy the
                                    * context, do not run static destructors, never re-exec */
 
+/*
+ * Output contracts.  What a call does to the caller's output buffers, whatever they held before -- none of them needs to be
+ * zeroed unless a line below says "added to" or "OR-ed into" (tests/test_gpu_output_contracts.py hands every entry point
+ * poisoned, fenced buffers and checks each line).  No call writes a byte outside the extents given here.
+ *   (C1) call mask (ampli_poisson_call / _records / _blocks, ampli_loo_call_records): CLEARED AND FULLY OVERWRITTEN by the call,
+ *        all [n_samples][P + E] bytes, in every mode, with and without position ranges, captured or not.
+ *   (C2) the mask's pad bytes: the buffer is rounded up to a multiple of 4 bytes; the up to 3 bytes behind the last record may be
+ *        zeroed by the call and mean nothing.  Nothing behind them is touched.
+ *   (C3) dense outputs -- d_q, d_af, d_thr_loo; d_rate, d_code, d_thr, d_germ_val, d_germ_present of every ampli_error_* entry
+ *        point that takes them; d_min_reads and d_status of ampli_limit_records; d_power and d_lod of ampli_power_records;
+ *        d_recs16 / d_recs24 of ampli_records_pack16 / 24: FULLY OVERWRITTEN, every element (d_germ_val holds a value of no
+ *        meaning where d_germ_present is 0; d_q holds -1 where a score was not evaluated).
+ *   (C4) ADDED TO (zero them for a count of one call): d_callable_pos, d_callable_sample of ampli_loo_call_records; d_counts of
+ *        ampli_limit_records and of ampli_power_records.
+ *   (C5) OR-ED INTO (zero them first): every flag word -- d_flags of the ampli_error_* entry points and of ampli_loo_call_records,
+ *        d_overflow of ampli_records_pack16 / 24, the flag word in the 64-byte tail of a slice block.  A call never clears a bit.
+ *   (C6) the sliced exchange buffers d_sums / d_gm (ampli_error_reduce_sliced, ampli_error_reduce_records_sliced,
+ *        ampli_acc_to_slices) and the slice block of ampli_error_finalize_slice: every entry of a position < P of the addressed
+ *        batch is overwritten; entries of positions >= P (the tail of the last slice that holds positions, whole slices behind
+ *        it), the other batches of a group and the 60 bytes behind a block's flag word are NEVER WRITTEN and never read.
+ *   (C7) accumulator table: the eight planes are overwritten (accumulate == 0) or folded into (accumulate != 0) over their
+ *        [..][P] extents; the PADDING between the planes and behind the last one, up to ampli_acc_bytes(P), is NEVER WRITTEN.
+ *        gm_first, gm_first_af and gm_rest hold values of no meaning where gm_n says that no (no second) record qualified.
+ *   (C8) call list: segment k is written from its start; an entry is written only at an index below both the segment's count and
+ *        capacity / AMPLI_CALL_SHARDS.  Entries beyond the count are UNTOUCHED, and no segment is written past its end however
+ *        far its counter runs beyond it.
+ *   (C9) d_n_calls: the AMPLI_CALL_SHARDS counters (words k * AMPLI_CALL_COUNTER_STRIDE) are RESET BY THE CALL ITSELF, whatever
+ *        they held -- with position ranges each range resets the shards dealt to it; the words between the counters mean nothing
+ *        and may be zeroed.
+ */
 typedef struct ampli_ctx ampli_ctx;
 
 int ampli_abi_version(void);

@@ -112,6 +112,43 @@ def toy_data(dst):
     return str(dst)
 
 
+FENCE_GUARD = 4096  # bytes of guard on either side of a fenced payload
+FENCE_ALIGN = 256   # the payload starts where a device allocation would
+
+
+def fenced(shape, dtype, poison=0xFF, device="cuda"):
+    """An output buffer whose prior content exposes a missed or a stray store: ONE uint8 tensor, guard | payload | guard (4096 bytes
+    each side, the payload 256-byte aligned and rounded up to 16 bytes), every byte of it `poison`.  Returns the typed payload view
+    and check(): both guards (every byte of the tensor outside the payload) still hold the poison, and so does the payload's own
+    tail behind the view -- all of it, or all but the first `pad` bytes (check(pad=k): the k bytes a contract lets a call write
+    there, such as the call mask's rounding to 4 bytes).  check.raw is the whole tensor, check.repoison() fills it again.
+    0xFF is NaN as f32 / f64, -1 as int32, 255 as uint8, and a call-mask byte with four impossible bits.  Outputs only: never
+    poison what a kernel reads as an index, a count or a bound."""
+    import torch
+
+    shape = tuple(int(x) for x in (shape if isinstance(shape, (tuple, list)) else (shape,)))
+    n = 1
+    for d in shape:
+        n *= d
+    nbytes = n * torch.empty(0, dtype=dtype).element_size()
+    payload = (nbytes + 15) // 16 * 16
+    raw = torch.empty(FENCE_GUARD + FENCE_ALIGN + payload + FENCE_GUARD, dtype=torch.uint8, device=device)
+    raw.fill_(poison)
+    off = FENCE_GUARD + (-(raw.data_ptr() + FENCE_GUARD)) % FENCE_ALIGN
+    view = raw[off: off + nbytes].view(dtype).view(*shape)
+    assert view.data_ptr() % FENCE_ALIGN == 0 and off >= FENCE_GUARD and raw.numel() - (off + payload) >= FENCE_GUARD
+
+    def check(pad=0):
+        lo, hi = raw[:off], raw[off + nbytes + pad:]
+        bad_lo, bad_hi = int((lo != poison).sum()), int((hi != poison).sum())
+        assert bad_lo == 0, f"{bad_lo} byte(s) written in front of the payload, the nearest {off - int((lo != poison).nonzero().max())} byte(s) before it"
+        assert bad_hi == 0, f"{bad_hi} byte(s) written behind the payload, the nearest {int((hi != poison).nonzero().min()) + pad} byte(s) past its end"
+
+    check.raw = raw
+    check.repoison = lambda: raw.fill_(poison)
+    return view, check
+
+
 def synth_recs(P, n, first=0, seed=SEED, depth=2000, tumour=False):
     out = np.empty((n, P, 8), np.int32)
     rc = host_lib().ampli_host_synth_fill(out.ctypes.data_as(C.c_void_p), P, n, first, seed, depth, int(tumour))
