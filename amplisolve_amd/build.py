@@ -13,6 +13,7 @@ import os
 import shutil
 import subprocess
 import sys
+from concurrent.futures import ThreadPoolExecutor
 
 PKG = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG)
@@ -23,9 +24,14 @@ BIN = os.path.join(PKG, "bin")
 HIP_LIB = os.path.join(LIB, "libamplisolve_hip.so")
 HOST_LIB = os.path.join(LIB, "libamplisolve_host.so")
 
-# ampli_kernels.hip: the path's kernels + their C ABI; ampli_runtime.hip: context, streams, memory and settings;
-# ampli_pileup.hip: the upstream counting kernel; ampli_comm.hip: RCCL binding
-HIP_SOURCES = ["ampli_kernels.hip", "ampli_runtime.hip", "ampli_pileup.hip", "ampli_comm.hip"]
+# The kernels + their C ABI, one translation unit per stage (the map: csrc/ampli_kernels.hip): ampli_kernels.hip the timed step (records,
+# error reduce, finalize, Poisson), ampli_exchange.hip the multi-GPU merges and slices, ampli_loo.hip leave-one-out, ampli_limits.hip
+# detection limits and power, ampli_aux.hip scorer checks and synthetic panels.  ampli_runtime.hip: context, streams, memory and
+# settings; ampli_pileup.hip: the upstream counting kernel; ampli_comm.hip: RCCL binding
+HIP_SOURCES = ["ampli_kernels.hip", "ampli_exchange.hip", "ampli_loo.hip", "ampli_limits.hip", "ampli_aux.hip", "ampli_runtime.hip",
+               "ampli_pileup.hip", "ampli_comm.hip"]
+HIP_HEADERS = ["ampli_device.h", "ampli_internal.h", "ampli_math.h", "ampli_synth.h"]
+OBJ = os.path.join(PKG, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off"]
 CXX_FLAGS = ["-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-pthread"]
 
@@ -54,10 +60,15 @@ def hipcc_path() -> str:
 def build_hip(force: bool = False) -> str:
     os.makedirs(LIB, exist_ok=True)
     srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, "ampli_internal.h"), os.path.join(CSRC, "ampli_math.h"), os.path.join(CSRC, "ampli_synth.h"),
-                   os.path.join(ROOT, "include", "amplisolve_hip.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(ROOT, "include", "amplisolve_hip.h")]
     if force or _newer(HIP_LIB, deps):
-        _run([hipcc_path(), *HIPCC_FLAGS, "-o", HIP_LIB, *srcs])
+        # every translation unit to an object of its own, all at once (at most 16 compilers), then one link
+        os.makedirs(OBJ, exist_ok=True)
+        objs = [os.path.join(OBJ, os.path.splitext(f)[0] + ".o") for f in HIP_SOURCES]
+        flags = [f for f in HIPCC_FLAGS if f != "-shared"]
+        with ThreadPoolExecutor(max_workers=min(len(srcs), 16)) as pool:
+            list(pool.map(lambda so: _run([hipcc_path(), *flags, "-c", "-o", so[1], so[0]]), zip(srcs, objs)))
+        _run([hipcc_path(), *HIPCC_FLAGS, "-o", HIP_LIB, *objs])
     return HIP_LIB
 
 

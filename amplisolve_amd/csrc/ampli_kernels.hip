@@ -1,125 +1,56 @@
-// amplisolve_amd/csrc/ampli_kernels.hip -- the HIP kernels of libamplisolve_hip.so (gfx950, wave64), their launchers and C ABI.
+// amplisolve_amd/csrc/ampli_kernels.hip -- the kernels of the step bench.py times, their launchers and C ABI (gfx950, wave64); and the
+// map of the kernel translation units of libamplisolve_hip.so.
 //
 // HBM-bound integer / scalar-FP work, no MFMA.  LAY = record layout (AMPLI_RECORDS_I32 / _U16 / _U24: 32 / 16 / 24 bytes per record).
-// The file follows the path; every stage holds its kernels, then their launchers and entry points:
+// The units follow the path; every stage holds its kernels, then their launchers and entry points.  A kernel is defined and launched
+// in one unit only; where another unit needs it, it calls a host launcher declared in ampli_device.h.
+// This file (bench.py's kernel_source_sha() covers it and ampli_math.h):
 //   records            records_pack16_kernel / records_pack24_kernel   int32 records -> the packed layouts
 //   error reduce       error_reduce_kernel<FAST,G,LAY>   EE:1149-1296 (+clones), EE:1565-1631 (+clones)   one record read per
 //                        (position, sample); epilogue: fused finalize_lane (one GPU), packed sums (all-reduce merge) or slice-major
 //                        sums + germ-max pairs (position-sliced merge)
 //                      error_reduce_u16_kernel / error_reduce_u24_kernel<DUP,TAB>   the same with a compact per-position state, the
 //                        shipped shape for packed records; dup_tiles_kernel lists the tiles they leave to error_reduce_kernel
+//                      acc_merge_kernel / acc_pack_sliced_kernel   after a cut along the samples: the partial tables folded in order,
+//                        the merged table -> slice-major exchange buffers
 //                      error_sums_inorder_kernel<LAY>   the eight threshold sums in the reference's own order (outside the envelope)
-//   merges and slices  acc_merge_kernel / acc_merge_ptr_kernel / gm_merge_kernel   ordered combines of partial accumulator tables
-//                      acc_pack_kernel / acc_unpack_kernel / acc_pack_sliced_kernel   additive planes <-> exchange buffers
-//                      error_finalize_slice_kernel -> error_table_unslice_kernel   one slice's error-table block -> plane-major table
-//   finalize           error_finalize_kernel / error_finalize_merged_kernel   EE:1659-1714 (+clones), sentinel rule
-//                        EE:1260/1318/1374/1431, text round trip EE:1704 -> VC:889
+//   finalize           error_finalize_kernel   EE:1659-1714 (+clones), sentinel rule EE:1260/1318/1374/1431, text round trip
+//                        EE:1704 -> VC:889
 //   Poisson            poisson_stream_kernel<LAY,IRR> + poisson_drain_kernel   VC:752-898 (+clones), VC:3721-3884   prefilter mode:
 //                        one record read per (position, tumour), the few scores past the gate queued and drained
 //                      poisson_full_kernel<LAY>   all-scores mode: light scores in place, heavy ones compacted per workgroup
 //                      poisson_call_kernel<MODE,LAY>   one lane per record, every score in place: the dense VAF output (either mode)
 //                      lgamma_table_kernel   kf_lgamma at the integers, for the drain and the all-scores mode
-//   detection limits   limit_pairs_kernel<LAY,IRR>   the smallest counts the gate of VC:898 would pass, per record and base
-//   auxiliary          score_batch_kernel / score_dense_batch_kernel / roundtrip_batch_kernel   scorer and text round trip on lists
+//                      queue_counters_reset_kernel   the prefilter queue's counters inside a captured graph
+// ampli_exchange.hip   merges and slices of the multi-GPU paths:
+//                      acc_merge_ptr_kernel / gm_merge_kernel   ordered combines of partial accumulator tables
+//                      acc_pack_kernel / acc_unpack_kernel   additive planes <-> exchange buffers
+//                      error_finalize_slice_kernel -> error_table_unslice_kernel   one slice's error-table block -> plane-major table
+//                      error_finalize_merged_kernel   finalize from the all-reduced sums and the gathered germ-max regions
+// ampli_loo.hip        leave-one-out: loo_stream_kernel<LAY,IRR> + loo_drain_kernel   the panel of normals against its S-1 tables
+// ampli_limits.hip     detection limits and power: limit_pairs_kernel<LAY,IRR>   the smallest counts the gate of VC:898 would pass, per
+//                        record and base; limit_power_kernel<LAY>   the gate's power at given allele fractions, LoD
+// ampli_aux.hip        score_batch_kernel / score_dense_batch_kernel / roundtrip_batch_kernel   scorer and text round trip on lists
 //                      synth_fill_kernel / synth_ref_kernel   synthetic panels (ampli_synth.h)
+// ampli_device.h       what more than one of these units needs: record types and decode, accumulator state, finalize, the queue's item,
+//                        hand-over and drain body, launch dispatch, the host helpers one unit defines for the others
 // See include/amplisolve_hip.h for the data layout and DESIGN.md for the rooflines.  The library's other translation units:
 // ampli_runtime.hip (context, streams, memory, settings), ampli_pileup.hip (pileup_count_kernel, the step upstream of the path),
-// ampli_comm.hip (RCCL binding of the multi-GPU merge), ampli_internal.h (what they share).
+// ampli_comm.hip (RCCL binding of the multi-GPU merge), ampli_internal.h (the context and the stream helpers they all share).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 #include <cstring>
 #include <string>
-#include <type_traits>
 
 #include "../../include/amplisolve_hip.h"
+#include "ampli_device.h"
 #include "ampli_internal.h"
 #include "ampli_math.h"
-#include "ampli_synth.h"
 
 // ==== records: layouts, the cohort a kernel reads, int32 -> packed records =============================================================
 
-// streaming 16-byte load of record data (default cache policy: non-temporal loads measured 4-10 % slower)
-__device__ __forceinline__ int4 ld_stream(const int4 *p) { return *p; }
-
-// Record layouts (include/amplisolve_hip.h), template parameter LAY:
-//   AMPLI_RECORDS_I32  8 x int32, two int4 per record                      (absent: INT32_MIN in field 0)
-//   AMPLI_RECORDS_U16  8 x uint16, one int4 per record                     (absent: 0xFFFF)
-//   AMPLI_RECORDS_U24  8 x 24-bit little-endian, 24 bytes = three 8-byte loads per record (absent: 0xFFFFFF)
-// A raw record is what a lane keeps in flight; rec_decode widens it to the {forward int4, reverse int4} pair every
-// visit function takes.
-template <int LAY> struct RawRec { int4 a, b; };
-template <> struct RawRec<AMPLI_RECORDS_U24> { uint2 a, b, c; };
-
-template <int LAY> __device__ __forceinline__ RawRec<LAY> rec_load(const int4 *__restrict__ recs, const size_t index)
-{
-    RawRec<LAY> r;
-    if constexpr (LAY == AMPLI_RECORDS_U24) {
-        const uint2 *__restrict__ q = (const uint2 *)((const char *)recs + index * 24);
-        r.a = q[0]; r.b = q[1]; r.c = q[2];
-    } else if constexpr (LAY == AMPLI_RECORDS_U16) {
-        r.a = ld_stream(recs + index); r.b = r.a;
-    } else {
-        r.a = ld_stream(recs + index * 2); r.b = ld_stream(recs + index * 2 + 1);
-    }
-    return r;
-}
-
-// A cohort (or one chunk of a streamed cohort) on the device.  Record r < P of sample s lives at
-// base + (s*row_stride + r) * record_bytes; extra occurrence e (record P + e) at ext + (s*ext_stride + e) * record_bytes.
-// The dense interchange layout [n][P+E] is row_stride = ext_stride = P + E, ext = base + P records; a padded row stride
-// (power-of-two panels) or a separately uploaded extras array are the same kernels with other numbers.
-struct RecView {
-    const char *base;
-    long long row_stride; // records
-    const char *ext;
-    long long ext_stride; // records
-    // optional RD column of the lines whose RD differs from A+C+G+T (EE:1178-1181, VC:762-765): rd [n][P], rd_ext [n][E],
-    // AMPLI_ABSENT where the line is regular; NULL when every line of the cohort is
-    const int *rd;
-    const int *rd_ext;
-};
-
-__host__ __device__ constexpr int rec_bytes(const int layout)
-{
-    return layout == AMPLI_RECORDS_U24 ? 24 : (layout == AMPLI_RECORDS_U16 ? 16 : 32);
-}
-
-template <int LAY> __device__ __forceinline__ RawRec<LAY> rec_load_at(const char *__restrict__ q)
-{
-    RawRec<LAY> r;
-    if constexpr (LAY == AMPLI_RECORDS_U24) {
-        const uint2 *__restrict__ u = (const uint2 *)q;
-        r.a = u[0]; r.b = u[1]; r.c = u[2];
-    } else if constexpr (LAY == AMPLI_RECORDS_U16) {
-        r.a = ld_stream((const int4 *)q); r.b = r.a;
-    } else {
-        r.a = ld_stream((const int4 *)q); r.b = ld_stream((const int4 *)q + 1);
-    }
-    return r;
-}
-
-// four 24-bit fields out of three dwords
-__device__ __forceinline__ int4 unpack24(const unsigned w0, const unsigned w1, const unsigned w2)
-{
-    return make_int4((int)(w0 & 0xFFFFFFu), (int)(__builtin_amdgcn_alignbit(w1, w0, 24) & 0xFFFFFFu),
-                     (int)(__builtin_amdgcn_alignbit(w2, w1, 16) & 0xFFFFFFu), (int)(w2 >> 8));
-}
-
-template <int LAY> __device__ __forceinline__ void rec_decode(const RawRec<LAY> &r, int4 &fw, int4 &bw)
-{
-    if constexpr (LAY == AMPLI_RECORDS_U24) {
-        fw = unpack24(r.a.x, r.a.y, r.b.x);
-        bw = unpack24(r.b.y, r.c.x, r.c.y);
-        if (fw.x == 0xFFFFFF) fw.x = AMPLI_ABSENT;
-    } else if constexpr (LAY == AMPLI_RECORDS_U16) {
-        fw = make_int4(r.a.x & 0xFFFF, (int)((unsigned)r.a.x >> 16), r.a.y & 0xFFFF, (int)((unsigned)r.a.y >> 16));
-        bw = make_int4(r.a.z & 0xFFFF, (int)((unsigned)r.a.z >> 16), r.a.w & 0xFFFF, (int)((unsigned)r.a.w >> 16));
-        if (fw.x == 0xFFFF) fw.x = AMPLI_ABSENT;
-    } else {
-        fw = r.a; bw = r.b;
-    }
-}
+// the record types, rec_load_at / rec_decode, RecView and DevCohort: ampli_device.h
 
 // 8 x int32 records -> 8 x uint16 records (AMPLI_ABSENT -> 0xFFFF); *overflow is raised for a count above 65534
 __global__ __launch_bounds__(256) void records_pack16_kernel(const int4 *__restrict__ in, const long long n, uint4 *__restrict__ out,
@@ -166,16 +97,6 @@ __global__ __launch_bounds__(256) void records_pack24_kernel(const int4 *__restr
     out[i * 3 + 2] = make_uint2(w[4], w[5]);
 }
 
-// what the kernels read: a cohort (or one chunk of a streamed one) resident on the device
-struct DevCohort {
-    RecView rv;
-    int layout;   // AMPLI_RECORDS_*
-    int n;        // samples
-    long long E;  // extra-occurrence slots per sample
-    const unsigned *dup_off; // [P+1]: extras of position p are e in [dup_off[p], dup_off[p+1])   (error_reduce)
-    const unsigned *ext_pos; // [E]: position of extra e                                          (poisson_call)
-};
-
 // the dense interchange layout [n][P+E] in the context's record layout (the classic entry points)
 static DevCohort dense_cohort(const ampli_ctx *ctx, const void *d_recs, int64_t P, int64_t E, int n, const uint32_t *dup_off,
                               const uint32_t *ext_pos)
@@ -191,7 +112,7 @@ static DevCohort dense_cohort(const ampli_ctx *ctx, const void *d_recs, int64_t 
     return c;
 }
 
-static int cohort_from_records(ampli_ctx *ctx, const ampli_records *r, int64_t P, DevCohort &c)
+int cohort_from_records(ampli_ctx *ctx, const ampli_records *r, int64_t P, DevCohort &c)
 {
     if (!r || !r->recs || r->n_samples <= 0 || r->E < 0) return fail(ctx, AMPLI_E_INVALID, "records: recs, n_samples > 0 and E >= 0 are required");
     if (r->layout != AMPLI_RECORDS_I32 && r->layout != AMPLI_RECORDS_U16 && r->layout != AMPLI_RECORDS_U24)
@@ -219,27 +140,13 @@ static int cohort_from_records(ampli_ctx *ctx, const ampli_records *r, int64_t P
 // what every kernel reading a cohort needs of it: extras come with their index (`index`, called `index_name` in the message;
 // index_name == nullptr: the kernel needs no index of the extras and none is asked for),
 // records 16-byte aligned (8-byte in the 24-byte layout)
-static int check_records(ampli_ctx *ctx, const DevCohort &co, const char *what, const uint32_t *index, const char *index_name)
+int check_records(ampli_ctx *ctx, const DevCohort &co, const char *what, const uint32_t *index, const char *index_name)
 {
     if (co.E > 0 && !index && index_name) return fail(ctx, AMPLI_E_INVALID, (std::string(what) + ": E > 0 needs " + index_name).c_str());
     const uintptr_t am = co.layout == AMPLI_RECORDS_U24 ? 7 : 15;
     if (((uintptr_t)co.rv.base & am) != 0 || (co.E > 0 && ((uintptr_t)co.rv.ext & am) != 0))
         return fail(ctx, AMPLI_E_INVALID, (std::string(what) + ": recs must be 16-byte aligned (8-byte for the 24-byte layout)").c_str());
     return AMPLI_OK;
-}
-
-// Launch dispatch: f(constant) for the run-time value, inside a generic lambda the template argument of a kernel.
-template <int V> using Const = std::integral_constant<int, V>;
-template <class F> static void with_layout(const int layout, F &&f) // every record layout
-{
-    if (layout == AMPLI_RECORDS_U24) f(Const<AMPLI_RECORDS_U24>{});
-    else if (layout == AMPLI_RECORDS_U16) f(Const<AMPLI_RECORDS_U16>{});
-    else f(Const<AMPLI_RECORDS_I32>{});
-}
-template <class F> static void with_bool(const bool b, F &&f)
-{
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
 }
 
 extern "C" int ampli_records_pack16(ampli_ctx *ctx, const int32_t *d_recs32, int64_t n_records, void *d_recs16, int32_t *d_overflow)
@@ -272,7 +179,7 @@ extern "C" int ampli_records_pack24(ampli_ctx *ctx, const int32_t *d_recs32, int
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 
 // every plane starts 256-byte aligned
-static void acc_offsets(int64_t P, size_t off[9])
+void acc_offsets(int64_t P, size_t off[9])
 {
     size_t o = 0;
     off[0] = o; o = align_up(o + (size_t)P * 8 * sizeof(double), 256);   // snt
@@ -314,20 +221,6 @@ extern "C" int ampli_acc_bind(void *base, int64_t P, ampli_acc_table *out)
     return AMPLI_OK;
 }
 
-// ---------------------------------------------------------------------------
-// per-lane accumulator for one position (all 4 nucleotides)
-// ---------------------------------------------------------------------------
-struct LaneAcc {
-    double snt[2][4];
-    long long srd[2][4];
-    int cnt[4];
-    int nrec;
-    int gm_n[4];
-    int gm_first[4];
-    float gm_first_af[4];
-    float gm_rest[4];
-};
-
 __device__ __forceinline__ void lane_acc_init(LaneAcc &a)
 {
 #pragma unroll
@@ -341,26 +234,6 @@ __device__ __forceinline__ void lane_acc_init(LaneAcc &a)
         a.gm_rest[nt] = -INFINITY;
     }
     a.nrec = 0;
-}
-
-// The threshold half of the record gate (EE:1595 + clones): bit nt set when the record's counts of nucleotide nt go into the
-// threshold sums -- covered on both strands and AF <= 0.05 on each strand, as an integer bound (ampli_math.h), or the literal fp
-// gates when `big` (an irregular line or RD >= 2^24: never for real panels).  visit_record and the leave-one-out kernel both
-// gate through here, so the table of the whole cohort and the S-1 tables subtracted from it cannot drift apart.
-__device__ __forceinline__ unsigned thr_gate(const int fw[4], const int bw[4], const int FW, const int BW, const bool covok, const bool big)
-{
-    const int lim_fw = ampli_af_limit(FW), lim_bw = ampli_af_limit(BW);
-    unsigned q = 0;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        bool g_fw = fw[nt] <= lim_fw, g_bw = bw[nt] <= lim_bw;
-        if (big) {
-            g_fw = ampli_af_gate_fp(fw[nt], FW);
-            g_bw = ampli_af_gate_fp(bw[nt], BW);
-        }
-        q |= (covok && g_fw && g_bw) ? 1u << nt : 0u;
-    }
-    return q;
 }
 
 // One record of one sample at this lane's position.  r0 = {Afw,Cfw,Gfw,Tfw}, r1 = {Ars,Crs,Grs,Trs}.
@@ -411,35 +284,6 @@ __device__ __forceinline__ void visit_record(LaneAcc &a, const int4 r0, const in
     }
 }
 
-// L = L (+) R, L covering the earlier samples
-__device__ __forceinline__ void lane_acc_merge(LaneAcc &L, const LaneAcc &R)
-{
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        L.snt[0][nt] += R.snt[0][nt]; L.snt[1][nt] += R.snt[1][nt];
-        L.srd[0][nt] += R.srd[0][nt]; L.srd[1][nt] += R.srd[1][nt];
-        L.cnt[nt] += R.cnt[nt];
-        if (R.gm_n[nt] != 0) {
-            if (L.gm_n[nt] == 0) {
-                L.gm_first[nt] = R.gm_first[nt];
-                L.gm_first_af[nt] = R.gm_first_af[nt];
-                L.gm_rest[nt] = R.gm_rest[nt];
-            } else {
-                float m = L.gm_rest[nt];
-                if (m <= R.gm_first_af[nt]) m = R.gm_first_af[nt];
-                if (m <= R.gm_rest[nt]) m = R.gm_rest[nt];
-                L.gm_rest[nt] = m;
-            }
-            L.gm_n[nt] += R.gm_n[nt];
-        }
-    }
-    L.nrec += R.nrec;
-}
-
-struct AccPtrs {
-    double *snt; long long *srd; int *cnt; int *nrec; int *gm_n; int *gm_first; float *gm_first_af; float *gm_rest;
-};
-
 __device__ __forceinline__ AccPtrs acc_at(char *base, long long /*P*/, size_t o0, size_t o1, size_t o2, size_t o3,
                                           size_t o4, size_t o5, size_t o6, size_t o7)
 {
@@ -449,62 +293,6 @@ __device__ __forceinline__ AccPtrs acc_at(char *base, long long /*P*/, size_t o0
     a.gm_first_af = (float *)(base + o6); a.gm_rest = (float *)(base + o7);
     return a;
 }
-
-__device__ __forceinline__ void lane_acc_store(const AccPtrs &t, long long P, long long p, const LaneAcc &a)
-{
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        t.snt[(0 * 4 + nt) * P + p] = a.snt[0][nt];
-        t.snt[(1 * 4 + nt) * P + p] = a.snt[1][nt];
-        t.srd[(0 * 4 + nt) * P + p] = a.srd[0][nt];
-        t.srd[(1 * 4 + nt) * P + p] = a.srd[1][nt];
-        t.cnt[nt * P + p] = a.cnt[nt];
-        t.gm_n[nt * P + p] = a.gm_n[nt];
-        t.gm_first[nt * P + p] = a.gm_first[nt];
-        t.gm_first_af[nt * P + p] = a.gm_first_af[nt];
-        t.gm_rest[nt * P + p] = a.gm_rest[nt];
-    }
-    t.nrec[p] = a.nrec;
-}
-
-__device__ __forceinline__ void lane_acc_load(const AccPtrs &t, long long P, long long p, LaneAcc &a)
-{
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        a.snt[0][nt] = t.snt[(0 * 4 + nt) * P + p];
-        a.snt[1][nt] = t.snt[(1 * 4 + nt) * P + p];
-        a.srd[0][nt] = t.srd[(0 * 4 + nt) * P + p];
-        a.srd[1][nt] = t.srd[(1 * 4 + nt) * P + p];
-        a.cnt[nt] = t.cnt[nt * P + p];
-        a.gm_n[nt] = t.gm_n[nt * P + p];
-        a.gm_first[nt] = t.gm_first[nt * P + p];
-        a.gm_first_af[nt] = t.gm_first_af[nt * P + p];
-        a.gm_rest[nt] = t.gm_rest[nt * P + p];
-    }
-    a.nrec = t.nrec[p];
-}
-
-// ---------------------------------------------------------------------------
-// finalize of one position from its merged LaneAcc: quorum, rates, NaN code, the table text round trip and the
-// Germ_Max sentinel rule (EE:1659-1714 + clones, EE:1260/1318/1374/1431, EE:1704 -> VC:889-890, EE:2680-2684).
-// Shared by error_finalize_kernel and by the fused epilogue of error_reduce_kernel.
-// ---------------------------------------------------------------------------
-struct FinOut {
-    float *rate; unsigned char *code; float *thr; float *germ_val; unsigned char *germ_present; int *flags;
-    double *packed; // optional: the additive planes as [snt 8P | srd 8P | cnt 4P | nrec P] doubles (multi-GPU merge)
-    // position-sliced exchange buffers (reduce-scatter / all-to-all merge): slice k = positions [k*slice_len, (k+1)*slice_len)
-    long long slice_len; // 0: `packed` is plane-major over the whole panel (above)
-    double *sl_sums;     // [n_slices][21][slice_len]: the same 21 additive planes, slice-major
-    float *sl_gm;        // [n_slices][8][slice_len]: germ-max first_af[4] (-1 = no qualifying record) | rest[4]
-    long long sl_group;  // batches per slice chunk (ampli_set_slice_group): chunk k of this batch starts k*sl_group*{planes,8}*slice_len
-                         //  elements behind sl_sums / sl_gm (which already point at this batch's part of chunk 0)
-    int sl_fmt;          // AMPLI_SLICE_WIDE: 21 planes, one value each; AMPLI_SLICE_SLIM: 14 planes, the integer planes packed
-    int sl_n;            //  (slim) number of slices = ranks whose contributions are summed: the range a shard may use of a packed field
-    int *sl_flags;       //  (slim) the context's flag word: AMPLI_FLAG_SLICE_RANGE when a value does not fit its share of a field
-    int accumulate;      // the table already holds the state of the EARLIER samples: result = table (+) this launch
-                         //  (streamed cohorts: one launch per uploaded chunk of samples, in visit order)
-    int summary;         // host side only: the caller takes the table as streaming state (AMPLI_REDUCE_SUMMARY), so the compact kernel may write it
-};
 
 __device__ __forceinline__ void lane_acc_store_packed(double *__restrict__ pk, const long long P, const long long p, const LaneAcc &a)
 {
@@ -518,17 +306,6 @@ __device__ __forceinline__ void lane_acc_store_packed(double *__restrict__ pk, c
     }
     pk[20 * P + p] = (double)a.nrec;
 }
-
-// The sums of the sliced exchange travel as doubles (ONE reduce-scatter, SUM, f64).  AMPLI_SLICE_WIDE: 21 planes, one value
-// each (snt 8 | srd 8 | cnt 4 | nrec 1) = 168 B per position.  AMPLI_SLICE_SLIM: 14 planes = 112 B: the integer planes share
-// doubles -- the two strands' depth sums of a nucleotide as lo + hi * 2^26, the counts as a + b * 2^17 (+ c * 2^34).  A sum of
-// doubles adds the fields independently and exactly as long as every field's TOTAL stays below its width (and the whole below
-// 2^53): each of the n shards may therefore use 1/n of a field's range, checked here where the shard's values are packed
-// (AMPLI_FLAG_SLICE_RANGE: the caller repeats the exchange in the wide format; config 4 on 8 GPUs uses < 3 % of the range).
-constexpr double SLIM_D = 67108864.0;        // 2^26: strand-depth sums
-constexpr double SLIM_C = 131072.0;          // 2^17: record counts
-constexpr double SLIM_C2 = 17179869184.0;    // 2^34
-__host__ __device__ constexpr int slice_planes(const int fmt) { return fmt == AMPLI_SLICE_SLIM ? 14 : 21; }
 
 // slice-major stores for the reduce-scatter merge: each destination rank's slice is one contiguous chunk
 // (Acc: LaneAcc, or the compact kernel's Part16 -- the same fields under the same names)
@@ -577,65 +354,6 @@ __device__ __forceinline__ void lane_acc_store_gm(const AccPtrs &t, const long l
         t.gm_first_af[nt * P + p] = a.gm_first_af[nt];
         t.gm_rest[nt * P + p] = a.gm_rest[nt];
     }
-}
-
-// quorum, rates and NaN code of one (position, nucleotide) from its sums (EE:1659-1682): the code, 0 estimate, 1 below quorum,
-// 2 NaN; the rates are 0 unless the code is 0.  Shared by finalize_one and the leave-one-out kernel's S-1 tables.
-__device__ __forceinline__ unsigned char fin_rates(const double sfw, const double sbw, const long long dfw, const long long dbw, const int cnt,
-                                                   const int nrec, float &r_fw, float &r_bw)
-{
-    r_fw = 0.0f; r_bw = 0.0f;
-    if ((double)cnt < 0.338 * (double)nrec) return 1; // EE:1659
-    r_fw = (float)sfw / (float)(double)dfw; // EE:1679
-    r_bw = (float)sbw / (float)(double)dbw; // EE:1680
-    if (isnan(r_fw) || isnan(r_bw)) { r_fw = 0.0f; r_bw = 0.0f; return 2; } // EE:1682
-    return 0;
-}
-
-// one (position, nucleotide): returns true when a double sum left the exactness envelope
-__device__ __forceinline__ bool finalize_one(const int nt, const double sfw, const double sbw, const long long dfw, const long long dbw,
-                                             const int cnt, const int nrec, const int gm_n, const float gm_rest, const long long P,
-                                             const long long p, const double limit, const FinOut &o)
-{
-    const long long i = nt * P + p, ifw = (0 * 4 + nt) * P + p, ibw = (1 * 4 + nt) * P + p;
-    float r_fw, r_bw;
-    const unsigned char c = fin_rates(sfw, sbw, dfw, dbw, cnt, nrec, r_fw, r_bw);
-    o.code[i] = c;
-    o.rate[ifw] = r_fw;
-    o.rate[ibw] = r_bw;
-    if (o.thr) {
-        o.thr[ifw] = c ? 0.01f : ampli_text_roundtrip(r_fw); // EE:2680-2684 / EE:1704 -> VC:889-890
-        o.thr[ibw] = c ? 0.01f : ampli_text_roundtrip(r_bw);
-    }
-    if (o.germ_val) {
-        float v = (nt == 0) ? -888.0f : 0.0f; // EE:1260 / EE:1318,1374,1431
-        if (gm_n > 1) { if (v <= gm_rest) v = gm_rest; }
-        o.germ_val[i] = gm_n ? v : 0.0f;
-        if (o.germ_present) o.germ_present[i] = gm_n ? 1 : 0;
-    }
-    return !(sfw < limit) || !(sbw < limit);
-}
-
-// exactness envelope of the double sums: every addend is a multiple of ulp(float(cov)*C) and the
-// running sum must stay below 2^52 such ulps
-__device__ __forceinline__ double envelope_limit(const float C, const int cov)
-{
-    const float pmin = (float)cov * C;
-    int ex;
-    (void)frexpf(pmin > 0 ? pmin : 1.0f, &ex);
-    return ldexp(1.0, ex - 24) * 9007199254740992.0 * 0.5;
-}
-
-__device__ __forceinline__ void finalize_lane(const LaneAcc &a, const long long P, const long long p, const float C,
-                                              const int cov, const FinOut &o)
-{
-    const double limit = envelope_limit(C, cov);
-    bool bad = false;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt)
-        bad |= finalize_one(nt, a.snt[0][nt], a.snt[1][nt], a.srd[0][nt], a.srd[1][nt], a.cnt[nt], a.nrec, a.gm_n[nt], a.gm_rest[nt], P, p,
-                            limit, o);
-    if (bad && o.flags) atomicOr(o.flags, 1);
 }
 
 // ---------------------------------------------------------------------------
@@ -765,7 +483,6 @@ __device__ __forceinline__ void visit_fast(FastAcc &a, const int4 r0, const int4
 // split for acc_merge_kernel.
 // ---------------------------------------------------------------------------
 constexpr int RED_WAVES = 4;
-
 
 __device__ __forceinline__ void fast_to_lane(const FastAcc &f, LaneAcc &a)
 {
@@ -1303,7 +1020,7 @@ __global__ __launch_bounds__(256, 5) void error_reduce_u24_kernel(const RecView 
     compact_reduce_body<AMPLI_RECORDS_U24, DUP, TAB>(sh, rv, P, p_lo, p_hi, dup_off, S, chunk_len, C, cov, flags, tab, fin);
 }
 
-static int ensure_ws(ampli_ctx *ctx, size_t bytes)
+int ensure_ws(ampli_ctx *ctx, size_t bytes)
 {
     if (ctx->ws_bytes >= bytes) return AMPLI_OK;
     if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "workspace would have to grow while capturing: run the sequence once first");
@@ -1313,7 +1030,7 @@ static int ensure_ws(ampli_ctx *ctx, size_t bytes)
     return AMPLI_OK;
 }
 
-static AccPtrs to_ptrs(const ampli_acc_table *t)
+AccPtrs to_ptrs(const ampli_acc_table *t)
 {
     AccPtrs a;
     a.snt = t->snt; a.srd = (long long *)t->srd; a.cnt = t->cnt; a.nrec = t->nrec; a.gm_n = t->gm_n;
@@ -1332,7 +1049,7 @@ static AccPtrs acc_ptrs(char *base, const size_t off[9])
 }
 
 // the error table a finalize writes (rate and code required; thr, germ_val, germ_present and flags optional)
-static FinOut table_out(float *rate, uint8_t *code, float *thr, float *germ_val, uint8_t *germ_present, int32_t *flags)
+FinOut table_out(float *rate, uint8_t *code, float *thr, float *germ_val, uint8_t *germ_present, int32_t *flags)
 {
     FinOut o = {};
     o.rate = rate; o.code = code; o.thr = thr; o.germ_val = germ_val; o.germ_present = germ_present; o.flags = flags;
@@ -1341,7 +1058,7 @@ static FinOut table_out(float *rate, uint8_t *code, float *thr, float *germ_val,
 
 // the slice-major exchange buffers of a position-sliced merge: [n_slices][group][planes][L] sums and [n_slices][group][8][L]
 // germ-max pairs, of which this call fills batch grp_index (ampli_set_slice_group) in the context's format (ampli_set_slice_format)
-static FinOut slice_out(const ampli_ctx *ctx, const long long P, const int n_slices, double *d_sums, float *d_gm)
+FinOut slice_out(const ampli_ctx *ctx, const long long P, const int n_slices, double *d_sums, float *d_gm)
 {
     FinOut o = {};
     o.slice_len = ampli_slice_len(P, n_slices);
@@ -1353,7 +1070,7 @@ static FinOut slice_out(const ampli_ctx *ctx, const long long P, const int n_sli
 }
 
 // a bound table must be one buffer carved by ampli_acc_bind
-static bool acc_is_bound(const ampli_acc_table *t)
+bool acc_is_bound(const ampli_acc_table *t)
 {
     if (!t || !t->snt || t->P <= 0) return false;
     size_t off[9];
@@ -1362,11 +1079,45 @@ static bool acc_is_bound(const ampli_acc_table *t)
     return memcmp(&carved, &given, sizeof(AccPtrs)) == 0;
 }
 
-// launched by error_reduce_impl after a cut along the samples (defined with their stages below)
-__global__ void acc_merge_kernel(char *, const char *, size_t, int, long long, size_t, size_t, size_t, size_t, size_t, size_t, size_t,
-                                 size_t, const char *);
-__global__ void acc_pack_kernel(AccPtrs, long long, double *);
-__global__ void acc_pack_sliced_kernel(AccPtrs, long long, FinOut);
+// after a cut along the samples error_reduce_impl folds the partial tables and, for a multi-GPU shard, fills the exchange buffers
+// from the merged table (acc_pack_kernel: ampli_exchange.hip, through launch_acc_pack)
+
+// dst = parts[0] (+) parts[1] (+) ... in order; parts are tables at base + i*stride
+__global__ __launch_bounds__(256) void acc_merge_kernel(char *dst_base, const char *parts_base, const size_t part_stride,
+                                                        const int nparts, const long long P, const size_t o0,
+                                                        const size_t o1, const size_t o2, const size_t o3,
+                                                        const size_t o4, const size_t o5, const size_t o6,
+                                                        const size_t o7, const char *prior_base)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    LaneAcc a;
+    // prior_base: a table holding the state of earlier samples (streamed cohorts); the parts follow it in order
+    lane_acc_load(acc_at(const_cast<char *>(prior_base ? prior_base : parts_base), P, o0, o1, o2, o3, o4, o5, o6, o7), P, p, a);
+    for (int i = prior_base ? 0 : 1; i < nparts; ++i) {
+        LaneAcc b;
+        lane_acc_load(acc_at(const_cast<char *>(parts_base) + (size_t)i * part_stride, P, o0, o1, o2, o3, o4, o5, o6, o7), P, p, b);
+        lane_acc_merge(a, b);
+    }
+    lane_acc_store(acc_at(dst_base, P, o0, o1, o2, o3, o4, o5, o6, o7), P, p, a);
+}
+
+// table -> slice-major exchange buffers (only when the sample axis had to be split across workgroups)
+__global__ __launch_bounds__(256) void acc_pack_sliced_kernel(AccPtrs t, const long long P, const FinOut o)
+{
+    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= P) return;
+    LaneAcc a;
+    lane_acc_load(t, P, p, a);
+    lane_acc_store_sliced(o, p, a);
+}
+
+int launch_acc_pack_sliced(ampli_ctx *ctx, const AccPtrs &t, long long P, const FinOut &fo)
+{
+    hipLaunchKernelGGL(acc_pack_sliced_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, P, fo);
+    return check_launch(ctx, "acc_pack_sliced_kernel");
+}
+
 static int launch_finalize(ampli_ctx *ctx, const AccPtrs &t, long long P, float C, int cov, const FinOut &fo);
 
 // reduce (+ optional fused finalize).  d_acc may be NULL when fin.rate is set (the table is then not materialised
@@ -1501,14 +1252,11 @@ static int error_reduce_impl(ampli_ctx *ctx, const DevCohort &co, int64_t P, int
         rc = check_launch(ctx, "acc_merge_kernel");
         if (rc) return rc;
         if (fin.packed) {
-            hipLaunchKernelGGL(acc_pack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, (long long)P,
-                               fin.packed);
-            rc = check_launch(ctx, "acc_pack_kernel");
+            rc = launch_acc_pack(ctx, t, P, fin.packed);
             if (rc) return rc;
         }
         if (fin.slice_len) {
-            hipLaunchKernelGGL(acc_pack_sliced_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), t, (long long)P, fin);
-            rc = check_launch(ctx, "acc_pack_sliced_kernel");
+            rc = launch_acc_pack_sliced(ctx, t, P, fin);
             if (rc) return rc;
         }
         if (fin.rate) rc = launch_finalize(ctx, t, P, C, cov, fin);
@@ -1650,336 +1398,6 @@ extern "C" int ampli_error_sums_inorder(ampli_ctx *ctx, const ampli_records *rec
     return check_launch(ctx, "error_sums_inorder_kernel");
 }
 
-// ==== merges and slices: partial tables of several launches or GPUs -> one =============================================================
-
-// dst = parts[0] (+) parts[1] (+) ... in order; parts are tables at base + i*stride
-__global__ __launch_bounds__(256) void acc_merge_kernel(char *dst_base, const char *parts_base, const size_t part_stride,
-                                                        const int nparts, const long long P, const size_t o0,
-                                                        const size_t o1, const size_t o2, const size_t o3,
-                                                        const size_t o4, const size_t o5, const size_t o6,
-                                                        const size_t o7, const char *prior_base)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    LaneAcc a;
-    // prior_base: a table holding the state of earlier samples (streamed cohorts); the parts follow it in order
-    lane_acc_load(acc_at(const_cast<char *>(prior_base ? prior_base : parts_base), P, o0, o1, o2, o3, o4, o5, o6, o7), P, p, a);
-    for (int i = prior_base ? 0 : 1; i < nparts; ++i) {
-        LaneAcc b;
-        lane_acc_load(acc_at(const_cast<char *>(parts_base) + (size_t)i * part_stride, P, o0, o1, o2, o3, o4, o5, o6, o7), P, p, b);
-        lane_acc_merge(a, b);
-    }
-    lane_acc_store(acc_at(dst_base, P, o0, o1, o2, o3, o4, o5, o6, o7), P, p, a);
-}
-
-// merge of arbitrary (non-strided) part tables: pointers passed through a small device array
-__global__ __launch_bounds__(256) void acc_merge_ptr_kernel(AccPtrs dst, const AccPtrs *parts, const int nparts,
-                                                            const long long P)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    LaneAcc a;
-    lane_acc_load(parts[0], P, p, a);
-    for (int i = 1; i < nparts; ++i) {
-        LaneAcc b;
-        lane_acc_load(parts[i], P, p, b);
-        lane_acc_merge(a, b);
-    }
-    lane_acc_store(dst, P, p, a);
-}
-
-// ---------------------------------------------------------------------------
-// pack / unpack of the additive planes for the multi-GPU merge: ONE float64 buffer
-// [snt 8P | srd 8P | cnt 4P | nrec P] so that the shards merge with a single RCCL all-reduce (SUM).
-// srd / cnt / nrec are integers far below 2^53: exact in a double, exact under any summation order.
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void acc_pack_kernel(AccPtrs t, const long long P, double *__restrict__ out)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 21 * P) return;
-    double v;
-    if (i < 8 * P) v = t.snt[i];
-    else if (i < 16 * P) v = (double)t.srd[i - 8 * P];
-    else if (i < 20 * P) v = (double)t.cnt[i - 16 * P];
-    else v = (double)t.nrec[i - 20 * P];
-    out[i] = v;
-}
-
-__global__ __launch_bounds__(256) void acc_unpack_kernel(AccPtrs t, const long long P, const double *__restrict__ in)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= 21 * P) return;
-    const double v = in[i];
-    if (i < 8 * P) t.snt[i] = v;
-    else if (i < 16 * P) t.srd[i - 8 * P] = (long long)v;
-    else if (i < 20 * P) t.cnt[i - 16 * P] = (int)v;
-    else t.nrec[i - 20 * P] = (int)v;
-}
-
-// germ-max triples only.  regions: nparts copies of the gm region of a table (gm_n .. end of gm_rest),
-// region k at regions + k*stride; plane offsets inside a region as in the table.
-__global__ __launch_bounds__(256) void gm_merge_kernel(int *gm_n, int *gm_first, float *gm_first_af, float *gm_rest,
-                                                       const char *regions, const size_t stride, const size_t ofa,
-                                                       const size_t orr, const int nparts, const long long P)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; // over 4*P
-    if (i >= 4 * P) return;
-    int n = 0, first = 0x7fffffff;
-    float first_af = 0.0f, rest = -INFINITY;
-    for (int k = 0; k < nparts; ++k) {
-        const char *b = regions + (size_t)k * stride;
-        const int rn = ((const int *)b)[i];
-        if (rn == 0) continue;
-        const float fa = ((const float *)(b + ofa))[i], rr = ((const float *)(b + orr))[i];
-        if (n == 0) {
-            first = -1; first_af = fa; rest = rr; // the sample index is not exchanged: unknown after a gathered merge
-        } else {
-            if (rest <= fa) rest = fa;
-            if (rest <= rr) rest = rr;
-        }
-        n += rn;
-    }
-    gm_n[i] = n; gm_first[i] = first; gm_first_af[i] = first_af; gm_rest[i] = rest;
-}
-
-// ---------------------------------------------------------------------------
-// Position-sliced merge (reduce-scatter / all-to-all / all-gather): rank k owns positions [k*L, (k+1)*L).
-//   error_finalize_slice_kernel: the reduce-scattered sums of one slice + every rank's germ-max pair for that slice
-//                                (folded in rank order = sample order) -> one error-table block
-//   error_table_unslice_kernel : the all-gathered blocks -> the plane-major error table poisson_call reads
-// Block of a slice (all-gather unit): rate f32[8][L] | thr f32[8][L] | germ_val f32[4][L] | code u8[4][L] |
-// germ_present u8[4][L] | 64-byte tail (int32 flags).
-// ---------------------------------------------------------------------------
-__host__ __device__ __forceinline__ size_t slice_block_bytes(const long long L) { return (size_t)L * 88 + 64; }
-
-__device__ __forceinline__ FinOut slice_block_view(char *blk, const long long L)
-{
-    FinOut o = {};
-    o.rate = (float *)blk;
-    o.thr = (float *)(blk + (size_t)L * 32);
-    o.germ_val = (float *)(blk + (size_t)L * 64);
-    o.code = (unsigned char *)(blk + (size_t)L * 80);
-    o.germ_present = (unsigned char *)(blk + (size_t)L * 84);
-    o.flags = (int *)(blk + (size_t)L * 88);
-    return o;
-}
-
-__global__ __launch_bounds__(256) void error_finalize_slice_kernel(const double *__restrict__ sums, const float *__restrict__ gm,
-                                                                   const size_t gm_stride /* elements between the shards' pairs */,
-                                                                   const int nparts, const long long L, const long long p0,
-                                                                   const long long P, const float C, const int cov, char *blk, const int fmt)
-{
-    // one thread per (nucleotide, position of the slice): the slice is short (P / n positions), so the launch is a
-    // latency chain -- four times the threads, a quarter of the chain
-    const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int nt = (int)(t / L);
-    const long long q = t - (long long)nt * L;
-    if (nt >= 4 || p0 + q >= P) return;
-    int n = 0;
-    float rest = -INFINITY;
-    for (int k = 0; k < nparts; ++k) { // L (+) R = (L.first, max(L.rest, R.first_af, R.rest)), shards in sample order
-        const float fa = gm[(size_t)k * gm_stride + (size_t)nt * L + q];
-        if (fa < 0.0f) continue; // shard without a qualifying record
-        const float rr = gm[(size_t)k * gm_stride + (size_t)(4 + nt) * L + q];
-        if (n == 0) { rest = rr; n = (rr > -INFINITY) ? 2 : 1; } // n: 0, 1 or "more than one"
-        else { if (rest <= fa) rest = fa; if (rest <= rr) rest = rr; n = 2; }
-    }
-    const FinOut o = slice_block_view(blk, L);
-    long long d_fw, d_bw;
-    int cnt, nrec;
-    if (fmt == AMPLI_SLICE_SLIM) { // the summed fields come apart again: every one stayed below its width (checked where the shards packed them)
-        const double d = sums[(8 + nt) * L + q], hi = floor(d / SLIM_D);
-        d_fw = (long long)(d - hi * SLIM_D);
-        d_bw = (long long)hi;
-        const double c0 = sums[12 * L + q], c1 = sums[13 * L + q];
-        const double c0_2 = floor(c0 / SLIM_C2), c0_r = c0 - c0_2 * SLIM_C2, c0_1 = floor(c0_r / SLIM_C), c0_0 = c0_r - c0_1 * SLIM_C;
-        const double c1_1 = floor(c1 / SLIM_C), c1_0 = c1 - c1_1 * SLIM_C;
-        cnt = (int)(nt == 0 ? c0_0 : nt == 1 ? c0_1 : nt == 2 ? c0_2 : c1_0);
-        nrec = (int)c1_1;
-    } else {
-        d_fw = (long long)sums[(8 + 0 * 4 + nt) * L + q];
-        d_bw = (long long)sums[(8 + 1 * 4 + nt) * L + q];
-        cnt = (int)sums[(16 + nt) * L + q];
-        nrec = (int)sums[20 * L + q];
-    }
-    const bool bad = finalize_one(nt, sums[(0 * 4 + nt) * L + q], sums[(1 * 4 + nt) * L + q], d_fw, d_bw, cnt, nrec, n, rest, L, q,
-                                  envelope_limit(C, cov), o);
-    if (bad) atomicOr(o.flags, 1);
-}
-
-__global__ __launch_bounds__(256) void error_table_unslice_kernel(const char *__restrict__ blocks, const size_t block_stride,
-                                                                  const int nparts, const long long L, const long long P, const FinOut o)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p == 0 && o.flags) {
-        int f = 0;
-        for (int k = 0; k < nparts; ++k) f |= *(const int *)(blocks + (size_t)k * block_stride + (size_t)L * 88);
-        if (f) atomicOr(o.flags, f);
-    }
-    if (p >= P) return;
-    const long long k = p / L, q = p - k * L;
-    const FinOut b = slice_block_view(const_cast<char *>(blocks) + (size_t)k * block_stride, L);
-#pragma unroll
-    for (int j = 0; j < 8; ++j) {
-        o.rate[j * P + p] = b.rate[j * L + q];
-        if (o.thr) o.thr[j * P + p] = b.thr[j * L + q];
-    }
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        o.code[nt * P + p] = b.code[nt * L + q];
-        if (o.germ_val) o.germ_val[nt * P + p] = b.germ_val[nt * L + q];
-        if (o.germ_present) o.germ_present[nt * P + p] = b.germ_present[nt * L + q];
-    }
-}
-
-// table -> slice-major exchange buffers (only when the sample axis had to be split across workgroups)
-__global__ __launch_bounds__(256) void acc_pack_sliced_kernel(AccPtrs t, const long long P, const FinOut o)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    LaneAcc a;
-    lane_acc_load(t, P, p, a);
-    lane_acc_store_sliced(o, p, a);
-}
-
-extern "C" int ampli_acc_merge(ampli_ctx *ctx, const ampli_acc_table *d_dst, const ampli_acc_table *d_parts, int32_t nparts)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_dst || !d_parts || nparts < 1 || nparts > 64) return fail(ctx, AMPLI_E_INVALID, "acc_merge: 1 <= nparts <= 64");
-    const int64_t P = d_dst->P;
-    for (int i = 0; i < nparts; ++i)
-        if (d_parts[i].P != P) return fail(ctx, AMPLI_E_INVALID, "acc_merge: part table P mismatch");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "acc_merge cannot be captured (it uploads a pointer list)");
-    { int rc = ensure_ws(ctx, sizeof(AccPtrs) * 64); if (rc) return rc; }
-    AccPtrs hp[64];
-    for (int i = 0; i < nparts; ++i) hp[i] = to_ptrs(&d_parts[i]);
-    // small synchronous upload of the pointer list (not on a captured path)
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->ws, hp, sizeof(AccPtrs) * nparts, hipMemcpyHostToDevice, main_stream(ctx)));
-    HIP_TRY(ctx, hipStreamSynchronize(main_stream(ctx)));
-    hipLaunchKernelGGL(acc_merge_ptr_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_dst),
-                       (const AccPtrs *)ctx->ws, (int)nparts, (long long)P);
-    return check_launch(ctx, "acc_merge_ptr_kernel");
-}
-
-extern "C" int64_t ampli_acc_packed_len(int64_t P) { return P > 0 ? 21 * P : 0; }
-
-extern "C" int ampli_acc_pack(ampli_ctx *ctx, const ampli_acc_table *d_acc, double *d_packed)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || d_acc->P <= 0 || !d_packed) return fail(ctx, AMPLI_E_INVALID, "acc_pack: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_acc->P;
-    hipLaunchKernelGGL(acc_pack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P, d_packed);
-    return check_launch(ctx, "acc_pack_kernel");
-}
-
-extern "C" int ampli_acc_unpack(ampli_ctx *ctx, const double *d_packed, const ampli_acc_table *d_acc)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || d_acc->P <= 0 || !d_packed) return fail(ctx, AMPLI_E_INVALID, "acc_unpack: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_acc->P;
-    hipLaunchKernelGGL(acc_unpack_kernel, dim3((unsigned)((21 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P, d_packed);
-    return check_launch(ctx, "acc_unpack_kernel");
-}
-
-extern "C" int ampli_acc_regions(int64_t P, size_t *sum_bytes, size_t *gm_offset, size_t *gm_bytes)
-{
-    if (P <= 0) return AMPLI_E_INVALID;
-    size_t off[9];
-    acc_offsets(P, off);
-    if (sum_bytes) *sum_bytes = off[6]; // snt|srd|cnt|nrec|gm_n
-    if (gm_offset) *gm_offset = off[4];
-    if (gm_bytes) *gm_bytes = off[5] - off[4]; // gm_n|gm_first_af|gm_rest
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_gm_merge(ampli_ctx *ctx, const ampli_acc_table *d_dst, const void *d_regions, int32_t nparts)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_dst || !d_regions || nparts < 1) return fail(ctx, AMPLI_E_INVALID, "gm_merge: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_dst->P;
-    size_t off[9];
-    acc_offsets(P, off);
-    hipLaunchKernelGGL(gm_merge_kernel, dim3((unsigned)((4 * P + 255) / 256)), dim3(256), 0, main_stream(ctx), d_dst->gm_n,
-                       d_dst->gm_first, d_dst->gm_first_af, d_dst->gm_rest, (const char *)d_regions, off[5] - off[4],
-                       off[6] - off[4], off[7] - off[4], (int)nparts, P);
-    return check_launch(ctx, "gm_merge_kernel");
-}
-
-extern "C" int64_t ampli_slice_len(int64_t P, int32_t n_slices)
-{
-    if (P <= 0 || n_slices < 1) return 0;
-    const int64_t per = (P + n_slices - 1) / n_slices;
-    return (per + 63) / 64 * 64;
-}
-
-extern "C" int32_t ampli_slice_planes(int32_t format) { return slice_planes(format); }
-
-extern "C" int ampli_set_slice_format(ampli_ctx *ctx, int32_t format)
-{
-    if (!ctx || (format != AMPLI_SLICE_WIDE && format != AMPLI_SLICE_SLIM)) return AMPLI_E_INVALID;
-    ctx->slice_fmt = format;
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_slice_bytes_fmt(int64_t P, int32_t n_slices, int32_t format, size_t *sums_bytes, size_t *gm_bytes, size_t *block_bytes)
-{
-    const int64_t L = ampli_slice_len(P, n_slices);
-    if (L <= 0 || (format != AMPLI_SLICE_WIDE && format != AMPLI_SLICE_SLIM)) return AMPLI_E_INVALID;
-    if (sums_bytes) *sums_bytes = (size_t)n_slices * (size_t)slice_planes(format) * (size_t)L * sizeof(double);
-    if (gm_bytes) *gm_bytes = (size_t)n_slices * 8 * (size_t)L * sizeof(float);
-    if (block_bytes) *block_bytes = slice_block_bytes(L);
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_slice_bytes(int64_t P, int32_t n_slices, size_t *sums_bytes, size_t *gm_bytes, size_t *block_bytes)
-{
-    return ampli_slice_bytes_fmt(P, n_slices, AMPLI_SLICE_WIDE, sums_bytes, gm_bytes, block_bytes);
-}
-
-extern "C" int ampli_acc_to_slices(ampli_ctx *ctx, const ampli_acc_table *d_acc, int32_t n_slices, double *d_sums, float *d_gm)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!d_acc || !acc_is_bound(d_acc) || n_slices < 1 || !d_sums || !d_gm) return fail(ctx, AMPLI_E_INVALID, "acc_to_slices: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long P = d_acc->P;
-    hipLaunchKernelGGL(acc_pack_sliced_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), to_ptrs(d_acc), P,
-                       slice_out(ctx, P, n_slices, d_sums, d_gm));
-    return check_launch(ctx, "acc_pack_sliced_kernel");
-}
-
-extern "C" int ampli_error_finalize_slice(ampli_ctx *ctx, int64_t P, int32_t n_slices, int32_t slice_index,
-                                          const double *d_sum_slice, const float *d_gm_recv, float C, int32_t cov, void *d_block)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (P <= 0 || n_slices < 1 || slice_index < 0 || slice_index >= n_slices || !d_sum_slice || !d_gm_recv || !d_block || cov < 1)
-        return fail(ctx, AMPLI_E_INVALID, "error_finalize_slice: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long L = ampli_slice_len(P, n_slices);
-    const size_t G = (size_t)ctx->grp_size, g = (size_t)ctx->grp_index; // [group][planes][L] sums, [n][group][8][L] pairs, [group][block] out
-    hipLaunchKernelGGL(error_finalize_slice_kernel, dim3((unsigned)((4 * L + 255) / 256)), dim3(256), 0, main_stream(ctx),
-                       d_sum_slice + g * (size_t)slice_planes(ctx->slice_fmt) * (size_t)L, d_gm_recv + g * 8 * (size_t)L, G * 8 * (size_t)L, (int)n_slices, L,
-                       (long long)slice_index * L, (long long)P, C, (int)cov, (char *)d_block + g * slice_block_bytes(L), ctx->slice_fmt);
-    return check_launch(ctx, "error_finalize_slice_kernel");
-}
-
-extern "C" int ampli_error_table_unslice(ampli_ctx *ctx, int64_t P, int32_t n_slices, const void *d_blocks, float *d_rate,
-                                         uint8_t *d_code, float *d_thr, float *d_germ_val, uint8_t *d_germ_present,
-                                         int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (P <= 0 || n_slices < 1 || !d_blocks || !d_rate || !d_code) return fail(ctx, AMPLI_E_INVALID, "error_table_unslice: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    const long long L = ampli_slice_len(P, n_slices);
-    hipLaunchKernelGGL(error_table_unslice_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx),
-                       (const char *)d_blocks + (size_t)ctx->grp_index * slice_block_bytes(L), (size_t)ctx->grp_size * slice_block_bytes(L),
-                       (int)n_slices, L, (long long)P, table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags));
-    return check_launch(ctx, "error_table_unslice_kernel");
-}
-
 // ==== finalize: accumulator table -> error table =======================================================================================
 
 __global__ __launch_bounds__(256) void error_finalize_kernel(AccPtrs t, const long long P, const float C, const int cov, FinOut o)
@@ -1988,41 +1406,6 @@ __global__ __launch_bounds__(256) void error_finalize_kernel(AccPtrs t, const lo
     if (p >= P) return;
     LaneAcc a;
     lane_acc_load(t, P, p, a);
-    finalize_lane(a, P, p, C, cov, o);
-}
-
-// finalize straight from the merged pieces of a multi-GPU reduction: the all-reduced packed sums and the gathered
-// germ-max regions (folded here in rank order); no accumulator table is read or written.
-__global__ __launch_bounds__(256) void error_finalize_merged_kernel(const double *__restrict__ pk, const char *__restrict__ regions,
-                                                                    const size_t stride, const size_t ofa, const size_t orr,
-                                                                    const int nparts, const long long P, const float C,
-                                                                    const int cov, FinOut o)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= P) return;
-    LaneAcc a;
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-        a.snt[0][nt] = pk[(0 * 4 + nt) * P + p];
-        a.snt[1][nt] = pk[(1 * 4 + nt) * P + p];
-        a.srd[0][nt] = (long long)pk[8 * P + (0 * 4 + nt) * P + p];
-        a.srd[1][nt] = (long long)pk[8 * P + (1 * 4 + nt) * P + p];
-        a.cnt[nt] = (int)pk[16 * P + nt * P + p];
-        int n = 0;
-        float rest = -INFINITY;
-        for (int k = 0; k < nparts; ++k) { // ordered fold of the shards' germ-max triples (as gm_merge_kernel)
-            const char *b = regions + (size_t)k * stride;
-            const long long i = nt * P + p;
-            const int rn = ((const int *)b)[i];
-            if (rn == 0) continue;
-            const float fa = ((const float *)(b + ofa))[i], rr = ((const float *)(b + orr))[i];
-            if (n == 0) rest = rr;
-            else { if (rest <= fa) rest = fa; if (rest <= rr) rest = rr; }
-            n += rn;
-        }
-        a.gm_n[nt] = n; a.gm_rest[nt] = rest; a.gm_first[nt] = 0; a.gm_first_af[nt] = 0.0f;
-    }
-    a.nrec = (int)pk[20 * P + p];
     finalize_lane(a, P, p, C, cov, o);
 }
 
@@ -2040,22 +1423,6 @@ extern "C" int ampli_error_finalize(ampli_ctx *ctx, const ampli_acc_table *d_acc
     if (!d_acc || d_acc->P <= 0 || !d_rate || !d_code || cov < 1) return fail(ctx, AMPLI_E_INVALID, "error_finalize: bad argument");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     return launch_finalize(ctx, to_ptrs(d_acc), d_acc->P, C, (int)cov, table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags));
-}
-
-extern "C" int ampli_error_finalize_merged(ampli_ctx *ctx, int64_t P, const double *d_packed, const void *d_gm_regions,
-                                           int32_t nparts, float C, int32_t cov, float *d_rate, uint8_t *d_code, float *d_thr,
-                                           float *d_germ_val, uint8_t *d_germ_present, int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (P <= 0 || !d_packed || !d_gm_regions || nparts < 1 || !d_rate || !d_code || cov < 1)
-        return fail(ctx, AMPLI_E_INVALID, "error_finalize_merged: bad argument");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    size_t off[9];
-    acc_offsets(P, off);
-    hipLaunchKernelGGL(error_finalize_merged_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), d_packed,
-                       (const char *)d_gm_regions, off[5] - off[4], off[6] - off[4], off[7] - off[4], (int)nparts, (long long)P, C,
-                       (int)cov, table_out(d_rate, d_code, d_thr, d_germ_val, d_germ_present, d_flags));
-    return check_launch(ctx, "error_finalize_merged_kernel");
 }
 
 // ==== Poisson: tumour records + thresholds -> calls ====================================================================================
@@ -2088,18 +1455,6 @@ __device__ __forceinline__ float thr_at(const float *__restrict__ thr, const lon
     if (slice_len == 0) return thr[j * P + p];
     const long long k = p / slice_len, q = p - k * slice_len;
     return ((const float *)((const char *)thr + (size_t)k * block_bytes + (size_t)slice_len * 32))[j * slice_len + q];
-}
-
-// the reported VAFs and the evidence of one emitted call (VC:772-817)
-__device__ __forceinline__ void call_fill(ampli_call &c, const int sample, const int record, const int alt, const int rd, const double q_fw,
-                                          const double q_bw, const int k_fw, const int k_bw, const int FW, const int BW, const int flags = 0)
-{
-    c.sample = sample; c.record = record; c.alt = alt; c.rd = rd;
-    c.q_fw = q_fw; c.q_bw = q_bw;
-    c.af = (float)(k_fw + k_bw) / (float)rd;               // VC:814-817
-    c.af_fw = FW == 0 ? 0.0f : (float)k_fw / (float)FW;    // VC:785-790
-    c.af_bw = BW == 0 ? 0.0f : (float)k_bw / (float)BW;    // VC:805-810
-    c.k_fw = k_fw; c.k_bw = k_bw; c.fw = FW; c.bw = BW; c.flags = flags;
 }
 
 template <int MODE, int LAY>
@@ -2351,16 +1706,6 @@ __global__ __launch_bounds__(256, 4) void poisson_full_kernel(
 // LDS (an earlier version) still paid one such loop per wave for a couple of items.
 // ---------------------------------------------------------------------------
 
-struct PcItem { // 40 bytes, self-contained: the drain kernel needs no second look at the records or the thresholds
-    int sample;
-    int record_alt;   // record | alt << 30
-    int k_fw, k_bw;   // alt reads per strand
-    int FW, BW;       // strand depths
-    int rd;           // RD column: d_fw = rd - BW (VC:895), AF = X / rd (VC:814)
-    float e_fw, e_bw; // effective errors (ampli_effective_err); the leave-one-out kernel queues the raw thresholds of its S-1 table here
-    int pad;
-};
-
 // blockIdx.x -> (tile, row group): workgroups are dealt round-robin to the 8 XCDs (b and b + 8 share one), so the
 // row groups of a tile are given consecutive slots of ONE XCD.  tiles8 = tiles rounded up to a multiple of 8.
 __device__ __forceinline__ void pc_block_map(const unsigned b, const unsigned gy, unsigned &tile, unsigned &y)
@@ -2368,27 +1713,6 @@ __device__ __forceinline__ void pc_block_map(const unsigned b, const unsigned gy
     const unsigned xcd = b & 7u, slot = b >> 3;
     tile = (slot / gy) * 8u + xcd;
     y = slot % gy;
-}
-
-// Queue hand-over of a wave's staged items: ONE returning atomic on the shard's counter for up to PC_STAGE items (a
-// returning atomic costs a wave 1-3 us under load; one per (row, alternative) with a survivor, as a first version did,
-// kept ~40 % of the waves waiting at some point of their short lives), then a coalesced copy LDS -> HBM.
-constexpr int PC_STAGE = 64; // items a wave stages before it must hand over (64 lanes x at most one item per (row, alt))
-
-__device__ __forceinline__ void pc_flush(const PcItem *__restrict__ st, const int count, const int lane, PcItem *__restrict__ queue,
-                                         const long long queue_per_shard, unsigned long long *__restrict__ queue_n, const unsigned shard,
-                                         int *__restrict__ flags)
-{
-    unsigned long long base = 0;
-    if (lane == 0) base = atomicAdd(&queue_n[shard * AMPLI_CALL_COUNTER_STRIDE], (unsigned long long)count);
-    base = __shfl(base, 0);
-    // 40-byte items as 10 dwords each: lane l copies dwords l, l + 64, ...
-    const unsigned *__restrict__ src = (const unsigned *)st;
-    const long long room = queue_per_shard - (long long)base; // items that still fit (<= 0: none)
-    const int fit = room >= count ? count : (room > 0 ? (int)room : 0);
-    unsigned *__restrict__ dst = (unsigned *)(queue + (size_t)shard * queue_per_shard + base);
-    for (int i = lane; i < fit * 10; i += 64) dst[i] = src[i];
-    if (fit < count && lane == 0) atomicOr(flags, AMPLI_FLAG_QUEUE_OVERFLOW);
 }
 
 // Seven waves per SIMD (72 VGPRs), not eight: at 64 VGPRs the compiler spilled 7-23 registers to scratch, and every wave's
@@ -2522,6 +1846,7 @@ __global__ __launch_bounds__(256, 7) void poisson_stream_kernel(
             const bool skip_bw = exact && (unsigned)bw[nt] < (unsigned)AMPLI_COUNT_LIMIT && (float)bw[nt] <= c_bw * te[1][nt];
             if (live && nt != ref && !skip_fw && !skip_bw) pushmask |= 1u << nt;
         }
+        // (the same staging, with another fill of the item: loo_stream_kernel, ampli_loo.hip; a shared helper changes this kernel's code)
         if (__any(pushmask != 0)) { // rare: stage the items in LDS, one slot range per wave
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
@@ -2548,89 +1873,6 @@ __global__ __launch_bounds__(256, 7) void poisson_stream_kernel(
     if (staged) pc_flush(stage[wave], staged, lane, queue, queue_per_shard, queue_n, shard, flags);
 }
 
-// Two adjacent lanes per queued item, one per strand.  The scorer here is kf_gammaq's series branch in its
-// division-free form (ampli_kf_gammap_series_nodiv): a queued item has k > m on both strands or is no call.
-// LOO (the leave-one-out drain): the item carries the raw thresholds of its S-1 table instead of the effective errors, and
-// the list entries are ampli_loo_call, which keep those thresholds for the host.
-template <bool LOO>
-__device__ __forceinline__ void drain_body(
-    const PcItem *__restrict__ queue, const long long queue_per_shard, const unsigned long long *__restrict__ queue_n,
-    const long long R, unsigned *__restrict__ mask_words, std::conditional_t<LOO, ampli_loo_call, ampli_call> *__restrict__ calls,
-    const long long capacity, unsigned long long *__restrict__ n_calls, unsigned long long *__restrict__ next_queue_n, const unsigned shard_lo,
-    const unsigned shard_n, const double *__restrict__ lgtab)
-{
-    constexpr int IPB = 128; // items per workgroup pass
-    // the counter array of the NEXT poisson_call (the other half of a double buffer; its last reader, the previous
-    // drain, finished before this kernel started) is reset here, which saves a memset launch per call
-    if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x < AMPLI_CALL_SHARDS) next_queue_n[threadIdx.x * AMPLI_CALL_COUNTER_STRIDE] = 0ull;
-    // blockIdx.x = queue shard, blockIdx.y = workgroup within the shard: one load tells a workgroup what is its to do
-    const unsigned shard = blockIdx.x;
-    const int slot = threadIdx.x >> 1, strand = threadIdx.x & 1;
-    // the first pass's item is fetched BEFORE the shard's count is known (the slot exists whatever the count is): the kernel is one
-    // chain of dependent latencies -- count, item, scorer, returning atomic -- and this takes one link out of it
-    const long long i0 = (long long)blockIdx.y * IPB + slot;
-    PcItem first = queue[(size_t)shard * queue_per_shard + (i0 < queue_per_shard ? i0 : 0)];
-    long long cnt = (long long)queue_n[shard * AMPLI_CALL_COUNTER_STRIDE];
-    if (cnt > queue_per_shard) cnt = queue_per_shard;
-    for (long long ib = (long long)blockIdx.y * IPB; ib < cnt; ib += (long long)gridDim.y * IPB) {
-        const long long i = ib + slot;
-        const bool on = i < cnt;
-        PcItem it = ib == (long long)blockIdx.y * IPB ? first : queue[(size_t)shard * queue_per_shard + (on ? i : ib)];
-        const int k = strand ? it.k_bw : it.k_fw;
-        const int d = strand ? it.BW : it.rd - it.BW; // VC:895-896
-        const float err = LOO ? ampli_effective_err(strand ? it.e_bw : it.e_fw) : (strand ? it.e_bw : it.e_fw);
-        // err_eff = +inf stands for err == -1 (Q = -888, VC:3844-3849); 0 was already replaced by 0.0010008f.
-        // k <= m: the exact form of the prefilter bound (ampli_prefilter_nocall), Q < 5 -- no call whatever the value.
-        const double m = (double)d * err; // VC:3864: double * float
-        const bool eval = on && !isinf(err) && (double)k > m; // then z = m < s = k: the series branch of kf_gammaq (VC:3728)
-        double qv = -1.0; // "no call" (any value below 5)
-        if (eval) {
-            if (m > 0) qv = ampli_q_from_p(ampli_drain_p(k, m, lgtab, AMPLI_LGTAB)); // VC:3865 on top of VC:3728: p = 1 - (1 - P(s, z))
-            else if (m == 0) qv = 100.0; // z = 0: the reference's series gives P = exp(-inf) = 0, p = 0 < 1e-10
-            // m < 0 (a negative error cell, or an irregular line with RD < RD_reverse): log(z) is NaN in the reference,
-            // Q is NaN and VC:898 is false
-        }
-        const double q_other = __shfl_xor(qv, 1);
-        const bool is_call = on && strand == 0 && qv >= 5 && q_other >= 5; // VC:898 (coverage was checked before queueing)
-        // a Q within 1e-6 of the gate cannot be decided here (include/amplisolve_hip.h, AMPLI_CALL_BORDERLINE): the pair goes
-        // on the list either way, flagged, for the host to re-evaluate with the reference's own operation sequence
-        const double lo = 5.0 - AMPLI_CALL_GATE_EPS, hi = 5.0 + AMPLI_CALL_GATE_EPS;
-        const bool near_gate = on && strand == 0 && qv >= lo && q_other >= lo && (qv < hi || q_other < hi);
-        const bool emit = is_call || near_gate;
-        if (is_call) {
-            const int record = it.record_alt & 0x3FFFFFFF, alt = (it.record_alt >> 30) & 3;
-            const size_t o = (size_t)it.sample * R + record;
-            atomicOr(&mask_words[o >> 2], (1u << alt) << ((o & 3) * 8));
-        }
-        if (n_calls) { // one counter add per wave, not per call
-            const unsigned long long bal = __ballot(emit);
-            if (bal) {
-                const int lane = threadIdx.x & 63, leader = (int)__ffsll((long long)bal) - 1;
-                const unsigned cs = shard_lo + (unsigned)((blockIdx.y * gridDim.x + blockIdx.x) % shard_n); // this launch's shards of the call list
-                const long long per = capacity / AMPLI_CALL_SHARDS;
-                unsigned long long base = 0;
-                if (lane == leader) base = atomicAdd(&n_calls[cs * AMPLI_CALL_COUNTER_STRIDE], (unsigned long long)__popcll(bal));
-                base = __shfl(base, leader);
-                if (emit && calls) {
-                    const long long idx = (long long)base + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0));
-                    if (idx < per) {
-                        ampli_call c;
-                        call_fill(c, it.sample, it.record_alt & 0x3FFFFFFF, (it.record_alt >> 30) & 3, it.rd, qv, q_other, it.k_fw, it.k_bw, it.FW, it.BW,
-                                  near_gate ? AMPLI_CALL_BORDERLINE : 0);
-                        if constexpr (LOO) {
-                            ampli_loo_call lc;
-                            lc.call = c; lc.thr_fw = it.e_fw; lc.thr_bw = it.e_bw; lc.code = it.pad; lc.pad = 0;
-                            calls[(size_t)cs * per + idx] = lc;
-                        } else {
-                            calls[(size_t)cs * per + idx] = c;
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(256) void poisson_drain_kernel(
     const PcItem *__restrict__ queue, const long long queue_per_shard, const unsigned long long *__restrict__ queue_n,
     const long long R, unsigned *__restrict__ mask_words, ampli_call *__restrict__ calls, const long long capacity,
@@ -2640,21 +1882,13 @@ __global__ __launch_bounds__(256) void poisson_drain_kernel(
     drain_body<false>(queue, queue_per_shard, queue_n, R, mask_words, calls, capacity, n_calls, next_queue_n, shard_lo, shard_n, lgtab);
 }
 
-__global__ __launch_bounds__(256) void loo_drain_kernel(
-    const PcItem *__restrict__ queue, const long long queue_per_shard, const unsigned long long *__restrict__ queue_n,
-    const long long R, unsigned *__restrict__ mask_words, ampli_loo_call *__restrict__ calls, const long long capacity,
-    unsigned long long *__restrict__ n_calls, unsigned long long *__restrict__ next_queue_n, const double *__restrict__ lgtab)
-{
-    drain_body<true>(queue, queue_per_shard, queue_n, R, mask_words, calls, capacity, n_calls, next_queue_n, 0, AMPLI_CALL_SHARDS, lgtab);
-}
-
 __global__ void lgamma_table_kernel(double *t, const int n)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < n) t[i] = ampli_kf_lgamma((double)i);
 }
 
-static int ensure_lgtab(ampli_ctx *ctx)
+int ensure_lgtab(ampli_ctx *ctx)
 {
     if (ctx->d_lgtab) return AMPLI_OK;
     if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "the lgamma table would have to be built while capturing: run the sequence once first");
@@ -2671,7 +1905,7 @@ __global__ void queue_counters_reset_kernel(unsigned long long *__restrict__ qn)
 
 // The prefilter queue of a launch on `st`: at least `want` items (rounded up to whole shards), and the half of the double-buffered shard
 // counters this launch appends to (qn; the stream kernel finds it zeroed) and the half its drain resets for the next launch (qn_next)
-static int queue_prepare(ampli_ctx *ctx, AmpliQueue &Q, size_t want, hipStream_t st, long long &per, unsigned long long *&qn,
+int queue_prepare(ampli_ctx *ctx, AmpliQueue &Q, size_t want, hipStream_t st, long long &per, unsigned long long *&qn,
                          unsigned long long *&qn_next)
 {
     want = (want + AMPLI_CALL_SHARDS - 1) / AMPLI_CALL_SHARDS * AMPLI_CALL_SHARDS;
@@ -2875,692 +2109,4 @@ extern "C" int ampli_poisson_call_blocks(ampli_ctx *ctx, const int32_t *d_trecs,
     d_blocks = (const char *)d_blocks + (size_t)ctx->grp_index * slice_block_bytes(L); // [n_slices][group][block]: this batch's blocks
     return poisson_call_impl(ctx, dense_cohort(ctx, d_trecs, P, E, T, nullptr, d_ext_pos), P, (const float *)d_blocks, L,
                              (size_t)ctx->grp_size * slice_block_bytes(L), d_ref_code, cov, mode, d_call_mask, d_calls, capacity, d_n_calls, d_q, d_af);
-}
-
-// ==== leave-one-out: what the panel of normals calls in itself =========================================================================
-
-// loo_stream_kernel<LAY,IRR>: for every normal s of a resident chunk and every position p, the calling gate of VC on
-// s's records at p against the thresholds the OTHER S-1 normals give.  One lane owns one position: it loads the whole
-// cohort's sums once (snt, srd, cnt, nrec: 148 B) and, for every row, subtracts the held-out sample's own contribution -- its
-// records at p that pass the threshold gate error_reduce used (thr_gate) -- and finalises that row's S-1 table in registers
-// (fin_rates, the text round trip).  Inside the exactness envelope every addend of snt is >= 0, so every partial sum of any subset
-// is bounded by the total and exact: the difference IS the S-1 sum, in whatever order the reference would have added it.  Outside
-// the envelope that fails: flag bit 0 (the caller refuses).
-// A workgroup = 4 waves over one 64-position tile, wave w taking rows w, w + 4, ...; the per-position callable count is summed over
-// the waves in LDS (no atomics), the per-sample one takes one reduction and one atomic per (wave, row).  Survivors of the prefilter
-// go onto poisson_call's queue as PcItems carrying the raw S-1 thresholds, and loo_drain_kernel scores them.
-struct LooRec {
-    int fw[4], bw[4];
-    int FW, BW, RD;
-    bool present, big;
-};
-
-template <int LAY, bool IRR>
-__device__ __forceinline__ LooRec loo_rec(const RecView &rv, const long long P, const long long E, const int s, const long long r)
-{
-    const RawRec<LAY> raw = r < P ? rec_load_at<LAY>(rv.base + ((size_t)s * (size_t)rv.row_stride + (size_t)r) * rec_bytes(LAY))
-                                  : rec_load_at<LAY>(rv.ext + ((size_t)s * (size_t)rv.ext_stride + (size_t)(r - P)) * rec_bytes(LAY));
-    int4 r0, r1;
-    rec_decode<LAY>(raw, r0, r1);
-    LooRec o;
-    o.fw[0] = r0.x; o.fw[1] = r0.y; o.fw[2] = r0.z; o.fw[3] = r0.w;
-    o.bw[0] = r1.x; o.bw[1] = r1.y; o.bw[2] = r1.z; o.bw[3] = r1.w;
-    o.FW = r0.x + r0.y + r0.z + r0.w; // EE:1175, VC:760
-    o.BW = r1.x + r1.y + r1.z + r1.w; // EE:1176, VC:761
-    o.RD = o.FW + o.BW;
-    bool irregular = false;
-    if (IRR) { // EE:1178-1181, VC:762-765: the line's own RD column
-        const int *rdp = r < P ? rv.rd : rv.rd_ext;
-        const int rdc = rdp ? rdp[r < P ? (size_t)s * P + r : (size_t)s * E + (r - P)] : AMPLI_ABSENT;
-        if (rdc != AMPLI_ABSENT) { o.RD = rdc; irregular = true; }
-    }
-    o.present = r0.x != AMPLI_ABSENT;
-    o.big = irregular || o.RD >= AMPLI_COUNT_LIMIT; // as visit_record
-    return o;
-}
-
-template <int LAY, bool IRR>
-__global__ __launch_bounds__(256) void loo_stream_kernel(
-    const RecView rv, const long long P, const long long E, const unsigned *__restrict__ dup_off, const int n, const AccPtrs acc,
-    const float C, const int cov, const int call_cov, const unsigned char *__restrict__ ref_code, const int prefilter,
-    PcItem *__restrict__ queue, const long long queue_per_shard, unsigned long long *__restrict__ queue_n,
-    unsigned long long *__restrict__ n_calls, int *__restrict__ callable_pos, int *__restrict__ callable_sample,
-    float *__restrict__ thr_loo, int *__restrict__ env_flags, int *__restrict__ ctx_flags)
-{
-    __shared__ PcItem stage[4][PC_STAGE];
-    __shared__ int lds_callable[4][64];
-    int staged = 0; // wave-uniform
-    const int lane = threadIdx.x & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // the call-list counters are reset here: only the drain, which starts after this kernel has finished, appends to the list
-    if (n_calls && blockIdx.x == 0 && threadIdx.x < AMPLI_CALL_SHARDS) n_calls[threadIdx.x * AMPLI_CALL_COUNTER_STRIDE] = 0ull;
-    const long long p_raw = (long long)blockIdx.x * 64 + lane;
-    const bool valid = p_raw < P;
-    const long long p = valid ? p_raw : P - 1;
-    double tsnt[2][4];
-    long long tsrd[2][4];
-    int tcnt[4];
-#pragma unroll
-    for (int nt = 0; nt < 4; ++nt) {
-#pragma unroll
-        for (int st = 0; st < 2; ++st) {
-            tsnt[st][nt] = acc.snt[(st * 4 + nt) * P + p];
-            tsrd[st][nt] = acc.srd[(st * 4 + nt) * P + p];
-        }
-        tcnt[nt] = acc.cnt[nt * P + p];
-    }
-    const int tnrec = acc.nrec[p];
-    const int ref = valid ? (int)ref_code[p] : 255;
-    const long long e0 = E > 0 ? (long long)dup_off[p] : 0;
-    const int n_ext = E > 0 && valid ? (int)(dup_off[p + 1] - dup_off[p]) : 0;
-    // the record loops below run n_ext_max + 1 times in EVERY lane: the queue staging inside them is wave-wide (ballots, the
-    // wave-uniform fill count of the stage), so no lane may leave them early; a lane past its own records visits nothing
-    int n_ext_max = n_ext;
-#pragma unroll
-    for (int off = 32; off >= 1; off >>= 1) n_ext_max = max(n_ext_max, __shfl_xor(n_ext_max, off));
-    if (env_flags && wave == 0) { // the totals' exactness envelope (finalize_one's test): outside it the differences below are not the S-1 sums
-        const double limit = envelope_limit(C, cov);
-        bool bad = false;
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) bad |= !(tsnt[0][nt] < limit) || !(tsnt[1][nt] < limit);
-        if (valid && bad) atomicOr(env_flags, 1);
-    }
-    const unsigned shard = blockIdx.x % AMPLI_CALL_SHARDS;
-    int callable = 0; // this lane's callable records over this wave's rows
-    for (int s = wave; s < n; s += 4) {
-        // 1. the S-1 sums of (s, p): the totals minus s's records at p that pass the threshold gate
-        double snt[2][4];
-        long long srd[2][4];
-        int cnt[4];
-#pragma unroll
-        for (int nt = 0; nt < 4; ++nt) {
-            snt[0][nt] = tsnt[0][nt]; snt[1][nt] = tsnt[1][nt];
-            srd[0][nt] = tsrd[0][nt]; srd[1][nt] = tsrd[1][nt];
-            cnt[nt] = tcnt[nt];
-        }
-        int m = 0;       // s's present records at p: nrec' = nrec - m
-        bool any_live = false;
-        for (int j = 0; j <= n_ext_max; ++j) { // the primary record, then the extras of p (record P + e0 + j - 1)
-            const bool has = j <= n_ext;
-            LooRec a = loo_rec<LAY, IRR>(rv, P, E, s, j == 0 || !has ? p : P + e0 + j - 1);
-            a.present &= has;
-            m += a.present ? 1 : 0;
-            const bool covok = a.present && a.FW >= cov && a.BW >= cov;
-            any_live |= valid && a.present && ref <= 3 && a.FW >= call_cov && a.BW >= call_cov;
-            const unsigned qual = thr_gate(a.fw, a.bw, a.FW, a.BW, covok, a.big);
-            if (qual) {
-                const double prod_fw = (double)((float)a.FW * C), prod_bw = (double)((float)a.BW * C); // EE:1597,1599
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    if ((qual >> nt) & 1u) { // the addends of EE:1597-1606, taken out in the order they went in
-                        snt[0][nt] = snt[0][nt] - (double)a.fw[nt] - prod_fw;
-                        snt[1][nt] = snt[1][nt] - (double)a.bw[nt] - prod_bw;
-                        srd[0][nt] -= a.FW;
-                        srd[1][nt] -= a.BW;
-                        cnt[nt] -= 1;
-                    }
-                }
-            }
-        }
-        // 2. the S-1 table's thresholds: quorum, fp32 rate, NaN -> NONE, text round trip, 0.01 for NONE (finalize_one)
-        float thr[2][4] = {{0.01f, 0.01f, 0.01f, 0.01f}, {0.01f, 0.01f, 0.01f, 0.01f}}; // read only where a record is live
-        int tcode[4] = {1, 1, 1, 1};
-        if (any_live || thr_loo) {
-#pragma unroll
-            for (int nt = 0; nt < 4; ++nt) {
-                float r_fw, r_bw;
-                const unsigned char c = tcode[nt] = fin_rates(snt[0][nt], snt[1][nt], srd[0][nt], srd[1][nt], cnt[nt], tnrec - m, r_fw, r_bw);
-                thr[0][nt] = c ? 0.01f : ampli_text_roundtrip(r_fw); // EE:2680-2684 / EE:1704 -> VC:889-890
-                thr[1][nt] = c ? 0.01f : ampli_text_roundtrip(r_bw);
-                if (thr_loo && valid) {
-                    thr_loo[((size_t)s * 8 + nt) * P + p] = thr[0][nt];
-                    thr_loo[((size_t)s * 8 + 4 + nt) * P + p] = thr[1][nt];
-                }
-            }
-        }
-        // 3. VC's gate on each of s's records at p against those thresholds (poisson_stream_kernel's, per record)
-        int row_callable = 0;
-        for (int j = 0; j <= n_ext_max; ++j) {
-            const bool has = j <= n_ext;
-            const long long r = j == 0 || !has ? p : P + e0 + j - 1;
-            LooRec a = loo_rec<LAY, IRR>(rv, P, E, s, r);
-            a.present &= has;
-            const bool live = valid && a.present && ref <= 3 && a.FW >= call_cov && a.BW >= call_cov; // VC:898, VC:3290
-            row_callable += live ? 1 : 0;
-            const int d_fw = a.RD - a.BW, d_bw = a.BW; // VC:895-896
-            const bool exact = prefilter && (unsigned)a.RD < (unsigned)AMPLI_COUNT_LIMIT && a.FW >= 0 && a.BW >= 0 && d_fw >= 0;
-            const float c_fw = (float)d_fw * 0.999999f, c_bw = (float)d_bw * 0.999999f;
-            unsigned pushmask = 0;
-            if (live) {
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) { // ampli_prefilter_skip_f32: settles most pairs; what it does not skip is scored exactly
-                    const bool skip_fw = exact && (unsigned)a.fw[nt] < (unsigned)AMPLI_COUNT_LIMIT && (float)a.fw[nt] <= c_fw * ampli_effective_err(thr[0][nt]);
-                    const bool skip_bw = exact && (unsigned)a.bw[nt] < (unsigned)AMPLI_COUNT_LIMIT && (float)a.bw[nt] <= c_bw * ampli_effective_err(thr[1][nt]);
-                    if (nt != ref && !skip_fw && !skip_bw) pushmask |= 1u << nt;
-                }
-            }
-            if (__any(pushmask != 0)) {
-#pragma unroll
-                for (int nt = 0; nt < 4; ++nt) {
-                    const bool push = (pushmask >> nt) & 1;
-                    const unsigned long long bal = __ballot(push);
-                    if (bal) {
-                        const int k = __popcll(bal);
-                        if (staged + k > PC_STAGE) {
-                            pc_flush(stage[wave], staged, lane, queue, queue_per_shard, queue_n, shard, ctx_flags);
-                            staged = 0;
-                        }
-                        if (push) {
-                            PcItem it;
-                            it.sample = s; it.record_alt = (int)r | (nt << 30);
-                            it.k_fw = a.fw[nt]; it.k_bw = a.bw[nt]; it.FW = a.FW; it.BW = a.BW; it.rd = a.RD;
-                            it.e_fw = thr[0][nt]; it.e_bw = thr[1][nt]; it.pad = tcode[nt];
-                            stage[wave][staged + __builtin_amdgcn_mbcnt_hi((unsigned)(bal >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)bal, 0))] = it;
-                        }
-                        staged += k;
-                    }
-                }
-            }
-        }
-        callable += row_callable;
-        if (callable_sample) { // one reduction and one atomic per (wave, row)
-            int w = row_callable;
-#pragma unroll
-            for (int off = 32; off >= 1; off >>= 1) w += __shfl_xor(w, off);
-            if (lane == 0 && w) atomicAdd(&callable_sample[s], w);
-        }
-    }
-    if (staged) pc_flush(stage[wave], staged, lane, queue, queue_per_shard, queue_n, shard, ctx_flags);
-    if (callable_pos) {
-        lds_callable[wave][lane] = callable;
-        __syncthreads();
-        if (wave == 0 && valid) callable_pos[p] += lds_callable[0][lane] + lds_callable[1][lane] + lds_callable[2][lane] + lds_callable[3][lane];
-    }
-}
-
-extern "C" int ampli_loo_call_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_acc_table *d_acc, float C,
-                                      int32_t cov, int32_t call_cov, const uint8_t *d_ref_code, int32_t mode, uint8_t *d_call_mask,
-                                      ampli_loo_call *d_calls, int64_t capacity, unsigned long long *d_n_calls, int32_t *d_callable_pos,
-                                      int32_t *d_callable_sample, float *d_thr_loo, int32_t *d_flags)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    DevCohort co;
-    { int rc = cohort_from_records(ctx, recs, P, co); if (rc) return rc; }
-    if (P <= 0 || !d_ref_code || !d_call_mask || cov < 1 || call_cov < 1) return fail(ctx, AMPLI_E_INVALID, "loo_call: bad argument");
-    if (!acc_is_bound(d_acc) || d_acc->P != P) return fail(ctx, AMPLI_E_INVALID, "loo_call: d_acc must be an ampli_acc_bind table of P positions");
-    { int rc = check_records(ctx, co, "loo_call", co.dup_off, "dup_off"); if (rc) return rc; }
-    if (mode != AMPLI_POISSON_FULL && mode != AMPLI_POISSON_PREFILTER) return fail(ctx, AMPLI_E_INVALID, "loo_call: bad mode");
-    if (d_calls && (!d_n_calls || capacity < AMPLI_CALL_SHARDS)) return fail(ctx, AMPLI_E_INVALID, "loo_call: call list needs n_calls and capacity >= AMPLI_CALL_SHARDS");
-    if (d_n_calls && !d_calls) capacity = 0;
-    if (((uintptr_t)d_call_mask & 3) != 0) return fail(ctx, AMPLI_E_INVALID, "loo_call: call_mask must be 4-byte aligned");
-    const long long E = co.E, R = P + E;
-    const int n = co.n;
-    if (R >= (1ll << 30)) return fail(ctx, AMPLI_E_RANGE, "loo_call: P + E must be below 2^30 records per sample");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rcj = join_drain(ctx); if (rcj) return rcj; } // the queue and its counters are about to be reused
-    { int rcl = ensure_lgtab(ctx); if (rcl) return rcl; }
-    hipStream_t st = main_stream(ctx);
-    // all-scores mode queues every live (record, alt) pair: the drain's exact bound decides them all
-    // items go to shard blockIdx.x % AMPLI_CALL_SHARDS, one workgroup = one tile of 64 positions: a shard takes at most
-    // ceil(tiles / SHARDS) tiles' worth of pairs (3 alternatives of every record of the tile's positions, extras included), which is
-    // what the all-scores mode sizes for; ampli_set_queue_items raises either mode's size
-    const unsigned tiles = (unsigned)((P + 63) / 64);
-    const size_t shard_tiles = (tiles + AMPLI_CALL_SHARDS - 1) / AMPLI_CALL_SHARDS;
-    size_t want = mode == AMPLI_POISSON_FULL ? (size_t)AMPLI_CALL_SHARDS * shard_tiles * 3 * ((size_t)n * 64 + (size_t)n * (size_t)E)
-                                             : (size_t)std::max<long long>(1 << 16, (long long)n * R / 4);
-    if (ctx->queue_min_items) want = std::max(want, ctx->queue_min_items + (size_t)AMPLI_CALL_SHARDS * shard_tiles * 3 * 64 * (size_t)n);
-    long long per;
-    unsigned long long *qn, *qn_next;
-    { int rcq = queue_prepare(ctx, ctx->lanes[0].q, want, st, per, qn, qn_next); if (rcq) return rcq; }
-    HIP_TRY(ctx, hipMemsetAsync(d_call_mask, 0, ((size_t)n * (size_t)R + 3) / 4 * 4, st));
-    with_layout(co.layout, [&](auto L) {
-        with_bool(co.rv.rd || co.rv.rd_ext, [&](auto IRR) {
-            hipLaunchKernelGGL((loo_stream_kernel<L, IRR>), dim3(tiles), dim3(256), 0, st, co.rv, (long long)P, E, co.dup_off, n, to_ptrs(d_acc), C,
-                               (int)cov, (int)call_cov, d_ref_code, mode == AMPLI_POISSON_PREFILTER ? 1 : 0, (PcItem *)ctx->lanes[0].q.items, per, qn,
-                               d_n_calls, d_callable_pos, d_callable_sample, d_thr_loo, d_flags, ctx->d_flags);
-        });
-    });
-    { int rc = check_launch(ctx, "loo_stream_kernel"); if (rc) return rc; }
-    const unsigned dgy = (unsigned)(ctx->pc_drain_blocks > 0 ? ctx->pc_drain_blocks
-                                                             : std::min<long long>(1024, std::max<long long>(16, (long long)n * R / 300000)));
-    hipLaunchKernelGGL(loo_drain_kernel, dim3(AMPLI_CALL_SHARDS, dgy), dim3(256), 0, st, (const PcItem *)ctx->lanes[0].q.items, per, qn, (long long)R,
-                       (unsigned *)d_call_mask, d_calls, (long long)capacity, d_n_calls, qn_next, (const double *)ctx->d_lgtab);
-    return check_launch(ctx, "loo_drain_kernel");
-}
-
-// ==== detection limits: the smallest alternative counts the calling gate would pass, per record and base ===============================
-
-// limit_pairs_kernel<LAY,IRR>: one lane per (record, alternative base) pair, a workgroup = 3 waves over 64 records of one
-// sample.  A pair is two searches (forward, reverse; ampli_limit_init / ampli_limit_step of ampli_math.h), and a search is 1 to ~26
-// scorer evaluations of ~1000 dependent fp64 instructions each, so a wave runs as long as the longest of its lanes.  The lane therefore
-// runs ONE loop whose body is one evaluation, and moves from its forward to its reverse strand inside it: a wave lasts the largest SUM
-// of two searches of its lanes, not the sum of the two largest.  Three lanes per record, not four: the reference base has no search
-// and a fourth lane would idle through every evaluation of its wave; lane 0 of a record writes the reference base's cell as well.
-// The lanes of a wave hold consecutive (record, base) cells, so their stores are one contiguous run of 8-byte and of 1-byte elements.
-// Counters: one ballot per counter and wave, summed over the workgroup in LDS, one atomic per workgroup and non-zero counter.
-constexpr int LIM_RECS = 64, LIM_THREADS = 3 * LIM_RECS;
-
-template <int LAY, bool IRR>
-__global__ __launch_bounds__(LIM_THREADS) void limit_pairs_kernel(
-    const RecView rv, const long long P, const long long E, const unsigned *__restrict__ ext_pos, const float *__restrict__ thr,
-    const unsigned char *__restrict__ ref_code, const int cov, const float *__restrict__ levels, const int n_levels,
-    int2 *__restrict__ min_reads, unsigned char *__restrict__ status, unsigned long long *__restrict__ counts,
-    const double *__restrict__ lgtab, unsigned long long *__restrict__ stats)
-{
-    constexpr int RB = rec_bytes(LAY);
-    __shared__ unsigned cnt[AMPLI_LIMIT_COUNTERS + AMPLI_LIMIT_MAX_LEVELS];
-    __shared__ unsigned ev[3]; // strands searched, evaluations, the most of one strand
-    const int tid = threadIdx.x;
-    if (tid < AMPLI_LIMIT_COUNTERS + AMPLI_LIMIT_MAX_LEVELS) cnt[tid] = 0;
-    if (tid < 3) ev[tid] = 0;
-    __syncthreads();
-    const long long R = P + E;
-    const int rl = tid / 3, a = tid - 3 * rl;
-    const long long r = (long long)blockIdx.x * LIM_RECS + rl;
-    const int t = blockIdx.y;
-    const bool in_range = r < R; // lanes past the end keep company at the barrier
-    int code = AMPLI_LIMIT_ABSENT, nt = a, mf = 0, mb = 0;
-    bool recheck = false, called = false, noref_line = false, second_cell = false;
-    int second_code = AMPLI_LIMIT_ABSENT, second_nt = 3;
-    float min_af = 0.0f;
-    unsigned n_strands = 0, n_evals = 0, max_evals = 0;
-    if (in_range) {
-        const long long p = r < P ? r : (long long)ext_pos[r - P];
-        const int ref = ref_code[p];
-        const char *q = r < P ? rv.base + ((size_t)t * (size_t)rv.row_stride + (size_t)r) * RB
-                              : rv.ext + ((size_t)t * (size_t)rv.ext_stride + (size_t)(r - P)) * RB;
-        int4 r0, r1;
-        rec_decode<LAY>(rec_load_at<LAY>(q), r0, r1);
-        const bool present = r0.x != AMPLI_ABSENT;
-        second_cell = a == 0;
-        if (present && ref > 3) {
-            code = second_code = AMPLI_LIMIT_NOREF; // VC:3290
-            noref_line = a == 0;
-        } else if (present) {
-            nt = a + (a >= ref ? 1 : 0);
-            second_code = AMPLI_LIMIT_REF; second_nt = ref;
-            const int fw[4] = {r0.x, r0.y, r0.z, r0.w};
-            const int bw[4] = {r1.x, r1.y, r1.z, r1.w};
-            const int FW = fw[0] + fw[1] + fw[2] + fw[3]; // VC:760
-            const int BW = bw[0] + bw[1] + bw[2] + bw[3]; // VC:761
-            int RD = FW + BW;
-            if constexpr (IRR) { // the RD column of lines where it is not A+C+G+T (VC:762-765)
-                const int *rdp = r < P ? rv.rd : rv.rd_ext;
-                const int rdc = rdp ? rdp[r < P ? (size_t)t * P + r : (size_t)t * E + (r - P)] : AMPLI_ABSENT;
-                if (rdc != AMPLI_ABSENT) RD = rdc;
-            }
-            const float th_fw = thr[(size_t)nt * P + p], th_bw = thr[(size_t)(4 + nt) * P + p]; // VC:887-890
-            int k_fw = 0, k_bw = 0;
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { if (j == nt) { k_fw = fw[j]; k_bw = bw[j]; } }
-            if (FW < cov || BW < cov) code = AMPLI_LIMIT_LOWDEPTH; // VC:898
-            else if (th_fw == -1 || th_bw == -1) code = AMPLI_LIMIT_NOESTIMATE;
-            else {
-                // the two searches in one loop: a pass of the body is one scorer evaluation, whichever strand the lane is at
-                ampli_limit_search s;
-                ampli_limit_init(&s, RD - BW, th_fw, FW); // VC:895: forward depth is RD - RD_reverse
-                int strand = 0, r_fw = AMPLI_LIMK_PENDING, r_bw = AMPLI_LIMK_PENDING;
-                for (;;) {
-                    if (s.res != AMPLI_LIMK_PENDING) {
-                        if (s.evals) { ++n_strands; n_evals += (unsigned)s.evals; max_evals = max(max_evals, (unsigned)s.evals); }
-                        if (strand == 0) {
-                            r_fw = s.res;
-                            if (r_fw <= 0) break; // no forward count, or not decided here: the reverse strand changes nothing
-                            strand = 1;
-                            ampli_limit_init(&s, BW, th_bw, BW); // VC:896
-                            continue;
-                        }
-                        r_bw = s.res;
-                        break;
-                    }
-                    ampli_limit_step(&s, lgtab, AMPLI_LGTAB);
-                }
-                if (r_fw == AMPLI_LIMK_RECHECK || r_bw == AMPLI_LIMK_RECHECK) recheck = true;
-                else if (r_fw == AMPLI_LIMK_UNREACHABLE || r_bw == AMPLI_LIMK_UNREACHABLE) {
-                    code = AMPLI_LIMIT_UNREACHABLE;
-                    if (RD - BW <= 0 && k_fw > 0) {
-                        // an own-RD line without forward depth has no limit, but the reference's gate still scores it (a mean of 0 gives
-                        // p = 0, Q = 100): the called bit is whatever the literal scorer says, as in poisson_call
-                        const double q_fw = ampli_poisson_score(k_fw, RD - BW, th_fw), q_bw = ampli_poisson_score(k_bw, BW, th_bw);
-                        const double lo = 5.0 - AMPLI_CALL_GATE_EPS, hi = 5.0 + AMPLI_CALL_GATE_EPS;
-                        called = q_fw >= 5 && q_bw >= 5;
-                        if (q_fw >= lo && q_bw >= lo && (q_fw < hi || q_bw < hi)) recheck = true;
-                    }
-                }
-                else {
-                    code = AMPLI_LIMIT_OK;
-                    mf = r_fw; mb = r_bw;
-                    called = k_fw >= mf && k_bw >= mb; // Q rises with the count: the gate on the observed counts
-                    min_af = (float)(mf + mb) / (float)RD; // as VC:814-817 forms an AF
-                }
-            }
-        }
-        const size_t o = ((size_t)t * (size_t)R + (size_t)r) * 4;
-        min_reads[o + nt] = make_int2(mf, mb);
-        status[o + nt] = recheck ? (unsigned char)AMPLI_LIMIT_RECHECK : (unsigned char)(code | (called ? AMPLI_LIMIT_CALLED : 0));
-        if (second_cell) {
-            min_reads[o + second_nt] = make_int2(0, 0);
-            status[o + second_nt] = (unsigned char)second_code;
-        }
-    }
-    const bool pair = in_range && !recheck;
-    const bool lane0 = (tid & 63) == 0;
-    auto tally = [&](const int slot, const bool pred) { // one LDS add per wave
-        const unsigned n = (unsigned)__popcll(__ballot(pred));
-        if (lane0 && n) atomicAdd(&cnt[slot], n);
-    };
-    tally(0, noref_line);
-    tally(1, pair && code == AMPLI_LIMIT_OK);
-    tally(2, pair && code == AMPLI_LIMIT_LOWDEPTH);
-    tally(3, pair && code == AMPLI_LIMIT_NOESTIMATE);
-    tally(4, pair && code == AMPLI_LIMIT_UNREACHABLE);
-    tally(5, recheck);
-    for (int l = 0; l < n_levels; ++l) tally(AMPLI_LIMIT_COUNTERS + l, pair && code == AMPLI_LIMIT_OK && min_af <= levels[l]);
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        n_strands += __shfl_xor(n_strands, d);
-        n_evals += __shfl_xor(n_evals, d);
-        max_evals = max(max_evals, __shfl_xor(max_evals, d));
-    }
-    if (lane0 && n_strands) { atomicAdd(&ev[0], n_strands); atomicAdd(&ev[1], n_evals); atomicMax(&ev[2], max_evals); }
-    __syncthreads();
-    const int nc = AMPLI_LIMIT_COUNTERS + n_levels;
-    if (tid < nc && cnt[tid]) atomicAdd(&counts[(size_t)t * nc + tid], (unsigned long long)cnt[tid]);
-    if (tid == 0 && ev[0]) { atomicAdd(&stats[0], (unsigned long long)ev[0]); atomicAdd(&stats[1], (unsigned long long)ev[1]); atomicMax(&stats[2], (unsigned long long)ev[2]); }
-}
-
-static int ensure_limit_stats(ampli_ctx *ctx)
-{
-    if (ctx->d_limit_stats) return AMPLI_OK;
-    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "the limit counters would have to be allocated while capturing: run the sequence once first");
-    if (hipMalloc((void **)&ctx->d_limit_stats, 3 * sizeof(unsigned long long)) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "limit counters hipMalloc failed");
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_limit_stats, 0, 3 * sizeof(unsigned long long), main_stream(ctx)));
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_limit_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, const float *d_thr, const uint8_t *d_ref_code,
-                                   int32_t cov, const float *d_levels, int32_t n_levels, int32_t *d_min_reads, uint8_t *d_status,
-                                   int64_t *d_counts)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    DevCohort co;
-    { int rc = cohort_from_records(ctx, trecs, P, co); if (rc) return rc; }
-    if (P <= 0 || !d_thr || !d_ref_code || cov < 1 || !d_min_reads || !d_status || !d_counts)
-        return fail(ctx, AMPLI_E_INVALID, "limit_records: bad argument (P > 0, thr, ref_code, coverage_cutoff >= 1 and the three outputs are required)");
-    if (n_levels < 0 || n_levels > AMPLI_LIMIT_MAX_LEVELS || (n_levels > 0 && !d_levels))
-        return fail(ctx, AMPLI_E_INVALID, "limit_records: n_levels must be 0 .. 8, with d_levels when it is not 0");
-    { int rc = check_records(ctx, co, "limit_records", co.ext_pos, "ext_pos"); if (rc) return rc; }
-    if (((uintptr_t)d_min_reads & 7) != 0 || ((uintptr_t)d_counts & 7) != 0)
-        return fail(ctx, AMPLI_E_INVALID, "limit_records: min_reads and counts must be 8-byte aligned");
-    const long long E = co.E, R = P + E;
-    if (R >= (1ll << 30)) return fail(ctx, AMPLI_E_RANGE, "limit_records: P + E must be below 2^30 records per sample");
-    if (co.n > 65535) return fail(ctx, AMPLI_E_RANGE, "limit_records: more than 65535 samples in one call (grid limit); split the cohort");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rcl = ensure_lgtab(ctx); if (rcl) return rcl; }
-    { int rcs = ensure_limit_stats(ctx); if (rcs) return rcs; }
-    const dim3 grid((unsigned)((R + LIM_RECS - 1) / LIM_RECS), (unsigned)co.n);
-    with_layout(co.layout, [&](auto L) {
-        with_bool(co.rv.rd || co.rv.rd_ext, [&](auto IRR) {
-            hipLaunchKernelGGL((limit_pairs_kernel<L, IRR>), grid, dim3(LIM_THREADS), 0, main_stream(ctx), co.rv, (long long)P, E, co.ext_pos, d_thr,
-                               d_ref_code, (int)cov, d_levels, (int)n_levels, (int2 *)d_min_reads, d_status, (unsigned long long *)d_counts,
-                               (const double *)ctx->d_lgtab, ctx->d_limit_stats);
-        });
-    });
-    return check_launch(ctx, "limit_pairs_kernel");
-}
-
-extern "C" int ampli_limit_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!out) return fail(ctx, AMPLI_E_INVALID, "limit_stats: out is required");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    out[0] = out[1] = out[2] = 0;
-    if (!ctx->d_limit_stats) return AMPLI_OK;
-    hipStream_t st = main_stream(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_limit_stats, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (reset) HIP_TRY(ctx, hipMemsetAsync(ctx->d_limit_stats, 0, 3 * sizeof(unsigned long long), st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return AMPLI_OK;
-}
-
-// ==== detection power: the probability that the gate passes at given allele fractions, and the fraction at which it reaches a confidence =
-
-// limit_power_kernel<LAY>: one lane per cell (record, base), a workgroup = 4 waves over 64 records of one sample, so the
-// lanes of a wave hold 64 consecutive cells: the LoD store is one contiguous run of floats; a level's power store has a stride of
-// n_levels floats between neighbouring lanes and is issued where the lane finishes that level.  A lane whose cell is OK owes two
-// binomial tails per level and two per step of the root search, each a closed-form first term and a sum of a few to a few thousand
-// further ones (ampli_math.h).  A wave lasts as long as its longest lane, so the lane runs ONE loop whose body is one unit of that work
-// (ampli_power_advance: a tail's start if one is due, one run of AMPLI_TAIL_RUN terms, the change of strand when the run ends the tail)
-// and walks through its levels and its search inside it.  Lanes whose tails all fit one run stay in step, tail by tail; a lane with a
-// longer tail falls behind by a trip per further run, and from then on a trip of the wave pays the start of some lanes AND the run of
-// others.  Nothing is indexed at run time but global memory: no scratch.  Counters as limit_pairs_kernel: one ballot per counter and
-// wave, summed in LDS, one atomic per workgroup and non-zero counter; the work counters are summed in 64 bits from the wave on (a lane's
-// own stay below 2^32: at most 208 tails of at most 2^19 terms).
-constexpr int PWR_RECS = 64, PWR_THREADS = 4 * PWR_RECS;
-
-template <int LAY>
-__global__ __launch_bounds__(PWR_THREADS) void limit_power_kernel(
-    const RecView rv, const long long P, const long long E, const int2 *__restrict__ min_reads, const unsigned char *__restrict__ status,
-    const float *__restrict__ levels, const int n_levels, const double conf, float *__restrict__ power, float *__restrict__ lod,
-    unsigned long long *__restrict__ counts, unsigned long long *__restrict__ stats)
-{
-    constexpr int RB = rec_bytes(LAY);
-    __shared__ unsigned cnt[1 + AMPLI_POWER_MAX_LEVELS];
-    __shared__ unsigned long long ev[3]; // tails, terms, the most terms of one tail
-    const int tid = threadIdx.x;
-    if (tid < 1 + AMPLI_POWER_MAX_LEVELS) cnt[tid] = 0;
-    if (tid < 3) ev[tid] = 0;
-    __syncthreads();
-    const long long R = P + E;
-    const int rl = tid >> 2, nt = tid & 3;
-    const long long r = (long long)blockIdx.x * PWR_RECS + rl;
-    const int t = blockIdx.y;
-    const bool in_range = r < R; // lanes past the end keep company at the barrier
-    const size_t cell = ((size_t)t * (size_t)R + (size_t)(in_range ? r : 0)) * 4 + nt;
-    bool ok = false;
-    unsigned pass = 0; // bit l: power(levels[l]) >= conf
-    float lod_out = 0.0f;
-    unsigned n_tails = 0, n_terms = 0, max_terms = 0;
-    if (in_range) {
-        const unsigned st = status[cell];
-        int FW = 0, BW = 0;
-        int2 mr = make_int2(0, 0);
-        if ((st & (7u | AMPLI_LIMIT_RECHECK)) == AMPLI_LIMIT_OK) {
-            mr = min_reads[cell];
-            const char *q = r < P ? rv.base + ((size_t)t * (size_t)rv.row_stride + (size_t)r) * RB
-                                  : rv.ext + ((size_t)t * (size_t)rv.ext_stride + (size_t)(r - P)) * RB;
-            int4 r0, r1;
-            rec_decode<LAY>(rec_load_at<LAY>(q), r0, r1);
-            if (r0.x != AMPLI_ABSENT) {
-                FW = r0.x + r0.y + r0.z + r0.w; // VC:760
-                BW = r1.x + r1.y + r1.z + r1.w; // VC:761
-            }
-            ok = mr.x >= 1 && mr.y >= 1 && mr.x <= FW && mr.y <= BW;
-        }
-        if (ok) {
-            ampli_power_eval e;
-            ampli_lod_search s;
-            ampli_power_begin(&e, FW, mr.x, BW, mr.y);
-            int l = 0; // the level in hand; n_levels: the root search
-            bool go = true;
-            if (n_levels > 0) ampli_power_at(&e, (double)levels[0]);
-            else if (lod) ampli_power_at(&e, ampli_lod_begin(&s, FW, mr.x, BW, mr.y, conf));
-            else go = false;
-            while (go) {
-                if (!ampli_power_advance(&e)) continue;
-                if (l < n_levels) {
-                    if (power) power[cell * (size_t)n_levels + l] = (float)e.pw;
-                    pass |= (e.pw >= conf ? 1u : 0u) << l;
-                    ++l;
-                    if (l < n_levels) ampli_power_at(&e, (double)levels[l]);
-                    else if (lod) ampli_power_at(&e, ampli_lod_begin(&s, FW, mr.x, BW, mr.y, conf));
-                    else go = false;
-                } else {
-                    const double v = ampli_lod_update(&s, e.pw, e.dpw);
-                    if (s.done) { lod_out = (float)v; go = false; }
-                    else ampli_power_at(&e, v);
-                }
-            }
-            n_tails = e.n_tails; n_terms = e.n_terms; max_terms = e.max_terms;
-        } else if (power) {
-            for (int l = 0; l < n_levels; ++l) power[cell * (size_t)n_levels + l] = 0.0f;
-        }
-        if (lod) lod[cell] = lod_out;
-    }
-    const bool lane0 = (tid & 63) == 0;
-    auto tally = [&](const int slot, const bool pred) { // one LDS add per wave
-        const unsigned n = (unsigned)__popcll(__ballot(pred));
-        if (lane0 && n) atomicAdd(&cnt[slot], n);
-    };
-    tally(0, ok);
-    for (int l = 0; l < n_levels; ++l) tally(1 + l, (pass >> l) & 1u);
-    unsigned long long w_tails = n_tails, w_terms = n_terms, w_max = max_terms;
-#pragma unroll
-    for (int d = 32; d > 0; d >>= 1) {
-        w_tails += __shfl_xor(w_tails, d);
-        w_terms += __shfl_xor(w_terms, d);
-        w_max = max(w_max, __shfl_xor(w_max, d));
-    }
-    if (lane0 && w_tails) { atomicAdd(&ev[0], w_tails); atomicAdd(&ev[1], w_terms); atomicMax(&ev[2], w_max); }
-    __syncthreads();
-    const int nc = 1 + n_levels;
-    if (tid < nc && cnt[tid]) atomicAdd(&counts[(size_t)t * nc + tid], (unsigned long long)cnt[tid]);
-    if (tid == 0 && ev[0]) { atomicAdd(&stats[0], ev[0]); atomicAdd(&stats[1], ev[1]); atomicMax(&stats[2], ev[2]); }
-}
-
-static int ensure_power_stats(ampli_ctx *ctx)
-{
-    if (ctx->d_power_stats) return AMPLI_OK;
-    if (is_capturing(ctx)) return fail(ctx, AMPLI_E_INVALID, "the power counters would have to be allocated while capturing: run the sequence once first");
-    if (hipMalloc((void **)&ctx->d_power_stats, 3 * sizeof(unsigned long long)) != hipSuccess) return fail(ctx, AMPLI_E_NOMEM, "power counters hipMalloc failed");
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_power_stats, 0, 3 * sizeof(unsigned long long), main_stream(ctx)));
-    return AMPLI_OK;
-}
-
-extern "C" int ampli_power_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, const int32_t *d_min_reads, const uint8_t *d_status,
-                                   const float *d_levels, int32_t n_levels, float confidence, float *d_power, float *d_lod, int64_t *d_counts)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!trecs || P <= 0 || !d_min_reads || !d_status || !d_counts || n_levels < 0 || n_levels > AMPLI_POWER_MAX_LEVELS || (n_levels > 0 && !d_levels) ||
-        !(confidence >= 0.5f && confidence <= 0.99f))
-        return fail(ctx, AMPLI_E_INVALID, "power_records: bad argument (records, P > 0, min_reads, status and counts are required; n_levels 0 .. 8, with "
-                                          "d_levels when it is not 0; confidence in [0.5, 0.99])");
-    DevCohort co;
-    { int rc = cohort_from_records(ctx, trecs, P, co); if (rc) return rc; }
-    { int rc = check_records(ctx, co, "power_records", nullptr, nullptr); if (rc) return rc; } // a cell needs its record only: no index of the extras
-    if (((uintptr_t)d_min_reads & 7) != 0 || ((uintptr_t)d_counts & 7) != 0)
-        return fail(ctx, AMPLI_E_INVALID, "power_records: min_reads and counts must be 8-byte aligned");
-    const long long E = co.E, R = P + E;
-    if (R >= (1ll << 30)) return fail(ctx, AMPLI_E_RANGE, "power_records: P + E must be below 2^30 records per sample");
-    if (co.n > 65535) return fail(ctx, AMPLI_E_RANGE, "power_records: more than 65535 samples in one call (grid limit); split the cohort");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rcs = ensure_power_stats(ctx); if (rcs) return rcs; }
-    const dim3 grid((unsigned)((R + PWR_RECS - 1) / PWR_RECS), (unsigned)co.n);
-    with_layout(co.layout, [&](auto L) {
-        hipLaunchKernelGGL((limit_power_kernel<L>), grid, dim3(PWR_THREADS), 0, main_stream(ctx), co.rv, (long long)P, E, (const int2 *)d_min_reads, d_status,
-                           d_levels, (int)n_levels, (double)confidence, d_power, d_lod, (unsigned long long *)d_counts, ctx->d_power_stats);
-    });
-    return check_launch(ctx, "limit_power_kernel");
-}
-
-extern "C" int ampli_power_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset)
-{
-    if (!ctx) return AMPLI_E_INVALID;
-    if (!out) return fail(ctx, AMPLI_E_INVALID, "power_stats: out is required");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    out[0] = out[1] = out[2] = 0;
-    if (!ctx->d_power_stats) return AMPLI_OK;
-    hipStream_t st = main_stream(ctx);
-    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->d_power_stats, 3 * sizeof(uint64_t), hipMemcpyDeviceToHost, st));
-    if (reset) HIP_TRY(ctx, hipMemsetAsync(ctx->d_power_stats, 0, 3 * sizeof(unsigned long long), st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    return AMPLI_OK;
-}
-
-// ==== auxiliary and synthetic: scorer checks, synthetic panels =========================================================================
-
-__global__ void score_dense_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, const double *lgtab)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) q[i] = ampli_poisson_score_dense(k[i], rd[i], err[i], lgtab, AMPLI_LGTAB);
-}
-
-__global__ void score_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, double *pv)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    if (q) q[i] = ampli_poisson_score(k[i], rd[i], err[i]);
-    if (pv) pv[i] = err[i] == -1 ? -1.0 : ampli_poisson_p(k[i], rd[i], err[i]);
-}
-
-__global__ void roundtrip_batch_kernel(const float *in, const long long n, float *out)
-{
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) out[i] = ampli_text_roundtrip(in[i]);
-}
-
-__global__ void synth_fill_kernel(int4 *recs, const long long P, const int n_samples, const int first_sample,
-                                  const unsigned long long seed, const int depth, const int tumour)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    const int s = blockIdx.y;
-    if (p >= P || s >= n_samples) return;
-    int rec[8];
-    ampli_synth_record(seed, (uint64_t)p, (uint64_t)(first_sample + s), depth, tumour, rec);
-    const size_t o = ((size_t)s * P + p) * 2;
-    recs[o] = make_int4(rec[0], rec[1], rec[2], rec[3]);
-    recs[o + 1] = make_int4(rec[4], rec[5], rec[6], rec[7]);
-}
-
-__global__ void synth_ref_kernel(unsigned char *ref, const long long P, const unsigned long long seed)
-{
-    const long long p = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p < P) ref[p] = (unsigned char)ampli_synth_ref_base(seed, (uint64_t)p);
-}
-
-extern "C" int ampli_score_batch(ampli_ctx *ctx, const int32_t *d_k, const int32_t *d_rd, const float *d_err, int64_t n,
-                                 double *d_q, double *d_p)
-{
-    if (!ctx || !d_k || !d_rd || !d_err || n <= 0) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(score_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, main_stream(ctx), d_k, d_rd, d_err,
-                       (long long)n, d_q, d_p);
-    return check_launch(ctx, "score_batch_kernel");
-}
-
-extern "C" int ampli_score_dense_batch(ampli_ctx *ctx, const int32_t *d_k, const int32_t *d_rd, const float *d_err, int64_t n, double *d_q)
-{
-    if (!ctx || !d_k || !d_rd || !d_err || !d_q || n <= 0) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    { int rcl = ensure_lgtab(ctx); if (rcl) return rcl; }
-    hipLaunchKernelGGL(score_dense_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, main_stream(ctx), d_k, d_rd, d_err,
-                       (long long)n, d_q, (const double *)ctx->d_lgtab);
-    return check_launch(ctx, "score_dense_batch_kernel");
-}
-
-extern "C" int ampli_roundtrip_batch(ampli_ctx *ctx, const float *d_in, int64_t n, float *d_out)
-{
-    if (!ctx || !d_in || !d_out || n <= 0) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(roundtrip_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, main_stream(ctx), d_in, (long long)n, d_out);
-    return check_launch(ctx, "roundtrip_batch_kernel");
-}
-
-extern "C" int ampli_synth_fill(ampli_ctx *ctx, int32_t *d_recs, int64_t P, int32_t n_samples, int32_t first_sample,
-                                uint64_t seed, int32_t depth, int32_t tumour)
-{
-    if (!ctx || !d_recs || P <= 0 || n_samples <= 0 || n_samples > 65535 || depth <= 0) return AMPLI_E_INVALID; // n_samples = gridDim.y
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)n_samples), dim3(256), 0, main_stream(ctx),
-                       (int4 *)d_recs, (long long)P, (int)n_samples, (int)first_sample, (unsigned long long)seed, (int)depth, (int)tumour);
-    return check_launch(ctx, "synth_fill_kernel");
-}
-
-extern "C" int ampli_synth_ref(ampli_ctx *ctx, uint8_t *d_ref_code, int64_t P, uint64_t seed)
-{
-    if (!ctx || !d_ref_code || P <= 0) return AMPLI_E_INVALID;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipLaunchKernelGGL(synth_ref_kernel, dim3((unsigned)((P + 255) / 256)), dim3(256), 0, main_stream(ctx), d_ref_code, (long long)P,
-                       (unsigned long long)seed);
-    return check_launch(ctx, "synth_ref_kernel");
 }

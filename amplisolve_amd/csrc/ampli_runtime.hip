@@ -1,7 +1,7 @@
 // amplisolve_amd/csrc/ampli_runtime.hip -- the context and runtime plumbing of libamplisolve_hip.so: context create / destroy, error
 // strings, device probe, the asynchronous drain's join, position ranges on concurrent streams, hipGraph capture, memory, copies,
-// events and the ampli_set_* knobs.  The kernels and their launchers are in ampli_kernels.hip; ampli_internal.h declares what the
-// launchers use of this file.
+// events and the ampli_set_* knobs.  The kernels and their launchers are in ampli_kernels.hip and the units
+// its header comment maps; ampli_internal.h declares what the launchers use of this file.
 #include <cstdio>
 #include <algorithm>
 #include <new>

@@ -22,7 +22,7 @@ P, S = 1500, 23
 
 
 def host_fold(acc, gathered, world):
-    """numpy twin of ampli_gm_merge (csrc/ampli_kernels.hip gm_merge_kernel)."""
+    """numpy twin of ampli_gm_merge (csrc/ampli_exchange.hip gm_merge_kernel)."""
     _, gm_off, gm_bytes = table_regions(acc.P)
     n4 = 4 * acc.P
     offs = [0, None, acc.struct.gm_first_af - acc.struct.gm_n, acc.struct.gm_rest - acc.struct.gm_n]  # gm_first is not exchanged

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Per-kernel register / scratch / LDS figures of the gfx950 code object of one .hip file (cross-compiles; no GPU needed).
-# usage: tools/kstat.sh [file.hip] [name filter]     e.g. tools/kstat.sh amplisolve_amd/csrc/ampli_kernels.hip error_reduce
+# usage: tools/kstat.sh [file.hip] [name filter]     e.g. tools/kstat.sh amplisolve_amd/csrc/ampli_loo.hip loo_stream   (any unit of csrc/; default: ampli_kernels.hip)
 set -e
 SRC=${1:-amplisolve_amd/csrc/ampli_kernels.hip}
 FILTER=${2:-.}
