@@ -141,6 +141,8 @@ HIP_SYMBOLS = {
     "ampli_limit_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), i32]),
     "ampli_power_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, vp, i32, f32, vp, vp, vp]),
     "ampli_power_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), i32]),
+    "ampli_dispersion_records": (C.c_int, [vp, C.POINTER(Records), i64, C.POINTER(AccTable), i32, vp, vp, i32, vp, vp, vp]),
+    "ampli_dispersion_finalize": (C.c_int, [vp, i64, C.POINTER(AccTable), vp, vp, C.c_double, vp, vp, vp, vp]),
 }
 
 class HostShard(C.Structure):
@@ -208,6 +210,7 @@ HOST_SYMBOLS = {
     "ampli_host_limit_search": (i32, [i32, f32, i32, C.POINTER(i32)]),
     "ampli_host_binom_tail": (C.c_double, [i32, i32, C.c_double, C.POINTER(i32)]),
     "ampli_host_power_pair": (C.c_int, [i32, i32, i32, i32, C.POINTER(f32), i32, f32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
+    "ampli_host_dispersion_cell_batch": (None, [vp, vp, vp, vp, vp, i64, C.c_double, vp, vp, vp]),
 }
 
 _hip = None

@@ -21,6 +21,8 @@ CALL_COUNTER_WORDS = CALL_SHARDS * CALL_COUNTER_STRIDE
 LIMIT_OK, LIMIT_REF, LIMIT_NOREF, LIMIT_LOWDEPTH, LIMIT_NOESTIMATE, LIMIT_UNREACHABLE, LIMIT_ABSENT = range(7)
 LIMIT_CALLED, LIMIT_RECHECK = 0x40, 0x80
 LIMIT_COUNTERS = 6
+# AMPLI_DISPERSION_* (Context.panel_dispersion)
+DISPERSION_OK, DISPERSION_FEW, DISPERSION_HIGH = 0, 1, 0x40
 
 
 def _ptr(t):
@@ -376,6 +378,47 @@ class Context:
         out = (C.c_uint64 * 3)()
         self._check(self.lib.ampli_power_stats(self.h, out, int(reset)))
         return int(out[0]), int(out[1]), int(out[2])
+
+    def dispersion_records(self, rec: Records, P: int, acc0: Acc, cov: int, x2, rinv, accumulate: bool = False, sample_x2=None,
+                           sample_expect=None, sample_terms=None):
+        """One resident chunk into the dispersion planes (ampli_dispersion_records): x2 / rinv float64 [2, 4, P] are overwritten or,
+        with accumulate, added to; the three sample arrays (float64, float64, int64 [n]) are overwritten, or all None."""
+        self._check(self.lib.ampli_dispersion_records(self.h, C.byref(rec), P, C.byref(acc0.struct), cov, _ptr(x2), _ptr(rinv), int(bool(accumulate)),
+                                                      _ptr(sample_x2), _ptr(sample_expect), _ptr(sample_terms)))
+
+    def dispersion_finalize(self, P: int, acc0: Acc, x2, rinv, z_cutoff: float, z, phi, status, counts):
+        """z (float64), phi (float32) and status (uint8), each [2, 4, P], from the summed planes (ampli_dispersion_finalize); counts int64
+        [4] is added to."""
+        self._check(self.lib.ampli_dispersion_finalize(self.h, P, C.byref(acc0.struct), _ptr(x2), _ptr(rinv), float(z_cutoff), _ptr(z), _ptr(phi),
+                                                       _ptr(status), _ptr(counts)))
+
+    def panel_dispersion(self, chunks, P: int, acc0: Acc, cov: int = 100, z_cutoff: float = 4.0, samples: bool = True):
+        """Per-position dispersion of a panel of normals and per-normal outlier scores.  chunks: the Records of the resident
+        cohort in visit order; acc0: the WHOLE cohort's table reduced with C_value = 0 and the same cov (error_reduce_records over every
+        chunk, summary=True is enough).  Returns x2, rinv, z (float64), phi (float32), status (uint8: DISPERSION_OK / _FEW in bits 0-2,
+        DISPERSION_HIGH where z >= z_cutoff), each [2, 4, P]; counts int64 [4] (cells OK, FEW, HIGH, positions with a HIGH cell); and,
+        with samples, sample_x2, sample_expect (float64) and sample_terms (int64) over all normals in visit order."""
+        import torch
+
+        d = self.device
+        x2 = torch.empty((2, 4, P), dtype=torch.float64, device=d)
+        rinv = torch.empty((2, 4, P), dtype=torch.float64, device=d)
+        S = sum(r.n_samples for r in chunks)
+        sx = torch.empty((S,), dtype=torch.float64, device=d) if samples else None
+        se = torch.empty((S,), dtype=torch.float64, device=d) if samples else None
+        stm = torch.empty((S,), dtype=torch.int64, device=d) if samples else None
+        lo = 0
+        for i, rec in enumerate(chunks):
+            hi = lo + rec.n_samples
+            self.dispersion_records(rec, P, acc0, cov, x2, rinv, accumulate=i > 0, sample_x2=sx[lo:hi] if samples else None,
+                                    sample_expect=se[lo:hi] if samples else None, sample_terms=stm[lo:hi] if samples else None)
+            lo = hi
+        z = torch.empty((2, 4, P), dtype=torch.float64, device=d)
+        phi = torch.empty((2, 4, P), dtype=torch.float32, device=d)
+        status = torch.empty((2, 4, P), dtype=torch.uint8, device=d)
+        counts = torch.zeros((4,), dtype=torch.int64, device=d)
+        self.dispersion_finalize(P, acc0, x2, rinv, z_cutoff, z, phi, status, counts)
+        return dict(x2=x2, rinv=rinv, z=z, phi=phi, status=status, counts=counts, sample_x2=sx, sample_expect=se, sample_terms=stm)
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

@@ -672,4 +672,33 @@ AMPLI_FN void ampli_power_lod(int32_t FW, int32_t k_fw, int32_t BW, int32_t k_bw
     if (stats) { stats[0] += e.n_tails; stats[1] += e.n_terms; if (e.max_terms > stats[2]) stats[2] = e.max_terms; }
 }
 
+// ---------------------------------------------------------------------------
+// Dispersion of the panel of normals.  One cell = (position, base, strand) with its n qualifying records (the records
+// the threshold sums count), K = sum of their alternative counts, D = sum of their strand depths, X2 = Pearson's statistic of the
+// counts against the pooled rate K / D, and rinv = sum of 1 / d_i.  Given K the counts are multinomial with cell probabilities
+// d_i / D under the pooled rate; Haldane's exact moments of X2 are then mean n - 1 and variance
+//   V = 2 (n - 1) + (D rinv - n^2 - 2 n + 2) / K   (>= n - 1 whenever K >= 2),
+// which hold where the expected counts are far below 1 and the chi-square table does not.
+//   z = (X2 - (n - 1)) / sqrt(V), phi = X2 / (n - 1).
+// Returns the status: AMPLI_DISPERSION_FEW (n < 2 or K < 2: z = phi = 0), else AMPLI_DISPERSION_OK, with AMPLI_DISPERSION_HIGH
+// where z >= z_cutoff.  The finalize kernel and ampli_host_dispersion_cell_batch both run this text.
+// ---------------------------------------------------------------------------
+#ifndef AMPLI_DISPERSION_HIGH // also in include/amplisolve_hip.h, which this header does not need
+#define AMPLI_DISPERSION_OK 0
+#define AMPLI_DISPERSION_FEW 1
+#define AMPLI_DISPERSION_HIGH 0x40
+#endif
+AMPLI_FN uint8_t ampli_dispersion_cell(int32_t n, double K, double D, double x2, double rinv, double z_cutoff, double *z, float *phi)
+{
+    *z = 0.0;
+    *phi = 0.0f;
+    if (n < 2 || !(K >= 2.0)) return AMPLI_DISPERSION_FEW;
+    const double nn = (double)n, nm1 = nn - 1.0;
+    const double V = 2.0 * nm1 + (D * rinv - (nn * nn + 2.0 * nn - 2.0)) / K;
+    const double zz = (x2 - nm1) / sqrt(V);
+    *z = zz;
+    *phi = (float)(x2 / nm1);
+    return zz >= z_cutoff ? AMPLI_DISPERSION_HIGH : AMPLI_DISPERSION_OK;
+}
+
 #endif

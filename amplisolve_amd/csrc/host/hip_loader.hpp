@@ -63,6 +63,10 @@ struct HipApi {
     int (*power_records)(ampli_ctx *, const ampli_records *, int64_t, const int32_t *, const uint8_t *, const float *, int32_t, float, float *, float *,
                          int64_t *);
     int (*power_stats)(ampli_ctx *, uint64_t *, int32_t);
+    int (*dispersion_records)(ampli_ctx *, const ampli_records *, int64_t, const ampli_acc_table *, int32_t, double *, double *, int32_t, double *,
+                              double *, int64_t *);
+    int (*dispersion_finalize)(ampli_ctx *, int64_t, const ampli_acc_table *, const double *, const double *, double, double *, float *, uint8_t *,
+                               int64_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

@@ -215,7 +215,7 @@ void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // without the static destructors and atexit handlers of the HIP runtime (queue / signal / pool teardown that only serves a
 // process that lives on; the driver reclaims everything at exit either way).  AMPLISOLVE_EXIT=orderly returns instead.
 void finish_process(int status);
-// ---- run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp ----
+// ---- run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp ----
 int run_error_estimation(const EeArgs &a);
 int run_variant_calling(const VcArgs &a);
 // AmpliSolveLeaveOneOut (loo_main.cpp): C_value is one value or a comma-separated list; exit status 0 / 1
@@ -234,6 +234,12 @@ struct DpArgs {
     std::string error_file, tumour_dir, output_dir, coverage_cutoff = "100", levels, confidence = "0.95";
 };
 int run_detection_power(const DpArgs &a);
+// AmpliSolvePanelDispersion (pd_main.cpp): z_cutoff is the z-score from which a cell is flagged HIGH; exit status 0 / 1
+struct PdArgs {
+    std::string panel_design, reference_genome, germline_dir, coverage_cutoff = "100", z_cutoff = "4", output_dir;
+    std::string refbases_file;
+};
+int run_panel_dispersion(const PdArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

@@ -281,6 +281,12 @@ extern "C" int ampli_host_power_pair(int32_t FW, int32_t min_fw, int32_t BW, int
     return 0;
 }
 
+extern "C" void ampli_host_dispersion_cell_batch(const int32_t *n, const double *K, const double *D, const double *x2, const double *rinv, int64_t count,
+                                                 double z_cutoff, double *z, float *phi, uint8_t *status)
+{
+    for (int64_t i = 0; i < count; ++i) status[i] = ampli_dispersion_cell(n[i], K[i], D[i], x2[i], rinv[i], z_cutoff, &z[i], &phi[i]);
+}
+
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)
 {
     try {

@@ -98,6 +98,10 @@ extern "C" {
  *   (C9) d_n_calls: the AMPLI_CALL_SHARDS counters (words k * AMPLI_CALL_COUNTER_STRIDE) are RESET BY THE CALL ITSELF, whatever
  *        they held -- with position ranges each range resets the shards dealt to it; the words between the counters mean nothing
  *        and may be zeroed.
+ *   (C10) panel dispersion (tests/test_gpu_dispersion_contracts.py): d_x2 and d_rinv of ampli_dispersion_records are FULLY OVERWRITTEN
+ *        (accumulate == 0) or ADDED TO (accumulate != 0) over their [2][4][P] extents; d_sample_x2, d_sample_expect and d_sample_terms
+ *        are FULLY OVERWRITTEN, all n entries, or all three NULL; d_z, d_phi and d_status of ampli_dispersion_finalize are FULLY
+ *        OVERWRITTEN; its d_counts[4] are ADDED TO.  The partials of the per-sample sums live in the context's workspace.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -531,6 +535,37 @@ int ampli_power_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, c
 /* work of the context's power_records launches so far: out[0] tails evaluated, out[1] pmf terms summed, out[2] the most terms of one
  * tail; reset != 0 clears them.  Synchronises the stream. */
 int ampli_power_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset);
+
+/*
+ * dispersion_records / dispersion_finalize -- per-position dispersion of the panel of normals and per-normal outlier scores.
+ * A cell is (strand, base, position); its qualifying records are the ones the threshold sums count (cnt of the accumulator table: every
+ * present record of every normal at the position, primary and extra occurrences, with FW >= and BW >= coverage_cutoff and both strand
+ * fractions of the base <= 0.05).  With k_i the record's count of the base on the strand, d_i the strand's depth, n the number of
+ * qualifying records, K = sum k_i, D = sum d_i and r = K / D:
+ *   X2  = sum (k_i - r d_i)^2 / (r d_i)          Pearson's statistic against the pooled rate
+ *   phi = X2 / (n - 1),  z = (X2 - (n - 1)) / sqrt(V),  V = 2 (n - 1) + (D sum 1/d_i - n^2 - 2 n + 2) / K   (Haldane's exact variance)
+ * A cell with n < 2 or K < 2 is FEW: X2 = sum 1/d = z = phi = 0, and it contributes to no per-sample sum.
+ *   d_acc0      the WHOLE cohort's table reduced with C = 0 and the same coverage_cutoff (ampli_error_reduce_records over every chunk,
+ *               AMPLI_REDUCE_SUMMARY is enough): snt = K exactly, srd = D, cnt = n.  A table of other parameters is not detected.
+ *   recs        one resident chunk of that cohort (any layout, dup_off required when E > 0, rd / rd_ext as for error_reduce); call once
+ *               per chunk, accumulate != 0 from the second chunk on
+ *   d_x2, d_rinv  double [2][4][P]: X2 and sum 1/d_i, overwritten (accumulate == 0) or ADDED to
+ *   d_sample_x2, d_sample_expect double [n], d_sample_terms int64 [n]: OVERWRITTEN, chunk-local rows, all three NULL or none -- over the
+ *               OK cells and the sample's qualifying records in them: sum (k - r d)^2 / (r d), sum (1 - d / D) (the null mean of the
+ *               same terms) and the number of terms.  x2 / expect is about 1 for an ordinary normal.
+ * ampli_dispersion_finalize, once every chunk has been added: d_z double, d_phi float, d_status uint8, each [2][4][P], overwritten --
+ * status AMPLI_DISPERSION_OK or _FEW in bits 0-2, AMPLI_DISPERSION_HIGH where the cell is OK and z >= z_cutoff; d_counts int64 [4] ADDED
+ * to: cells OK | cells FEW | cells HIGH | positions with a HIGH cell.
+ * No floating-point atomics: the same inputs in the same chunks give the same bytes.  Asynchronous on the context's stream.
+ */
+#define AMPLI_DISPERSION_OK 0
+#define AMPLI_DISPERSION_FEW 1
+#define AMPLI_DISPERSION_HIGH 0x40
+int ampli_dispersion_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_acc_table *d_acc0, int32_t coverage_cutoff,
+                             double *d_x2, double *d_rinv, int32_t accumulate, double *d_sample_x2, double *d_sample_expect,
+                             int64_t *d_sample_terms);
+int ampli_dispersion_finalize(ampli_ctx *ctx, int64_t P, const ampli_acc_table *d_acc0, const double *d_x2, const double *d_rinv,
+                              double z_cutoff, double *d_z, float *d_phi, uint8_t *d_status, int64_t *d_counts);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

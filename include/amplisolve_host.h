@@ -181,6 +181,12 @@ double ampli_host_binom_tail(int32_t n, int32_t k, double v, int32_t *terms);
 int ampli_host_power_pair(int32_t FW, int32_t min_fw, int32_t BW, int32_t min_bw, const float *levels, int32_t n_levels, float confidence,
                           double *power, double *lod, int32_t *iters);
 
+/* Panel dispersion: the finalize arithmetic of one cell (csrc/ampli_math.h, ampli_dispersion_cell -- what
+ * dispersion_finalize_kernel runs) over `count` cells: n qualifying records, K alternative reads, D depth, X2 and sum 1/d -> z, phi
+ * and the status (AMPLI_DISPERSION_OK / _FEW, AMPLI_DISPERSION_HIGH where z >= z_cutoff). */
+void ampli_host_dispersion_cell_batch(const int32_t *n, const double *K, const double *D, const double *x2, const double *rinv, int64_t count,
+                                      double z_cutoff, double *z, float *phi, uint8_t *status);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
