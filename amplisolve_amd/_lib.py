@@ -143,7 +143,15 @@ HIP_SYMBOLS = {
     "ampli_power_stats": (C.c_int, [vp, C.POINTER(C.c_uint64), i32]),
     "ampli_dispersion_records": (C.c_int, [vp, C.POINTER(Records), i64, C.POINTER(AccTable), i32, vp, vp, i32, vp, vp, vp]),
     "ampli_dispersion_finalize": (C.c_int, [vp, i64, C.POINTER(AccTable), vp, vp, C.c_double, vp, vp, vp, vp]),
+    "ampli_concordance_words": (i64, [i64]),
+    "ampli_genotype_planes_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp]),
+    "ampli_concordance_pairs": (C.c_int, [vp, i64, vp, i32, vp, i32, vp]),
 }
+
+class GenotypeParams(C.Structure):
+    """mirror of ampli_genotype_params (the four _pm fields are per mille)"""
+    _fields_ = [("min_depth", i32), ("absent_max_pm", i32), ("het_min_pm", i32), ("het_max_pm", i32), ("hom_min_pm", i32)]
+
 
 class HostShard(C.Structure):
     """mirror of ampli_host_shard (include/amplisolve_host.h): one shard of a multi-process run + its collective hooks"""
@@ -211,6 +219,8 @@ HOST_SYMBOLS = {
     "ampli_host_binom_tail": (C.c_double, [i32, i32, C.c_double, C.POINTER(i32)]),
     "ampli_host_power_pair": (C.c_int, [i32, i32, i32, i32, C.POINTER(f32), i32, f32, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(i32)]),
     "ampli_host_dispersion_cell_batch": (None, [vp, vp, vp, vp, vp, i64, C.c_double, vp, vp, vp]),
+    "ampli_host_genotype_classify_batch": (C.c_int, [vp, i64, vp, vp]),
+    "ampli_host_concordance_relation": (C.c_int, [i32, i32, i32, C.c_double]),
 }
 
 _hip = None

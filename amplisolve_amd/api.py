@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, LooCall, Records, hip_lib
+from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, GenotypeParams, LooCall, Records, hip_lib
 
 NT = "ACGT"
 POISSON_FULL = 0
@@ -23,6 +23,12 @@ LIMIT_CALLED, LIMIT_RECHECK = 0x40, 0x80
 LIMIT_COUNTERS = 6
 # AMPLI_DISPERSION_* (Context.panel_dispersion)
 DISPERSION_OK, DISPERSION_FEW, DISPERSION_HIGH = 0, 1, 0x40
+# the planes of Context.genotype_planes (AMPLI_GENO_*: bit k of a classified record is plane k), the counts of Context.concordance
+# and AMPLI_RELATION_* of ampli_host_concordance_relation
+GENO_PLANES = 6
+GENO_V, GENO_A, GENO_C, GENO_G, GENO_T, GENO_H = range(6)
+CONC_SITES, CONC_MATCH, CONC_IBS0, CONC_HET_EITHER, CONC_HET_MATCH = range(5)
+RELATION_UNDETERMINED, RELATION_SAME, RELATION_DIFFERENT = range(3)
 
 
 def _ptr(t):
@@ -419,6 +425,34 @@ class Context:
         counts = torch.zeros((4,), dtype=torch.int64, device=d)
         self.dispersion_finalize(P, acc0, x2, rinv, z_cutoff, z, phi, status, counts)
         return dict(x2=x2, rinv=rinv, z=z, phi=phi, status=status, counts=counts, sample_x2=sx, sample_expect=se, sample_terms=stm)
+
+    def genotype_planes(self, rec: Records, P: int, min_depth: int = 100, absent_max_pm: int = 100, het_min_pm: int = 250, het_max_pm: int = 750,
+                        hom_min_pm: int = 900, out=None):
+        """Genotype bit planes of one resident chunk from its counts alone (ampli_genotype_planes_records): int64 [n, 6, W]
+        holding the uint64 bit patterns, W = ceil(P / 64), planes V, A, C, G, T, H; bit i of word w is position 64 w + i.  Only the
+        primary records enter.  out: the chunk's rows of a larger buffer (a contiguous int64 [n, 6, W] view), overwritten."""
+        import torch
+
+        n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
+        if out is None:
+            out = torch.empty((n, GENO_PLANES, W), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, GENO_PLANES, W)
+        prm = GenotypeParams(min_depth, absent_max_pm, het_min_pm, het_max_pm, hom_min_pm)
+        self._check(self.lib.ampli_genotype_planes_records(self.h, C.byref(rec), P, C.byref(prm), _ptr(out)))
+        return out
+
+    def concordance(self, planes_a, planes_b, P: int):
+        """The five counts of every pair of two sets of genotype planes (ampli_concordance_pairs): int32 [n_a, n_b, 5] = sites, match,
+        ibs0, het_either, het_match (CONC_*).  The same tensor twice: the set against itself, its upper triangle computed and mirrored."""
+        import torch
+
+        W = int(self.lib.ampli_concordance_words(P))
+        for t in (planes_a, planes_b):
+            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and tuple(t.shape[1:]) == (GENO_PLANES, W)
+        n_a, n_b = planes_a.shape[0], planes_b.shape[0]
+        out = torch.empty((n_a, n_b, 5), dtype=torch.int32, device=self.device)
+        self._check(self.lib.ampli_concordance_pairs(self.h, P, _ptr(planes_a), n_a, _ptr(planes_b), n_b, _ptr(out)))
+        return out
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

@@ -701,4 +701,67 @@ AMPLI_FN uint8_t ampli_dispersion_cell(int32_t n, double K, double D, double x2,
     return zz >= z_cutoff ? AMPLI_DISPERSION_HIGH : AMPLI_DISPERSION_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Sample identity: the genotype of one (sample, position) from its counts alone, as six plane bits, and the relation of
+// a pair of samples from the pair's counts.  Only the PRIMARY record of a position enters (slot r < P): extra occurrences (ext,
+// dup_off, ext_pos) and the own-RD planes (rd, rd_ext) are ignored.  No reference base, no error table.
+//   n_b = fw[b] + bw[b], d = sum n_b; with the per-mille bounds of ampli_genotype_params base b is
+//     ABSENT 1000 n_b <= absent_max_pm d | HET het_min_pm d <= 1000 n_b <= het_max_pm d | HOM 1000 n_b >= hom_min_pm d | else AMBIGUOUS
+//   VALID: present, d >= min_depth, no AMBIGUOUS base, and one HOM with no HET or two HET with no HOM.
+// Every product is formed in int64: an int32-layout record may hold counts near 2^31 (n_b < 2^33, d < 2^35, 1000 d < 2^45).
+// Returns the bits AMPLI_GENO_V | _A | _C | _G | _T (the base is HET or HOM) | _H (the position is a het); 0 unless VALID.  Bit k is
+// plane k of the device's uint64 planes[sample][6][W].  genotype_planes_kernel and ampli_host_genotype_classify_batch run this text.
+// ---------------------------------------------------------------------------
+#ifndef AMPLI_GENOTYPE_PARAMS_DEFINED // also in include/amplisolve_hip.h, which this header does not need
+#define AMPLI_GENOTYPE_PARAMS_DEFINED
+typedef struct ampli_genotype_params {
+    int32_t min_depth, absent_max_pm, het_min_pm, het_max_pm, hom_min_pm;
+} ampli_genotype_params;
+#define AMPLI_GENO_V 1
+#define AMPLI_GENO_A 2
+#define AMPLI_GENO_C 4
+#define AMPLI_GENO_G 8
+#define AMPLI_GENO_T 16
+#define AMPLI_GENO_H 32
+#define AMPLI_GENO_PLANES 6
+#define AMPLI_RELATION_UNDETERMINED 0
+#define AMPLI_RELATION_SAME 1
+#define AMPLI_RELATION_DIFFERENT 2
+#endif
+// min_depth >= 1 and 0 <= absent_max_pm < het_min_pm <= het_max_pm < hom_min_pm <= 1000
+AMPLI_FN int ampli_genotype_params_ok(const ampli_genotype_params *q)
+{
+    return q->min_depth >= 1 && q->absent_max_pm >= 0 && q->absent_max_pm < q->het_min_pm && q->het_min_pm <= q->het_max_pm &&
+           q->het_max_pm < q->hom_min_pm && q->hom_min_pm <= 1000;
+}
+AMPLI_FN uint32_t ampli_genotype_classify(const int32_t fw[4], const int32_t bw[4], int present, const ampli_genotype_params *q)
+{
+    int64_t n[4], d = 0;
+    for (int b = 0; b < 4; ++b) {
+        n[b] = (int64_t)fw[b] + (int64_t)bw[b];
+        d += n[b];
+    }
+    const int64_t lim_abs = (int64_t)q->absent_max_pm * d, lim_het_lo = (int64_t)q->het_min_pm * d, lim_het_hi = (int64_t)q->het_max_pm * d,
+                  lim_hom = (int64_t)q->hom_min_pm * d;
+    uint32_t bits = 0;
+    int n_het = 0, n_hom = 0, n_amb = 0;
+    for (int b = 0; b < 4; ++b) {
+        const int64_t k = 1000 * n[b];
+        const int absent = k <= lim_abs, het = k >= lim_het_lo && k <= lim_het_hi, hom = k >= lim_hom;
+        n_het += het;
+        n_hom += hom;
+        n_amb += !(absent || het || hom);
+        bits |= (het || hom) ? 2u << b : 0u;
+    }
+    const int valid = present && d >= (int64_t)q->min_depth && n_amb == 0 && ((n_hom == 1 && n_het == 0) || (n_het == 2 && n_hom == 0));
+    return valid ? (bits | AMPLI_GENO_V | (n_het == 2 ? AMPLI_GENO_H : 0u)) : 0u;
+}
+// the relation of a pair from its het_either and het_match counts: positions where both samples are homozygous for the same base
+// (nearly every panel position) never enter the deciding ratio
+AMPLI_FN int ampli_concordance_relation(int32_t het_either, int32_t het_match, int32_t min_sites, double same_fraction)
+{
+    if (het_either < min_sites) return AMPLI_RELATION_UNDETERMINED;
+    return (double)het_match >= same_fraction * (double)het_either ? AMPLI_RELATION_SAME : AMPLI_RELATION_DIFFERENT;
+}
+
 #endif

@@ -67,6 +67,8 @@ struct HipApi {
                               double *, int64_t *);
     int (*dispersion_finalize)(ampli_ctx *, int64_t, const ampli_acc_table *, const double *, const double *, double, double *, float *, uint8_t *,
                                int64_t *);
+    int (*genotype_planes_records)(ampli_ctx *, const ampli_records *, int64_t, const ampli_genotype_params *, uint64_t *);
+    int (*concordance_pairs)(ampli_ctx *, int64_t, const uint64_t *, int32_t, const uint64_t *, int32_t, int32_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

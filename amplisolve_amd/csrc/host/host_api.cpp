@@ -287,6 +287,18 @@ extern "C" void ampli_host_dispersion_cell_batch(const int32_t *n, const double 
     for (int64_t i = 0; i < count; ++i) status[i] = ampli_dispersion_cell(n[i], K[i], D[i], x2[i], rinv[i], z_cutoff, &z[i], &phi[i]);
 }
 
+extern "C" int ampli_host_genotype_classify_batch(const int32_t *recs, int64_t count, const ampli_genotype_params *prm, uint8_t *bits)
+{
+    if (!recs || !prm || !bits || count < 0 || !ampli_genotype_params_ok(prm)) return AMPLI_E_INVALID;
+    for (int64_t i = 0; i < count; ++i) bits[i] = (uint8_t)ampli_genotype_classify(recs + i * 8, recs + i * 8 + 4, recs[i * 8] != AMPLI_ABSENT, prm);
+    return 0;
+}
+
+extern "C" int ampli_host_concordance_relation(int32_t het_either, int32_t het_match, int32_t min_sites, double same_fraction)
+{
+    return ampli_concordance_relation(het_either, het_match, min_sites, same_fraction);
+}
+
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)
 {
     try {

@@ -1,4 +1,4 @@
-// amplisolve_amd/csrc/host/pipeline.hpp -- what the four command lines (run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp) share.
+// amplisolve_amd/csrc/host/pipeline.hpp -- what the command lines (run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp) share.
 // Internal to those files and pipeline.cpp; the commands themselves are declared in host.hpp.
 #pragma once
 #include <algorithm>
@@ -187,6 +187,13 @@ void parallel_rows(size_t n, size_t grain, const std::function<void(size_t, size
 // what a failed command prints, and its exit status: the reference's banner (EE / VC) or one line (LOO / DL)
 int fail_banner(const Error &e);
 inline int fail_line(const char *program, const std::string &why) { std::cout << program << " failed: " << why << std::endl; return 1; }
+
+// AmpliSolveSampleConcordance (sc_main.cpp, run_sc.cpp): are the count files who they say they are.  tumour_dir "-" = the
+// normals only; min_depth, min_sites integers >= 1, same_fraction in (0, 1]; exit status 0 / 1
+struct ScArgs {
+    std::string panel_design, germline_dir, tumour_dir = "-", min_depth = "100", min_sites = "20", same_fraction = "0.8", output_dir;
+};
+int run_sample_concordance(const ScArgs &a);
 
 // ---- the emitted calls ----
 // Where a record of a chunk came from: the data line of its sample's file (-1: absent) and the panel position of record slot r in

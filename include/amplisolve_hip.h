@@ -102,6 +102,10 @@ extern "C" {
  *        (accumulate == 0) or ADDED TO (accumulate != 0) over their [2][4][P] extents; d_sample_x2, d_sample_expect and d_sample_terms
  *        are FULLY OVERWRITTEN, all n entries, or all three NULL; d_z, d_phi and d_status of ampli_dispersion_finalize are FULLY
  *        OVERWRITTEN; its d_counts[4] are ADDED TO.  The partials of the per-sample sums live in the context's workspace.
+ *   (C11) sample identity (tests/test_gpu_concordance_contracts.py): d_planes of ampli_genotype_planes_records is FULLY OVERWRITTEN, every
+ *        word of the chunk's [n_samples][6][W] rows, the bits at and beyond P zero; d_counts of ampli_concordance_pairs is FULLY
+ *        OVERWRITTEN, all [n_a][n_b][5] counts (with d_planes_a == d_planes_b too).  Neither touches anything else; the planes are
+ *        inputs of ampli_concordance_pairs and stay as they are.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -566,6 +570,49 @@ int ampli_dispersion_records(ampli_ctx *ctx, const ampli_records *recs, int64_t 
                              int64_t *d_sample_terms);
 int ampli_dispersion_finalize(ampli_ctx *ctx, int64_t P, const ampli_acc_table *d_acc0, const double *d_x2, const double *d_rinv,
                               double z_cutoff, double *d_z, float *d_phi, uint8_t *d_status, int64_t *d_counts);
+
+/*
+ * genotype_planes_records / concordance_pairs -- sample identity: are two count files the same person.
+ * The genotype of (sample, position) comes from the counts of the position's PRIMARY record alone (slot r < P): extra occurrences (ext,
+ * E, dup_off, ext_pos) and the own-RD planes (rd, rd_ext) of `recs` are ignored, no reference base and no error table is read.  With
+ * n_b = fw[b] + bw[b] and d = sum n_b (all products in int64), base b is ABSENT when 1000 n_b <= absent_max_pm d, HET when
+ * het_min_pm d <= 1000 n_b <= het_max_pm d, HOM when 1000 n_b >= hom_min_pm d, else AMBIGUOUS; the position is VALID when the record is
+ * present, d >= min_depth, no base is AMBIGUOUS and either one base is HOM and none HET or two are HET and none HOM.
+ *   prm       min_depth >= 1 and 0 <= absent_max_pm < het_min_pm <= het_max_pm < hom_min_pm <= 1000 (library defaults 100 / 100 / 250 /
+ *             750 / 900), else AMPLI_E_INVALID
+ *   d_planes  uint64 [recs->n_samples][6][W], W = ampli_concordance_words(P) = ceil(P / 64), 8-byte aligned, OVERWRITTEN, all of it:
+ *             plane 0 V (valid), 1-4 A, C, G, T (the base is HET or HOM), 5 H (the position is a het); every plane is 0 where V is 0;
+ *             bit i of word w is position 64 w + i; bits at and beyond P are 0.  A streamed cohort encodes each chunk into its rows of
+ *             one buffer: pass d_planes + first_sample * 6 * W.
+ * ampli_concordance_pairs: for every pair (a, b) of two plane sets (or of one: d_planes_a == d_planes_b with n_a == n_b computes the
+ * upper triangle and mirrors it) five int32 counts, summed over the words, with both = Va & Vb, diff = OR over the bases of Xa ^ Xb,
+ * share = OR of Xa & Xb:
+ *   d_counts  int32 [n_a][n_b][5], OVERWRITTEN: sites popcount(both) | match popcount(both & ~diff) | ibs0 popcount(both & ~share)
+ *             (opposite homozygotes) | het_either popcount(both & (Ha | Hb)) | het_match popcount(both & ~diff & Ha)
+ * On the diagonal of a set against itself sites is the sample's valid positions and het_either its het positions.  P < 2^31.
+ * Integers only: the same inputs give the same bytes.  Both are asynchronous on the context's stream.  The relation of a pair is
+ * decided on the host (ampli_host_concordance_relation, include/amplisolve_host.h).
+ */
+#ifndef AMPLI_GENOTYPE_PARAMS_DEFINED /* also in csrc/ampli_math.h */
+#define AMPLI_GENOTYPE_PARAMS_DEFINED
+typedef struct ampli_genotype_params {
+    int32_t min_depth, absent_max_pm, het_min_pm, het_max_pm, hom_min_pm;
+} ampli_genotype_params;
+#define AMPLI_GENO_V 1
+#define AMPLI_GENO_A 2
+#define AMPLI_GENO_C 4
+#define AMPLI_GENO_G 8
+#define AMPLI_GENO_T 16
+#define AMPLI_GENO_H 32
+#define AMPLI_GENO_PLANES 6
+#define AMPLI_RELATION_UNDETERMINED 0
+#define AMPLI_RELATION_SAME 1
+#define AMPLI_RELATION_DIFFERENT 2
+#endif
+int64_t ampli_concordance_words(int64_t P);
+int ampli_genotype_planes_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_genotype_params *prm, uint64_t *d_planes);
+int ampli_concordance_pairs(ampli_ctx *ctx, int64_t P, const uint64_t *d_planes_a, int32_t n_a, const uint64_t *d_planes_b, int32_t n_b,
+                            int32_t *d_counts);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

@@ -187,6 +187,15 @@ int ampli_host_power_pair(int32_t FW, int32_t min_fw, int32_t BW, int32_t min_bw
 void ampli_host_dispersion_cell_batch(const int32_t *n, const double *K, const double *D, const double *x2, const double *rinv, int64_t count,
                                       double z_cutoff, double *z, float *phi, uint8_t *status);
 
+/* Sample identity: the genotype of `count` records (int32 [count][8], absent: field 0 == INT32_MIN) as the six plane bits
+ * AMPLI_GENO_V | _A | _C | _G | _T | _H of include/amplisolve_hip.h -- csrc/ampli_math.h's ampli_genotype_classify, what
+ * genotype_planes_kernel runs.  Returns 0, or AMPLI_E_INVALID (-1) with nothing written when prm breaks its inequalities. */
+struct ampli_genotype_params; /* include/amplisolve_hip.h */
+int ampli_host_genotype_classify_batch(const int32_t *recs, int64_t count, const struct ampli_genotype_params *prm, uint8_t *bits);
+/* the relation of a pair of samples from two of its counts: AMPLI_RELATION_UNDETERMINED when het_either < min_sites, else _SAME when
+ * (double)het_match >= same_fraction * (double)het_either, else _DIFFERENT */
+int ampli_host_concordance_relation(int32_t het_either, int32_t het_match, int32_t min_sites, double same_fraction);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
