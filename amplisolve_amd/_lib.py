@@ -146,6 +146,7 @@ HIP_SYMBOLS = {
     "ampli_concordance_words": (i64, [i64]),
     "ampli_genotype_planes_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp]),
     "ampli_concordance_pairs": (C.c_int, [vp, i64, vp, i32, vp, i32, vp]),
+    "ampli_contamination_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -221,6 +222,7 @@ HOST_SYMBOLS = {
     "ampli_host_dispersion_cell_batch": (None, [vp, vp, vp, vp, vp, i64, C.c_double, vp, vp, vp]),
     "ampli_host_genotype_classify_batch": (C.c_int, [vp, i64, vp, vp]),
     "ampli_host_concordance_relation": (C.c_int, [i32, i32, i32, C.c_double]),
+    "ampli_host_contamination_estimate": (C.c_int, [vp, i64, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _hip = None

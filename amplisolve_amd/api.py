@@ -29,6 +29,11 @@ GENO_PLANES = 6
 GENO_V, GENO_A, GENO_C, GENO_G, GENO_T, GENO_H = range(6)
 CONC_SITES, CONC_MATCH, CONC_IBS0, CONC_HET_EITHER, CONC_HET_MATCH = range(5)
 RELATION_UNDETERMINED, RELATION_SAME, RELATION_DIFFERENT = range(3)
+# the nine sums of Context.contamination (AMPLI_CONTAM_*) and AMPLI_CONTAM_STATUS_* of ampli_host_contamination_estimate
+CONTAM_SUMS = 9
+(CONTAM_SITES_HOM, CONTAM_ALT_HOM, CONTAM_DEPTH_HOM, CONTAM_SITES_HET, CONTAM_ALT_HET, CONTAM_DEPTH_HET, CONTAM_SITES_BG, CONTAM_ALT_BG,
+ CONTAM_DEPTH_BG) = range(9)
+CONTAM_UNDETERMINED, CONTAM_CLEAN, CONTAM_CONTAMINATED = range(3)
 
 
 def _ptr(t):
@@ -452,6 +457,24 @@ class Context:
         n_a, n_b = planes_a.shape[0], planes_b.shape[0]
         out = torch.empty((n_a, n_b, 5), dtype=torch.int32, device=self.device)
         self._check(self.lib.ampli_concordance_pairs(self.h, P, _ptr(planes_a), n_a, _ptr(planes_b), n_b, _ptr(out)))
+        return out
+
+    def contamination(self, rec: Records, P: int, planes_a, planes_b, out=None):
+        """The nine sums of every ordered pair (recipient of one resident chunk, source) of the cross-sample contamination check
+        (ampli_contamination_records): int64 [n, n_b, 9] (CONTAM_*).  planes_a: the genotype planes of the chunk's own rows,
+        int64 [n, 6, W]; planes_b: those of the n_b sources.  Only the primary records enter.  out: the chunk's rows of a larger matrix
+        (a contiguous int64 [n, n_b, 9] view), overwritten."""
+        import torch
+
+        n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
+        for t in (planes_a, planes_b):
+            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and tuple(t.shape[1:]) == (GENO_PLANES, W)
+        assert planes_a.shape[0] == n
+        n_b = planes_b.shape[0]
+        if out is None:
+            out = torch.empty((n, n_b, CONTAM_SUMS), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, n_b, CONTAM_SUMS)
+        self._check(self.lib.ampli_contamination_records(self.h, C.byref(rec), P, _ptr(planes_a), _ptr(planes_b), n_b, _ptr(out)))
         return out
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,

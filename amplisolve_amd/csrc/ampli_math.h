@@ -764,4 +764,49 @@ AMPLI_FN int ampli_concordance_relation(int32_t het_either, int32_t het_match, i
     return (double)het_match >= same_fraction * (double)het_either ? AMPLI_RELATION_SAME : AMPLI_RELATION_DIFFERENT;
 }
 
+// ---------------------------------------------------------------------------
+// Cross-sample contamination: the fraction of recipient a's reads that come from source b, from the nine int64 sums of
+// the ordered pair (contamination_kernel, index order AMPLI_CONTAM_*).  At a position where a is validly homozygous for X and b
+// carries a base Y that a does not, a fraction c of b's reads shows n[Y] = c d reads where b is homozygous and c d / 2 where b is
+// heterozygous for Y; the sequencing error puts e d reads on each other base, e measured on the positions where b has a's genotype:
+//   alt = s1 + s4, slots = s2 + s5, den = s2 + s5 / 2, e = s7 / (3 s8), fraction = max(0, (alt - e slots) / den), se = sqrt(alt) / den.
+// In double, in exactly this order.  num is NOT fused: the host library and the kernels' unit are both built with -ffp-contract=off
+// (build.py), so that alt - e * slots is a rounded product and a rounded difference on every compiler -- the numpy model
+// (tests/contamination_model.py) computes it that way, and tests/test_contamination_host.py compares the two bit for bit.
+// fraction and se are NaN where den == 0.  The status: UNDETERMINED while s0 + s3 < min_sites, else CONTAMINATED where
+// fraction >= min_fraction (never for a NaN), else CLEAN.
+// ---------------------------------------------------------------------------
+#ifndef AMPLI_CONTAM_SUMS // also in include/amplisolve_hip.h, which this header does not need
+#define AMPLI_CONTAM_SITES_HOM 0
+#define AMPLI_CONTAM_ALT_HOM 1
+#define AMPLI_CONTAM_DEPTH_HOM 2
+#define AMPLI_CONTAM_SITES_HET 3
+#define AMPLI_CONTAM_ALT_HET 4
+#define AMPLI_CONTAM_DEPTH_HET 5
+#define AMPLI_CONTAM_SITES_BG 6
+#define AMPLI_CONTAM_ALT_BG 7
+#define AMPLI_CONTAM_DEPTH_BG 8
+#define AMPLI_CONTAM_SUMS 9
+#define AMPLI_CONTAM_STATUS_UNDETERMINED 0
+#define AMPLI_CONTAM_STATUS_CLEAN 1
+#define AMPLI_CONTAM_STATUS_CONTAMINATED 2
+#endif
+AMPLI_FN int ampli_contamination_estimate(const int64_t s[AMPLI_CONTAM_SUMS], int64_t min_sites, double min_fraction, double *fraction, double *se,
+                                          double *background)
+{
+    const double alt = (double)(s[AMPLI_CONTAM_ALT_HOM] + s[AMPLI_CONTAM_ALT_HET]);
+    const double slots = (double)(s[AMPLI_CONTAM_DEPTH_HOM] + s[AMPLI_CONTAM_DEPTH_HET]);
+    const double den = (double)s[AMPLI_CONTAM_DEPTH_HOM] + 0.5 * (double)s[AMPLI_CONTAM_DEPTH_HET];
+    const double e = s[AMPLI_CONTAM_DEPTH_BG] > 0 ? (double)s[AMPLI_CONTAM_ALT_BG] / (3.0 * (double)s[AMPLI_CONTAM_DEPTH_BG]) : 0.0;
+    const double prod = e * slots;
+    const double num = alt - prod;
+    const double q = num / den;
+    const double f = den > 0 ? (q > 0.0 ? q : 0.0) : (double)NAN;
+    if (fraction) *fraction = f;
+    if (se) *se = den > 0 ? sqrt(alt) / den : (double)NAN;
+    if (background) *background = e;
+    if (s[AMPLI_CONTAM_SITES_HOM] + s[AMPLI_CONTAM_SITES_HET] < min_sites) return AMPLI_CONTAM_STATUS_UNDETERMINED;
+    return f >= min_fraction ? AMPLI_CONTAM_STATUS_CONTAMINATED : AMPLI_CONTAM_STATUS_CLEAN;
+}
+
 #endif

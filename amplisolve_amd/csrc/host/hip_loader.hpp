@@ -69,6 +69,7 @@ struct HipApi {
                                int64_t *);
     int (*genotype_planes_records)(ampli_ctx *, const ampli_records *, int64_t, const ampli_genotype_params *, uint64_t *);
     int (*concordance_pairs)(ampli_ctx *, int64_t, const uint64_t *, int32_t, const uint64_t *, int32_t, int32_t *);
+    int (*contamination_records)(ampli_ctx *, const ampli_records *, int64_t, const uint64_t *, const uint64_t *, int32_t, int64_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

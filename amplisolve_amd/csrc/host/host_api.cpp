@@ -299,6 +299,13 @@ extern "C" int ampli_host_concordance_relation(int32_t het_either, int32_t het_m
     return ampli_concordance_relation(het_either, het_match, min_sites, same_fraction);
 }
 
+extern "C" int ampli_host_contamination_estimate(const int64_t *sums, int64_t min_sites, double min_fraction, double *fraction, double *se,
+                                                 double *background)
+{
+    if (!sums) return AMPLI_E_INVALID;
+    return ampli_contamination_estimate(sums, min_sites, min_fraction, fraction, se, background);
+}
+
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)
 {
     try {

@@ -195,6 +195,13 @@ struct ScArgs {
 };
 int run_sample_concordance(const ScArgs &a);
 
+// AmpliSolveContamination (ct_main.cpp, run_ct.cpp): which count file leaks into which, and how much.  tumour_dir "-" = the
+// normals only; min_depth, min_sites integers >= 1, min_fraction in (0, 1]; exit status 0 / 1
+struct CtArgs {
+    std::string panel_design, germline_dir, tumour_dir = "-", output_dir, min_depth = "100", min_sites = "20", min_fraction = "0.005";
+};
+int run_contamination(const CtArgs &a);
+
 // ---- the emitted calls ----
 // Where a record of a chunk came from: the data line of its sample's file (-1: absent) and the panel position of record slot r in
 // [0, P + E).  H is the Chunk, or a copy of these members that outlives it (leave-one-out's Resident).

@@ -106,6 +106,11 @@ extern "C" {
  *        word of the chunk's [n_samples][6][W] rows, the bits at and beyond P zero; d_counts of ampli_concordance_pairs is FULLY
  *        OVERWRITTEN, all [n_a][n_b][5] counts (with d_planes_a == d_planes_b too).  Neither touches anything else; the planes are
  *        inputs of ampli_concordance_pairs and stay as they are.
+ *   (C12) cross-sample contamination (tests/test_gpu_contamination_contracts.py): d_sums of ampli_contamination_records is FULLY
+ *        OVERWRITTEN, all [recs->n_samples][n_b][9] sums, whatever it held and however many position slices the launch is cut into (the
+ *        call clears it itself where slices are added into it).  Nothing else is written -- the other chunks' rows of a larger matrix
+ *        included -- and the records and both plane sets stay as they are.  Plane rows at and beyond n_samples / n_b and plane words
+ *        at and beyond W are never read.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -613,6 +618,45 @@ int64_t ampli_concordance_words(int64_t P);
 int ampli_genotype_planes_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_genotype_params *prm, uint64_t *d_planes);
 int ampli_concordance_pairs(ampli_ctx *ctx, int64_t P, const uint64_t *d_planes_a, int32_t n_a, const uint64_t *d_planes_b, int32_t n_b,
                             int32_t *d_counts);
+
+/*
+ * contamination_records -- cross-sample contamination: which file leaks into which, and how much.  The counts of every
+ * recipient a of a resident chunk are weighed against the genotypes of every source b, for every ordered pair.  Of `recs` only the
+ * primary record of each (sample, position) enters, as in ampli_genotype_planes_records; with n[Y] = fw[Y] + bw[Y] and d = sum n[Y]
+ * in int64, an absent record counting as all zeros whatever the planes say.  With the plane bits of a and b at a position:
+ *   homA = Va & ~Ha (a is validly homozygous for its one base X), o[Y] = homA & Vb & B_Y & ~A_Y (b carries a base that a does not),
+ *   bg = homA & Vb & ~(o[A] | o[C] | o[G] | o[T]) (b has a's genotype)
+ * nine int64 sums over the positions, in the order AMPLI_CONTAM_*:
+ *   sites_hom  1 if any o[Y] & ~Hb      alt_hom  n[Y] of those Y                  depth_hom  d, once
+ *   sites_het  1 if any o[Y] & Hb       alt_het  n[Y] of every such Y (1 or 2)    depth_het  d once per such Y
+ *   sites_bg   1 if bg                  alt_bg   sum of n[Y] over the Y with ~A_Y depth_bg   d
+ *   d_planes_a  uint64 [recs->n_samples][6][W]: the planes of THE CHUNK'S rows (ampli_genotype_planes_records), W = ceil(P / 64)
+ *   d_planes_b  uint64 [n_b][6][W]: the planes of the sources; may be (or overlap) d_planes_a
+ *   d_sums      int64 [recs->n_samples][n_b][9], 8-byte aligned, FULLY OVERWRITTEN (C12).  A streamed recipient set writes each chunk
+ *               into its rows of one matrix: pass d_sums + first_sample * n_b * 9.
+ * All sums are exact: with the 16- and 24-bit layouts d < 2^27 and every sum stays below 2^59 for any P < 2^31; with the int32 layout
+ * d < 2^34, counted at most twice per position, and P >= 2^28 is refused with AMPLI_E_RANGE (no data-dependent check is made).
+ * P >= 2^31 and n_b > 4194240 are AMPLI_E_RANGE too.  Integers only, and integer additions only where position slices meet: the
+ * same inputs give the same bytes.  Asynchronous on the context's stream.  The estimate and the status of a pair are decided on the
+ * host (ampli_host_contamination_estimate, include/amplisolve_host.h).
+ */
+#ifndef AMPLI_CONTAM_SUMS /* also in csrc/ampli_math.h */
+#define AMPLI_CONTAM_SITES_HOM 0
+#define AMPLI_CONTAM_ALT_HOM 1
+#define AMPLI_CONTAM_DEPTH_HOM 2
+#define AMPLI_CONTAM_SITES_HET 3
+#define AMPLI_CONTAM_ALT_HET 4
+#define AMPLI_CONTAM_DEPTH_HET 5
+#define AMPLI_CONTAM_SITES_BG 6
+#define AMPLI_CONTAM_ALT_BG 7
+#define AMPLI_CONTAM_DEPTH_BG 8
+#define AMPLI_CONTAM_SUMS 9
+#define AMPLI_CONTAM_STATUS_UNDETERMINED 0
+#define AMPLI_CONTAM_STATUS_CLEAN 1
+#define AMPLI_CONTAM_STATUS_CONTAMINATED 2
+#endif
+int ampli_contamination_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint64_t *d_planes_a, const uint64_t *d_planes_b,
+                                int32_t n_b, int64_t *d_sums);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

@@ -195,6 +195,12 @@ int ampli_host_genotype_classify_batch(const int32_t *recs, int64_t count, const
 /* the relation of a pair of samples from two of its counts: AMPLI_RELATION_UNDETERMINED when het_either < min_sites, else _SAME when
  * (double)het_match >= same_fraction * (double)het_either, else _DIFFERENT */
 int ampli_host_concordance_relation(int32_t het_either, int32_t het_match, int32_t min_sites, double same_fraction);
+/* Cross-sample contamination: fraction, its standard error and the background rate e of one ordered pair from its nine
+ * sums (order AMPLI_CONTAM_* of include/amplisolve_hip.h) -- csrc/ampli_math.h's ampli_contamination_estimate, in double, unfused.
+ * fraction and se are NaN where the pair has no depth on an informative site; any of the three pointers may be NULL.  Returns
+ * AMPLI_CONTAM_STATUS_UNDETERMINED when sites_hom + sites_het < min_sites, else _CONTAMINATED when fraction >= min_fraction, else
+ * _CLEAN; AMPLI_E_INVALID (-1) when sums is NULL. */
+int ampli_host_contamination_estimate(const int64_t *sums, int64_t min_sites, double min_fraction, double *fraction, double *se, double *background);
 
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
