@@ -147,6 +147,9 @@ HIP_SYMBOLS = {
     "ampli_genotype_planes_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp]),
     "ampli_concordance_pairs": (C.c_int, [vp, i64, vp, i32, vp, i32, vp]),
     "ampli_contamination_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, vp]),
+    "ampli_amplicon_depth_records": (C.c_int, [vp, C.POINTER(Records), i64, i32, vp, vp, i64, i32, vp]),
+    "ampli_amplicon_reference": (C.c_int, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
+    "ampli_amplicon_ratio": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -223,6 +226,11 @@ HOST_SYMBOLS = {
     "ampli_host_genotype_classify_batch": (C.c_int, [vp, i64, vp, vp]),
     "ampli_host_concordance_relation": (C.c_int, [i32, i32, i32, C.c_double]),
     "ampli_host_contamination_estimate": (C.c_int, [vp, i64, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "ampli_host_amplicon_median": (C.c_double, [vp, i64]),
+    "ampli_host_panel_describe": (i64, [C.c_char_p, C.c_char_p, i64]),
+    "ampli_host_amplicon_z": (C.c_double, [C.c_double, C.c_double, C.c_double]),
+    "ampli_host_amplicon_share": (C.c_double, [i64, i64]),
+    "ampli_host_amplicon_gene_status": (C.c_int, [i64, C.c_double, C.c_double, i64, C.c_double, C.c_double, C.c_double]),
 }
 
 _hip = None

@@ -34,6 +34,14 @@ CONTAM_SUMS = 9
 (CONTAM_SITES_HOM, CONTAM_ALT_HOM, CONTAM_DEPTH_HOM, CONTAM_SITES_HET, CONTAM_ALT_HET, CONTAM_DEPTH_HET, CONTAM_SITES_BG, CONTAM_ALT_BG,
  CONTAM_DEPTH_BG) = range(9)
 CONTAM_UNDETERMINED, CONTAM_CLEAN, CONTAM_CONTAMINATED = range(3)
+# the four sums of Context.amplicon_depth (AMPLI_AMP_*), the amplicon statuses of Context.amplicon_reference (AMPLI_AMPLICON_*), the
+# limit of N / A in the two stage-2 calls, the rows a wave of the depth kernel owns, and AMPLI_GENE_* of ampli_host_amplicon_gene_status
+AMP_SUMS = 4
+AMP_PRESENT, AMP_DEPTH_FW, AMP_DEPTH_BW, AMP_CALLABLE = range(4)
+AMPLICON_OK, AMPLICON_FEW, AMPLICON_DARK = range(3)
+AMPLICON_MAX = 4096
+AMPLICON_STRIP = 8
+GENE_NEUTRAL, GENE_GAIN, GENE_LOSS = range(3)
 
 
 def _ptr(t):
@@ -476,6 +484,69 @@ class Context:
         assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, n_b, CONTAM_SUMS)
         self._check(self.lib.ampli_contamination_records(self.h, C.byref(rec), P, _ptr(planes_a), _ptr(planes_b), n_b, _ptr(out)))
         return out
+
+    def amplicon_depth(self, rec: Records, P: int, amp_off, amp_pos, cov: int = 100, out=None):
+        """The four depth sums (AMP_*) of every (sample of one resident chunk, amplicon): int64 [n, A, 4] (ampli_amplicon_depth_records,
+        DESIGN 16).  amp_off [A + 1] and amp_pos [W] are the amplicons' position lists, a CSR over the BED walk with entries in [0, P):
+        device int32 tensors (read as uint32) or host arrays, which are checked (monotone, in range) and uploaded.  Only the primary
+        records enter.  out: the chunk's rows of a larger matrix (a contiguous int64 [n, A, 4] view), overwritten."""
+        import numpy as np
+        import torch
+
+        if not isinstance(amp_off, torch.Tensor):
+            off, pos = np.asarray(amp_off, np.int64), np.asarray(amp_pos, np.int64)
+            assert off.ndim == 1 and len(off) >= 2 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= len(pos) < 1 << 28
+            assert ((pos >= 0) & (pos < P)).all()
+            amp_off = torch.from_numpy(off.astype(np.int32)).to(self.device)
+            amp_pos = torch.from_numpy((pos if len(pos) else np.zeros(1, np.int64)).astype(np.int32)).to(self.device)
+            W = len(pos)
+        else:
+            W = amp_pos.numel()
+            if W == 0:  # a pointer is required even where nothing is read through it
+                amp_pos = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        for t in (amp_off, amp_pos):
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+        n, A = rec.n_samples, amp_off.numel() - 1
+        if out is None:
+            out = torch.empty((n, A, AMP_SUMS), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, A, AMP_SUMS)
+        self._check(self.lib.ampli_amplicon_depth_records(self.h, C.byref(rec), P, A, _ptr(amp_off), _ptr(amp_pos), W, cov, _ptr(out)))
+        return out
+
+    def amplicon_reference(self, sums, use, min_normals: int = 5):
+        """The reference of the panel of normals from their depth sums (int64 [N, A, 4]) and the mask use (uint8 [A]: the amplicons that
+        count towards library size): dict of total int64 [N], med and mad float64 [A], status uint8 [A] (AMPLICON_*)
+        (ampli_amplicon_reference)."""
+        import torch
+
+        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and sums.dim() == 3 and sums.shape[2] == AMP_SUMS
+        N, A = sums.shape[0], sums.shape[1]
+        assert use.dtype == torch.uint8 and use.is_cuda and use.is_contiguous() and tuple(use.shape) == (A,)
+        total = torch.empty((N,), dtype=torch.int64, device=self.device)
+        ref = torch.empty((A, 2), dtype=torch.float64, device=self.device)
+        status = torch.empty((A,), dtype=torch.uint8, device=self.device)
+        self._check(self.lib.ampli_amplicon_reference(self.h, _ptr(sums), N, A, _ptr(use), min_normals, _ptr(total), _ptr(ref), _ptr(status)))
+        return {"total": total, "med": ref[:, 0], "mad": ref[:, 1], "status": status, "ref": ref}
+
+    def amplicon_ratio(self, sums, use, ref):
+        """The ratios of any set of samples (int64 [S, A, 4] depth sums) against a reference (the dict of amplicon_reference): dict of
+        total int64 [S], centre float64 [S], k int32 [S], ratio and z float64 [S, A] (ampli_amplicon_ratio)."""
+        import torch
+
+        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and sums.dim() == 3 and sums.shape[2] == AMP_SUMS
+        S, A = sums.shape[0], sums.shape[1]
+        assert use.dtype == torch.uint8 and use.is_cuda and use.is_contiguous() and tuple(use.shape) == (A,)
+        r, st = ref["ref"], ref["status"]
+        assert r.dtype == torch.float64 and r.is_cuda and r.is_contiguous() and tuple(r.shape) == (A, 2)
+        assert st.dtype == torch.uint8 and st.is_cuda and st.is_contiguous() and tuple(st.shape) == (A,)
+        total = torch.empty((S,), dtype=torch.int64, device=self.device)
+        centre = torch.empty((S,), dtype=torch.float64, device=self.device)
+        k = torch.empty((S,), dtype=torch.int32, device=self.device)
+        ratio = torch.empty((S, A), dtype=torch.float64, device=self.device)
+        z = torch.empty((S, A), dtype=torch.float64, device=self.device)
+        self._check(self.lib.ampli_amplicon_ratio(self.h, _ptr(sums), S, A, _ptr(use), _ptr(r), _ptr(st), _ptr(total), _ptr(centre), _ptr(k),
+                                                  _ptr(ratio), _ptr(z)))
+        return {"total": total, "centre": centre, "k": k, "ratio": ratio, "z": z}
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

@@ -809,4 +809,93 @@ AMPLI_FN int ampli_contamination_estimate(const int64_t s[AMPLI_CONTAM_SUMS], in
     return f >= min_fraction ? AMPLI_CONTAM_STATUS_CONTAMINATED : AMPLI_CONTAM_STATUS_CLEAN;
 }
 
+// ---------------------------------------------------------------------------
+// Amplicon coverage and copy ratio (the definition is tests/amplicon_model.py).  Every value is an IEEE double + - x / in the
+// written order, unfused (-ffp-contract=off in both libraries), so that the kernels, the host library and the numpy model agree bit
+// for bit.
+//   share   x = (double)d / (double)T                       d = DEPTH_FW + DEPTH_BW of one (sample, amplicon), T its sample's total
+//   median  of m values in ascending order v: m odd v[(m-1)/2], m even (v[m/2-1] + v[m/2]) * 0.5, m == 0 NaN -- ONE function
+//           (ampli_amplicon_median_pick) applied to the two middle values, however they were selected: by a bitwise search on the bit
+//           patterns in the kernels (non-negative values), by ampli_amplicon_median here (signed values, a plain selection; NaNs are
+//           dropped first, and m counts what is left)
+//   z       mad > 0 ? ((ratio - 1.0) * med) / (1.4826 * mad) : NaN
+//   gene    GAIN if n >= min_amplicons, median ratio >= gain_ratio and median z >= z_cutoff; LOSS if n >= min_amplicons, median ratio
+//           <= loss_ratio and median z <= -z_cutoff; else NEUTRAL (a NaN median compares false: NEUTRAL)
+// ---------------------------------------------------------------------------
+#ifndef AMPLI_AMP_SUMS // also in include/amplisolve_hip.h, which this header does not need
+#define AMPLI_AMP_PRESENT 0
+#define AMPLI_AMP_DEPTH_FW 1
+#define AMPLI_AMP_DEPTH_BW 2
+#define AMPLI_AMP_CALLABLE 3
+#define AMPLI_AMP_SUMS 4
+#define AMPLI_AMPLICON_OK 0
+#define AMPLI_AMPLICON_FEW 1
+#define AMPLI_AMPLICON_DARK 2
+#define AMPLI_AMPLICON_MAX 4096
+#define AMPLI_AMPLICON_STRIP 8
+#define AMPLI_GENE_NEUTRAL 0
+#define AMPLI_GENE_GAIN 1
+#define AMPLI_GENE_LOSS 2
+#endif
+AMPLI_FN double ampli_amplicon_share(int64_t d, int64_t total) { return (double)d / (double)total; }
+
+AMPLI_FN double ampli_amplicon_median_pick(double lo, double hi, int64_t m)
+{
+    if (m <= 0) return (double)NAN;
+    return (m & 1) ? hi : (lo + hi) * 0.5;
+}
+
+// the k-th smallest (k from 0) of v[0 .. m), none of them NaN; v is reordered (Hoare's selection, ordinary comparisons)
+AMPLI_FN double ampli_amplicon_select(double *v, int64_t m, int64_t k)
+{
+    int64_t lo = 0, hi = m - 1;
+    while (lo < hi) {
+        const double pivot = v[lo + (hi - lo) / 2];
+        int64_t i = lo, j = hi;
+        while (i <= j) {
+            while (v[i] < pivot) ++i;
+            while (pivot < v[j]) --j;
+            if (i <= j) {
+                const double t = v[i];
+                v[i] = v[j];
+                v[j] = t;
+                ++i;
+                --j;
+            }
+        }
+        if (k <= j) hi = j;
+        else if (k >= i) lo = i;
+        else break;
+    }
+    return v[k];
+}
+
+// the median of the values of v[0 .. m) that are not NaN (signed values; v is reordered); NaN if there is none
+AMPLI_FN double ampli_amplicon_median(double *v, int64_t m)
+{
+    int64_t c = 0;
+    for (int64_t i = 0; i < m; ++i)
+        if (v[i] == v[i]) v[c++] = v[i];
+    if (c == 0) return (double)NAN;
+    const double hi = ampli_amplicon_select(v, c, c / 2);
+    const double lo = (c & 1) ? hi : ampli_amplicon_select(v, c, c / 2 - 1);
+    return ampli_amplicon_median_pick(lo, hi, c);
+}
+
+AMPLI_FN double ampli_amplicon_z(double ratio, double med, double mad)
+{
+    if (!(mad > 0.0)) return (double)NAN;
+    const double num = (ratio - 1.0) * med;
+    const double den = 1.4826 * mad;
+    return num / den;
+}
+
+AMPLI_FN int ampli_amplicon_gene_status(int64_t n, double median_ratio, double median_z, int64_t min_amplicons, double gain_ratio, double loss_ratio,
+                                        double z_cutoff)
+{
+    if (n >= min_amplicons && median_ratio >= gain_ratio && median_z >= z_cutoff) return AMPLI_GENE_GAIN;
+    if (n >= min_amplicons && median_ratio <= loss_ratio && median_z <= -z_cutoff) return AMPLI_GENE_LOSS;
+    return AMPLI_GENE_NEUTRAL;
+}
+
 #endif

@@ -70,6 +70,10 @@ struct HipApi {
     int (*genotype_planes_records)(ampli_ctx *, const ampli_records *, int64_t, const ampli_genotype_params *, uint64_t *);
     int (*concordance_pairs)(ampli_ctx *, int64_t, const uint64_t *, int32_t, const uint64_t *, int32_t, int32_t *);
     int (*contamination_records)(ampli_ctx *, const ampli_records *, int64_t, const uint64_t *, const uint64_t *, int32_t, int64_t *);
+    int (*amplicon_depth_records)(ampli_ctx *, const ampli_records *, int64_t, int32_t, const uint32_t *, const uint32_t *, int64_t, int32_t, int64_t *);
+    int (*amplicon_reference)(ampli_ctx *, const int64_t *, int32_t, int32_t, const uint8_t *, int32_t, int64_t *, double *, uint8_t *);
+    int (*amplicon_ratio)(ampli_ctx *, const int64_t *, int32_t, int32_t, const uint8_t *, const double *, const uint8_t *, int64_t *, double *, int32_t *,
+                          double *, double *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

@@ -18,6 +18,7 @@ namespace ampli {
 struct BedRow {
     std::string chrom;
     int start = -1, end = -1;
+    std::string name = ".", gene = "."; // columns 4 and 6 (the amplicon's id and its gene); "." where the row has no such column
 };
 
 // The panel: unique positions in order of first appearance in the BED walk

@@ -1,4 +1,5 @@
 // amplisolve_amd/csrc/host/host_api.cpp -- C ABI over the host library (include/amplisolve_host.h).
+#include <algorithm>
 #include <cstring>
 
 #include "../../../include/amplisolve_host.h"
@@ -304,6 +305,54 @@ extern "C" int ampli_host_contamination_estimate(const int64_t *sums, int64_t mi
 {
     if (!sums) return AMPLI_E_INVALID;
     return ampli_contamination_estimate(sums, min_sites, min_fraction, fraction, se, background);
+}
+
+// the BED rows and the position index of a panel as text, for tests: one line "R chrom start end name gene" per row, then "W" and the
+// walk, "D" and the dup flags, "P" and chrom:coord of every position; returns the length needed (the text is cut at cap - 1)
+extern "C" int64_t ampli_host_panel_describe(const char *bed_path, char *out, int64_t cap)
+{
+    try {
+        Panel p;
+        panel_from_bed(bed_path ? bed_path : "", p);
+        std::string s;
+        for (const BedRow &r : p.rows)
+            s += "R\t" + r.chrom + "\t" + std::to_string(r.start) + "\t" + std::to_string(r.end) + "\t" + r.name + "\t" + r.gene + "\n";
+        s += "W";
+        for (const uint32_t w : p.walk) s += " " + std::to_string(w);
+        s += "\nD";
+        for (const uint8_t d : p.dup) s += " " + std::to_string((int)d);
+        s += "\nP";
+        for (size_t i = 0; i < p.pos_coord.size(); ++i) s += " " + p.chroms[(size_t)p.pos_chrom[i]] + ":" + std::to_string(p.pos_coord[i]);
+        s += "\n";
+        for (size_t i = 0; i < p.pos_coord.size(); ++i)
+            if (p.find(p.chroms[(size_t)p.pos_chrom[i]], p.pos_coord[i]) != (int)i) return AMPLI_E_INVALID; // the index finds every position
+        if (out && cap > 0) {
+            const size_t n = std::min((size_t)cap - 1, s.size());
+            memcpy(out, s.data(), n);
+            out[n] = 0;
+        }
+        return (int64_t)s.size() + 1;
+    } catch (const Error &e) {
+        g_err = e.msg;
+        return e.code;
+    }
+}
+
+extern "C" double ampli_host_amplicon_median(const double *v, int64_t m)
+{
+    if (!v || m <= 0) return (double)NAN;
+    std::vector<double> w(v, v + m);
+    return ampli_amplicon_median(w.data(), m);
+}
+
+extern "C" double ampli_host_amplicon_z(double ratio, double med, double mad) { return ampli_amplicon_z(ratio, med, mad); }
+
+extern "C" double ampli_host_amplicon_share(int64_t d, int64_t total) { return ampli_amplicon_share(d, total); }
+
+extern "C" int ampli_host_amplicon_gene_status(int64_t n, double median_ratio, double median_z, int64_t min_amplicons, double gain_ratio,
+                                               double loss_ratio, double z_cutoff)
+{
+    return ampli_amplicon_gene_status(n, median_ratio, median_z, min_amplicons, gain_ratio, loss_ratio, z_cutoff);
 }
 
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)

@@ -61,21 +61,24 @@ void Panel::set_ref(uint32_t p, const std::string &base)
 }
 
 // Lines as `fscanf("%1000[^\n]\n")` + `sscanf("%s\t%d\t%d...")` see them (EE:615-633): blank lines vanish,
-// CR is whitespace, columns beyond the third are ignored here.
+// CR is whitespace, columns beyond the third do not enter the position index (the fourth and the sixth are kept with the row).
 void panel_from_bed(const std::string &bed_path, Panel &out)
 {
     std::ifstream in(bed_path);
     if (!in) throw Error{AMPLI_E_INVALID, "Cannot open file: " + bed_path};
     std::string line;
     while (std::getline(in, line)) {
-        char chrom[1024];
+        char chrom[1024], name[1024], gene[1024];
         int a = -1, b = -1;
         if (line.size() > 1000) line.resize(1000);
-        if (sscanf(line.c_str(), "%1000s %d %d", chrom, &a, &b) < 1) continue; // whitespace-only line
+        const int got = sscanf(line.c_str(), "%1000s %d %d %1000s %*s %1000s", chrom, &a, &b, name, gene);
+        if (got < 1) continue; // whitespace-only line
         BedRow r;
         r.chrom = chrom;
         r.start = a;
         r.end = b;
+        if (got >= 4) r.name = name; // the position index below does not depend on these two
+        if (got >= 5) r.gene = gene;
         out.rows.push_back(r);
         for (int idx = a; idx <= b; ++idx) {
             const size_t before = out.pos_coord.size();

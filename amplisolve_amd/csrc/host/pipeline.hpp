@@ -202,6 +202,16 @@ struct CtArgs {
 };
 int run_contamination(const CtArgs &a);
 
+// AmpliSolveAmpliconCoverage (ac_main.cpp, run_ac.cpp): which amplicons failed, and where the copy number is off against
+// the panel of normals.  tumour_dir "-" = the normals only; exclude_chrom: a comma list of chromosomes left out of library size and
+// centring, "-" = none; coverage_cutoff an integer >= 0, min_normals and min_amplicons integers >= 1, z_cutoff >= 0, gain_ratio > 1,
+// loss_ratio in (0, 1); exit status 0 / 1
+struct AcArgs {
+    std::string panel_design, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", min_normals = "5", min_amplicons = "3",
+                z_cutoff = "3", gain_ratio = "1.3", loss_ratio = "0.7", exclude_chrom = "chrX,chrY";
+};
+int run_amplicon_coverage(const AcArgs &a);
+
 // ---- the emitted calls ----
 // Where a record of a chunk came from: the data line of its sample's file (-1: absent) and the panel position of record slot r in
 // [0, P + E).  H is the Chunk, or a copy of these members that outlives it (leave-one-out's Resident).

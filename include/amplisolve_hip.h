@@ -111,6 +111,14 @@ extern "C" {
  *        call clears it itself where slices are added into it).  Nothing else is written -- the other chunks' rows of a larger matrix
  *        included -- and the records and both plane sets stay as they are.  Plane rows at and beyond n_samples / n_b and plane words
  *        at and beyond W are never read.
+ *   (C13) amplicon depth sums (tests/test_gpu_amplicon_contracts.py): d_sums of ampli_amplicon_depth_records is FULLY OVERWRITTEN, all
+ *        [recs->n_samples][A][4] sums, with plain stores (one wave owns a cell: nothing is cleared, nothing is added to), empty lists
+ *        included (four zeros).  Nothing else is written -- the other chunks' rows of a larger matrix included.  d_amp_off is read at
+ *        [0, A], d_amp_pos at [0, W) at most, a record only at a listed position below P of a row below n_samples.
+ *   (C14) amplicon reference: ampli_amplicon_reference FULLY OVERWRITES d_total [N], d_ref [A][2] and d_status [A] and writes nothing
+ *        else; d_sums and d_use stay as they are.
+ *   (C15) amplicon ratios: ampli_amplicon_ratio FULLY OVERWRITES d_total [S], d_centre [S], d_k [S], d_ratio [S][A] and d_z [S][A]
+ *        (a NaN is the quiet NaN 0x7FF8000000000000) and writes nothing else; d_sums, d_use, d_ref and d_status stay as they are.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -657,6 +665,68 @@ int ampli_concordance_pairs(ampli_ctx *ctx, int64_t P, const uint64_t *d_planes_
 #endif
 int ampli_contamination_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint64_t *d_planes_a, const uint64_t *d_planes_b,
                                 int32_t n_b, int64_t *d_sums);
+
+/*
+ * Amplicon coverage and copy ratio against the panel of normals (the definition, in plain numpy, is tests/amplicon_model.py).
+ *
+ * The amplicons are position lists, a CSR over the BED walk, IN DEVICE MEMORY: d_amp_off uint32 [A + 1], d_amp_pos uint32 [W] with
+ * entries in [0, P).  Lists may overlap, be in any order, name a position several times, and be empty.  That d_amp_off is monotone
+ * with d_amp_off[A] <= W and that the entries are below P is the caller's contract: the contents are NOT validated on the host
+ * (Context.amplicon_depth and AmpliSolveAmpliconCoverage build them).  The kernel still addresses nothing outside: list bounds are cut
+ * to [0, W] and an entry at or beyond P is skipped.
+ *
+ * amplicon_depth_records -- stage 1: for every sample s of the resident chunk and every amplicon a, four int64 sums over the entries p
+ * of a's list, from the PRIMARY record of (s, p) only (slot p < P; extras and an RD plane have no effect), in the order AMPLI_AMP_*:
+ *   PRESENT   += 1 where the record is present            DEPTH_FW += FW = fw[A] + fw[C] + fw[G] + fw[T]
+ *   CALLABLE  += 1 where FW >= cutoff and BW >= cutoff     DEPTH_BW += BW, likewise
+ * An absent record adds nothing.  A depth is below 2^27 with the 16- and 24-bit layouts and below 2^34 with int32 records, so with
+ * W < 2^28 no sum can leave int64: W >= 2^28 is AMPLI_E_RANGE, and there is no data-dependent check.  P >= 2^31 and
+ * n_samples > 2097120 are AMPLI_E_RANGE too.  AMPLI_E_INVALID: a null or misaligned pointer, P <= 0, A <= 0, W < 0, a negative
+ * cut-off, broken records.  On every refusal the output is untouched.
+ *   d_sums  int64 [recs->n_samples][A][4], 8-byte aligned, FULLY OVERWRITTEN with plain stores (C13).  A streamed cohort writes each
+ *           chunk into its rows of one matrix: pass d_sums + first_sample * A * 4.
+ * One form for every list length: a wave owns one amplicon and AMPLI_AMPLICON_STRIP consecutive rows; lists of up to 256 entries keep
+ * their indices in registers, longer ones are walked in rounds of 64 by the same wave (nothing is cut across waves, no atomics).
+ * Integers only: the same inputs give the same bytes.  Asynchronous on the context's stream.
+ *
+ * amplicon_reference -- stage 2a, from the sums of the N normals: d[n][a] = DEPTH_FW + DEPTH_BW; T[n] = sum of d[n][a] over use[a] != 0
+ * (int64); normal n is included iff T[n] > 0 (N_eff of them); x[n][a] = (double)d / (double)T[n]; med[a] = the median of x over the
+ * included normals, mad[a] = the median of |x - med[a]|; status[a] = AMPLI_AMPLICON_FEW if N_eff < min_normals, else _DARK if
+ * med[a] == 0, else _OK.  The median of m values in ascending order v is v[(m-1)/2] (m odd), (v[m/2-1] + v[m/2]) * 0.5 (m even),
+ * NaN (m == 0); it is found by selection on the bit patterns.
+ *   d_total int64 [N], d_ref double [A][2] (med, mad), d_status uint8 [A]: FULLY OVERWRITTEN (C14).
+ * AMPLI_E_INVALID: null or misaligned pointers, N <= 0, A <= 0, min_normals < 1.  AMPLI_E_RANGE: N > AMPLI_AMPLICON_MAX (what the
+ * workgroup's LDS buffer holds).
+ *
+ * amplicon_ratio -- stage 2b, for any S samples (tumours, or the normals themselves) from their sums and a reference: T[s] as above;
+ * r[s][a] = (d / T[s]) / med[a] where status[a] is OK and T[s] > 0, else NaN; K[s] = the number of amplicons with use[a] and OK
+ * (0 where T[s] <= 0), centre[s] = the median of r[s][a] over them (NaN where K[s] == 0); ratio[s][a] = r[s][a] / centre[s];
+ * z[s][a] = mad[a] > 0 ? ((ratio - 1.0) * med[a]) / (1.4826 * mad[a]) : NaN.  Every operation is an IEEE double operation in the
+ * written order (the library is built with -ffp-contract=off): the results equal the numpy model's bit for bit.
+ *   d_total int64 [S], d_centre double [S], d_k int32 [S], d_ratio, d_z double [S][A]: FULLY OVERWRITTEN (C15).
+ * AMPLI_E_INVALID as above; AMPLI_E_RANGE: A > AMPLI_AMPLICON_MAX.  Both are asynchronous on the context's stream.
+ */
+#ifndef AMPLI_AMP_SUMS /* also in csrc/ampli_math.h */
+#define AMPLI_AMP_PRESENT 0
+#define AMPLI_AMP_DEPTH_FW 1
+#define AMPLI_AMP_DEPTH_BW 2
+#define AMPLI_AMP_CALLABLE 3
+#define AMPLI_AMP_SUMS 4
+#define AMPLI_AMPLICON_OK 0
+#define AMPLI_AMPLICON_FEW 1
+#define AMPLI_AMPLICON_DARK 2
+#define AMPLI_AMPLICON_MAX 4096 /* N of amplicon_reference, A of amplicon_ratio: 32 KB of LDS */
+#define AMPLI_AMPLICON_STRIP 8  /* rows per wave of amplicon_depth_kernel */
+#define AMPLI_GENE_NEUTRAL 0
+#define AMPLI_GENE_GAIN 1
+#define AMPLI_GENE_LOSS 2
+#endif
+int ampli_amplicon_depth_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, int32_t A, const uint32_t *d_amp_off,
+                                 const uint32_t *d_amp_pos, int64_t W, int32_t coverage_cutoff, int64_t *d_sums);
+int ampli_amplicon_reference(ampli_ctx *ctx, const int64_t *d_sums, int32_t N, int32_t A, const uint8_t *d_use, int32_t min_normals,
+                             int64_t *d_total, double *d_ref, uint8_t *d_status);
+int ampli_amplicon_ratio(ampli_ctx *ctx, const int64_t *d_sums, int32_t S, int32_t A, const uint8_t *d_use, const double *d_ref,
+                         const uint8_t *d_status, int64_t *d_total, double *d_centre, int32_t *d_k, double *d_ratio, double *d_z);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

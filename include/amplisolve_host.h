@@ -201,6 +201,18 @@ int ampli_host_concordance_relation(int32_t het_either, int32_t het_match, int32
  * AMPLI_CONTAM_STATUS_UNDETERMINED when sites_hom + sites_het < min_sites, else _CONTAMINATED when fraction >= min_fraction, else
  * _CLEAN; AMPLI_E_INVALID (-1) when sums is NULL. */
 int ampli_host_contamination_estimate(const int64_t *sums, int64_t min_sites, double min_fraction, double *fraction, double *se, double *background);
+/* Amplicon copy ratio: csrc/ampli_math.h's functions, in double, unfused.  _median: the median of the m values of v that
+ * are not NaN (signed values; v is not changed), NaN if there is none or v is NULL.  _z: mad > 0 ? ((ratio - 1.0) * med) / (1.4826 * mad)
+ * : NaN.  _share: (double)d / (double)total.  _gene_status: AMPLI_GENE_GAIN / _LOSS / _NEUTRAL (include/amplisolve_hip.h). */
+double ampli_host_amplicon_median(const double *v, int64_t m);
+/* the BED rows (with the amplicon id of column 4 and the gene of column 6, "." where missing) and the position index of a panel as text,
+ * for tests: "R chrom start end name gene" per row, "W" + the walk, "D" + the dup flags, "P" + chrom:coord per position.  Returns the
+ * bytes needed, the NUL included (the text is cut at cap - 1), or a negative AMPLI_E_* code. */
+int64_t ampli_host_panel_describe(const char *bed_path, char *out, int64_t cap);
+double ampli_host_amplicon_z(double ratio, double med, double mad);
+double ampli_host_amplicon_share(int64_t d, int64_t total);
+int ampli_host_amplicon_gene_status(int64_t n, double median_ratio, double median_z, int64_t min_amplicons, double gain_ratio, double loss_ratio,
+                                    double z_cutoff);
 
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
