@@ -150,11 +150,18 @@ HIP_SYMBOLS = {
     "ampli_amplicon_depth_records": (C.c_int, [vp, C.POINTER(Records), i64, i32, vp, vp, i64, i32, vp]),
     "ampli_amplicon_reference": (C.c_int, [vp, vp, i32, i32, vp, i32, vp, vp, vp]),
     "ampli_amplicon_ratio": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ampli_spectrum_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, i32, i32, vp]),
+    "ampli_last_spectrum_segments": (C.c_int, [vp]),
 }
 
 class GenotypeParams(C.Structure):
     """mirror of ampli_genotype_params (the four _pm fields are per mille)"""
     _fields_ = [("min_depth", i32), ("absent_max_pm", i32), ("het_min_pm", i32), ("het_max_pm", i32), ("hom_min_pm", i32)]
+
+
+class SpectrumParams(C.Structure):
+    """mirror of ampli_spectrum_params (include/amplisolve_host.h)"""
+    _fields_ = [("min_sites", i64), ("min_normals", i64), ("excess_ratio", C.c_double), ("z_cutoff", C.c_double), ("asym_delta", C.c_double)]
 
 
 class HostShard(C.Structure):
@@ -231,6 +238,10 @@ HOST_SYMBOLS = {
     "ampli_host_amplicon_z": (C.c_double, [C.c_double, C.c_double, C.c_double]),
     "ampli_host_amplicon_share": (C.c_double, [i64, i64]),
     "ampli_host_amplicon_gene_status": (C.c_int, [i64, C.c_double, C.c_double, i64, C.c_double, C.c_double, C.c_double]),
+    "ampli_host_spectrum_enters_batch": (C.c_int, [vp, i64, vp, vp, i32, i32, i32, vp]),
+    "ampli_host_spectrum_class": (C.c_int, [i32, i32, i32]),
+    "ampli_host_spectrum_fold": (C.c_int, [vp, i64, vp, vp, vp, vp, vp]),
+    "ampli_host_spectrum_score": (C.c_int, [vp, vp, vp, i64, i64, C.POINTER(SpectrumParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
 }
 
 _hip = None

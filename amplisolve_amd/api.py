@@ -42,6 +42,16 @@ AMPLICON_OK, AMPLICON_FEW, AMPLICON_DARK = range(3)
 AMPLICON_MAX = 4096
 AMPLICON_STRIP = 8
 GENE_NEUTRAL, GENE_GAIN, GENE_LOSS = range(3)
+# the nine sums of Context.spectrum (AMPLI_SPEC_*), its limit of C and the rows a workgroup of the kernel owns, the classes, types and
+# channels of the command line's folds, and AMPLI_SPECTRUM_* of ampli_host_spectrum_score
+SPEC_SUMS = 9
+SPEC_SITES, SPEC_FW_A, SPEC_FW_C, SPEC_FW_G, SPEC_FW_T, SPEC_BW_A, SPEC_BW_C, SPEC_BW_G, SPEC_BW_T = range(9)
+SPECTRUM_MAX_CLASSES = 128
+SPECTRUM_STRIP = 4
+SPECTRUM_SKIP = 255
+SPECTRUM_CLASSES, SPECTRUM_TYPES, SPECTRUM_ALL, SPECTRUM_CHANNELS = 68, 13, 12, 96
+SPECTRUM_OK, SPECTRUM_LOW_SITES, SPECTRUM_NO_REFERENCE, SPECTRUM_ELEVATED, SPECTRUM_ASYMMETRIC = range(5)
+SPECTRUM_REF_OK, SPECTRUM_REF_FEW = range(2)
 
 
 def _ptr(t):
@@ -547,6 +557,37 @@ class Context:
         self._check(self.lib.ampli_amplicon_ratio(self.h, _ptr(sums), S, A, _ptr(use), _ptr(r), _ptr(st), _ptr(total), _ptr(centre), _ptr(k),
                                                   _ptr(ratio), _ptr(z)))
         return {"total": total, "centre": centre, "k": k, "ratio": ratio, "z": z}
+
+    def spectrum(self, rec: Records, P: int, ref_code, cls, C: int, cov: int = 100, max_alt_pm: int = 30, out=None):
+        """The nine class sums (SPEC_*) of every (sample of one resident chunk, class): int64 [n, C, 9] (ampli_spectrum_records).
+        ref_code and cls are uint8 [P]: the reference code (0..3) and the class (below C, or anything from C up -- 255 by convention --
+        to skip the position) of every position; device uint8 tensors, or host arrays, which are checked and uploaded.  Only the
+        primary records enter.  out: the chunk's rows of a larger matrix (a contiguous int64 [n, C, 9] view), overwritten."""
+        import ctypes  # the module's alias C is this method's number of classes
+
+        import numpy as np
+        import torch
+
+        def dev(x):
+            if isinstance(x, torch.Tensor):
+                return x
+            x = np.asarray(x)
+            assert x.dtype == np.uint8 and x.shape == (P,)
+            return torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+
+        ref_code, cls = dev(ref_code), dev(cls)
+        for t in (ref_code, cls):
+            assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (P,)
+        n = rec.n_samples
+        if out is None:
+            out = torch.empty((n, C, SPEC_SUMS), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, C, SPEC_SUMS)
+        self._check(self.lib.ampli_spectrum_records(self.h, ctypes.byref(rec), P, _ptr(ref_code), _ptr(cls), C, cov, max_alt_pm, _ptr(out)))
+        return out
+
+    def last_spectrum_segments(self) -> int:
+        """the number of position segments the last spectrum() launch was cut into (ampli_last_spectrum_segments)"""
+        return int(self.lib.ampli_last_spectrum_segments(self.h))
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

@@ -898,4 +898,205 @@ AMPLI_FN int ampli_amplicon_gene_status(int64_t n, double median_ratio, double m
     return AMPLI_GENE_NEUTRAL;
 }
 
+// ---------------------------------------------------------------------------
+// Substitution spectrum and strand asymmetry (the definition is tests/spectrum_model.py).
+//
+// Stage 1, integers (spectrum_kernel and ampli_host_spectrum_enters_batch run ampli_spectrum_enters): the PRIMARY record of (sample,
+// position) enters iff it is present, the position's reference code is 0..3 and its class is below C, FW >= cutoff and BW >= cutoff,
+// and every base b other than the reference has 1000 n_b <= max_alt_pm d (n_b = fw[b] + bw[b], d = FW + BW, all in int64: an int32
+// record may hold counts near 2^31).  d == 0 passes the last clause and is stopped only by a positive cut-off.  An entering record
+// adds 1 and its eight counts to the nine sums of (sample, class), index order AMPLI_SPEC_*.
+//
+// Stage 2, on the host, every operation one IEEE double operation in the written order (unfused, -ffp-contract=off):
+//   classes of the command line  16 r + 4 l + t with r the reference code and l, t the codes of the panel's own reference bases at
+//           coordinate - 1 / + 1 of the same chromosome; 64 + r where a neighbour is missing or not A/C/G/T; 255 where r is not 0..3
+//   types   ty = 3 r + k, k counting the alternatives in A,C,G,T order without r; type 12 (ALL) pools the twelve
+//   fold    ALT[st][ty] = sum over the classes with that r of count[st][y]; DEP[st][ty] = sum over them of the four counts of strand
+//           st (the same for the three types of one r); SITES[ty] likewise; ALL: the sums over every class
+//   rates   rate[st] = DEP[st] > 0 ? ALT[st] / DEP[st] : NaN; rate2 = DEP_fw + DEP_bw > 0 ? (ALT_fw + ALT_bw) / (DEP_fw + DEP_bw) : NaN;
+//           asym = rate_fw + rate_bw > 0 ? rate_fw / (rate_fw + rate_bw) : NaN
+//   reference, per type, from the normals with SITES >= min_sites (N_eff of them): med, mad of rate2 and med_a, mad_a of asym by
+//           ampli_amplicon_median (NaNs dropped); FEW if N_eff < min_normals
+//   score   ratio = med > 0 ? rate2 / med : NaN; z = mad > 0 ? (rate2 - med) / (1.4826 mad) : NaN; za likewise from asym
+//   flag    LOW_SITES if SITES < min_sites, else NO_REFERENCE if FEW, else ELEVATED if ratio >= excess_ratio and z >= z_cutoff, else
+//           ASYMMETRIC if |za| >= z_cutoff and |asym - med_a| >= asym_delta, else OK; a comparison with NaN is false
+//   96 channels  the classes below 64 folded onto a pyrimidine reference base (r in {A, G}: r' = 3 - r, l' = 3 - t, t' = 3 - l,
+//           y' = 3 - y), both strands summed: channel 16 sub + 4 l' + t', sub = (r' == T ? 3 : 0) + k' -- C>A C>G C>T T>A T>C T>G
+// ---------------------------------------------------------------------------
+#ifndef AMPLI_SPEC_SUMS // also in include/amplisolve_hip.h, which this header does not need
+#define AMPLI_SPEC_SITES 0
+#define AMPLI_SPEC_FW_A 1
+#define AMPLI_SPEC_FW_C 2
+#define AMPLI_SPEC_FW_G 3
+#define AMPLI_SPEC_FW_T 4
+#define AMPLI_SPEC_BW_A 5
+#define AMPLI_SPEC_BW_C 6
+#define AMPLI_SPEC_BW_G 7
+#define AMPLI_SPEC_BW_T 8
+#define AMPLI_SPEC_SUMS 9
+#define AMPLI_SPECTRUM_MAX_CLASSES 128
+#define AMPLI_SPECTRUM_STRIP 4
+#define AMPLI_SPECTRUM_SKIP 255
+#define AMPLI_SPECTRUM_CLASSES 68
+#define AMPLI_SPECTRUM_TYPES 13
+#define AMPLI_SPECTRUM_ALL 12
+#define AMPLI_SPECTRUM_CHANNELS 96
+#define AMPLI_SPECTRUM_OK 0
+#define AMPLI_SPECTRUM_LOW_SITES 1
+#define AMPLI_SPECTRUM_NO_REFERENCE 2
+#define AMPLI_SPECTRUM_ELEVATED 3
+#define AMPLI_SPECTRUM_ASYMMETRIC 4
+#define AMPLI_SPECTRUM_REF_OK 0
+#define AMPLI_SPECTRUM_REF_FEW 1
+#endif
+#ifndef AMPLI_SPECTRUM_PARAMS_DEFINED // also in include/amplisolve_host.h
+#define AMPLI_SPECTRUM_PARAMS_DEFINED
+typedef struct ampli_spectrum_params {
+    int64_t min_sites, min_normals;
+    double excess_ratio, z_cutoff, asym_delta;
+} ampli_spectrum_params;
+#endif
+
+// the gate of one record, without a branch on the data: every clause is evaluated and the results are and-ed
+AMPLI_FN int ampli_spectrum_enters(const int32_t fw[4], const int32_t bw[4], int present, uint32_t ref, uint32_t cls, int32_t C, int32_t cutoff,
+                                   int32_t max_alt_pm)
+{
+    int64_t n[4], FW = 0, BW = 0;
+    for (int b = 0; b < 4; ++b) {
+        n[b] = (int64_t)fw[b] + (int64_t)bw[b];
+        FW += (int64_t)fw[b];
+        BW += (int64_t)bw[b];
+    }
+    const int64_t lim = (int64_t)max_alt_pm * (FW + BW);
+    int ok = present != 0 && ref <= 3u && cls < (uint32_t)C && FW >= (int64_t)cutoff && BW >= (int64_t)cutoff;
+    for (int b = 0; b < 4; ++b) ok &= ((uint32_t)b == ref) | (1000 * n[b] <= lim);
+    return ok;
+}
+
+// the code of one reference-base string as a neighbour sees it: upper-cased, one of A C G T, else 255
+AMPLI_FN uint32_t ampli_spectrum_base_code(const char *s)
+{
+    if (!s || !s[0] || s[1]) return 255u;
+    const char c = (char)(s[0] >= 'a' && s[0] <= 'z' ? s[0] - 'a' + 'A' : s[0]);
+    return c == 'A' ? 0u : c == 'C' ? 1u : c == 'G' ? 2u : c == 'T' ? 3u : 255u;
+}
+
+// the class of a position from its reference code and its neighbours' codes (255: no such neighbour, or not A/C/G/T)
+AMPLI_FN uint32_t ampli_spectrum_class(uint32_t r, uint32_t l, uint32_t t)
+{
+    if (r > 3u) return AMPLI_SPECTRUM_SKIP;
+    return (l <= 3u && t <= 3u) ? 16u * r + 4u * l + t : 64u + r;
+}
+
+// the index of alternative y among A,C,G,T without r (y != r)
+AMPLI_FN int ampli_spectrum_alt_index(int r, int y) { return y < r ? y : y - 1; }
+
+// the sums of one sample, int64 [68][9], folded: alt, dep [2][13], sites [13], and the 96 channels (ctx_alt, ctx_dep; both may be NULL)
+AMPLI_FN void ampli_spectrum_fold(const int64_t *sums, int64_t *alt, int64_t *dep, int64_t *sites, int64_t *ctx_alt, int64_t *ctx_dep)
+{
+    const int T = AMPLI_SPECTRUM_TYPES;
+    for (int i = 0; i < 2 * T; ++i) alt[i] = dep[i] = 0;
+    for (int i = 0; i < T; ++i) sites[i] = 0;
+    if (ctx_alt && ctx_dep)
+        for (int i = 0; i < AMPLI_SPECTRUM_CHANNELS; ++i) ctx_alt[i] = ctx_dep[i] = 0;
+    for (int c = 0; c < AMPLI_SPECTRUM_CLASSES; ++c) {
+        const int64_t *v = sums + (size_t)c * AMPLI_SPEC_SUMS;
+        const int r = c < 64 ? c >> 4 : c - 64;
+        int64_t depth[2];
+        for (int st = 0; st < 2; ++st) {
+            depth[st] = v[1 + 4 * st] + v[2 + 4 * st] + v[3 + 4 * st] + v[4 + 4 * st];
+            for (int k = 0; k < 3; ++k) dep[st * T + 3 * r + k] += depth[st];
+            dep[st * T + AMPLI_SPECTRUM_ALL] += depth[st];
+            for (int y = 0; y < 4; ++y) {
+                if (y == r) continue;
+                alt[st * T + 3 * r + ampli_spectrum_alt_index(r, y)] += v[1 + 4 * st + y];
+                alt[st * T + AMPLI_SPECTRUM_ALL] += v[1 + 4 * st + y];
+            }
+        }
+        for (int k = 0; k < 3; ++k) sites[3 * r + k] += v[AMPLI_SPEC_SITES];
+        sites[AMPLI_SPECTRUM_ALL] += v[AMPLI_SPEC_SITES];
+        if (c >= 64 || !ctx_alt || !ctx_dep) continue;
+        const int l = (c >> 2) & 3, t = c & 3, pyr = r == 1 || r == 3;
+        const int r2 = pyr ? r : 3 - r, l2 = pyr ? l : 3 - t, t2 = pyr ? t : 3 - l;
+        for (int y = 0; y < 4; ++y) {
+            if (y == r) continue;
+            const int y2 = pyr ? y : 3 - y;
+            const int ch = 16 * ((r2 == 3 ? 3 : 0) + ampli_spectrum_alt_index(r2, y2)) + 4 * l2 + t2;
+            ctx_alt[ch] += v[1 + y] + v[5 + y];
+            ctx_dep[ch] += depth[0] + depth[1];
+        }
+    }
+}
+
+// the rates of one (sample, type) from its strand sums
+AMPLI_FN void ampli_spectrum_rates(int64_t alt_fw, int64_t dep_fw, int64_t alt_bw, int64_t dep_bw, double *rate_fw, double *rate_bw, double *rate2,
+                                   double *asym)
+{
+    const double rf = dep_fw > 0 ? (double)alt_fw / (double)dep_fw : (double)NAN;
+    const double rb = dep_bw > 0 ? (double)alt_bw / (double)dep_bw : (double)NAN;
+    const double sum = rf + rb;
+    *rate_fw = rf;
+    *rate_bw = rb;
+    *rate2 = dep_fw + dep_bw > 0 ? (double)(alt_fw + alt_bw) / (double)(dep_fw + dep_bw) : (double)NAN;
+    *asym = sum > 0.0 ? rf / sum : (double)NAN;
+}
+
+// (x - med) / (1.4826 mad), NaN unless mad > 0
+AMPLI_FN double ampli_spectrum_z(double x, double med, double mad)
+{
+    if (!(mad > 0.0)) return (double)NAN;
+    const double num = x - med;
+    const double den = 1.4826 * mad;
+    return num / den;
+}
+
+AMPLI_FN int ampli_spectrum_flag(int64_t sites, int few, double ratio, double z, double asym, double med_a, double za, const ampli_spectrum_params *q)
+{
+    if (sites < q->min_sites) return AMPLI_SPECTRUM_LOW_SITES;
+    if (few) return AMPLI_SPECTRUM_NO_REFERENCE;
+    if (ratio >= q->excess_ratio && z >= q->z_cutoff) return AMPLI_SPECTRUM_ELEVATED;
+    if (fabs(za) >= q->z_cutoff && fabs(asym - med_a) >= q->asym_delta) return AMPLI_SPECTRUM_ASYMMETRIC;
+    return AMPLI_SPECTRUM_OK;
+}
+
+// The score of S samples, the first N of them the normals, from their folds alt, dep int64 [S][2][13] and sites int64 [S][13].
+// tmp: N doubles of scratch.  ref double [13][4] = med, mad, med_a, mad_a; n_eff int32 [13]; status uint8 [13] (AMPLI_SPECTRUM_REF_*);
+// rate2, ratio, z, asym, za double [S][13]; flag uint8 [S][13] (AMPLI_SPECTRUM_OK ...).
+AMPLI_FN void ampli_spectrum_score(const int64_t *alt, const int64_t *dep, const int64_t *sites, int64_t S, int64_t N, const ampli_spectrum_params *q,
+                                   double *tmp, double *ref, int32_t *n_eff, uint8_t *status, double *rate2, double *ratio, double *z, double *asym,
+                                   double *za, uint8_t *flag)
+{
+    const int T = AMPLI_SPECTRUM_TYPES;
+    for (int64_t s = 0; s < S; ++s)
+        for (int ty = 0; ty < T; ++ty) {
+            const int64_t *a = alt + s * 2 * T, *d = dep + s * 2 * T;
+            double rf, rb;
+            ampli_spectrum_rates(a[ty], d[ty], a[T + ty], d[T + ty], &rf, &rb, &rate2[s * T + ty], &asym[s * T + ty]);
+        }
+    for (int ty = 0; ty < T; ++ty) {
+        double *r = ref + 4 * ty;
+        for (int pass = 0; pass < 2; ++pass) { // rate2, then asym
+            const double *x = pass ? asym : rate2;
+            int64_t m = 0;
+            for (int64_t n = 0; n < N; ++n)
+                if (sites[n * T + ty] >= q->min_sites) tmp[m++] = x[n * T + ty];
+            if (!pass) n_eff[ty] = (int32_t)m;
+            const double med = ampli_amplicon_median(tmp, m);
+            m = 0;
+            for (int64_t n = 0; n < N; ++n)
+                if (sites[n * T + ty] >= q->min_sites) tmp[m++] = fabs(x[n * T + ty] - med);
+            r[2 * pass] = med;
+            r[2 * pass + 1] = ampli_amplicon_median(tmp, m);
+        }
+        status[ty] = (uint8_t)((int64_t)n_eff[ty] < q->min_normals ? AMPLI_SPECTRUM_REF_FEW : AMPLI_SPECTRUM_REF_OK);
+        for (int64_t s = 0; s < S; ++s) {
+            const int64_t i = s * T + ty;
+            ratio[i] = r[0] > 0.0 ? rate2[i] / r[0] : (double)NAN;
+            z[i] = ampli_spectrum_z(rate2[i], r[0], r[1]);
+            za[i] = ampli_spectrum_z(asym[i], r[2], r[3]);
+            flag[i] = (uint8_t)ampli_spectrum_flag(sites[i], status[ty] == AMPLI_SPECTRUM_REF_FEW, ratio[i], z[i], asym[i], r[2], za[i], q);
+        }
+    }
+}
+
 #endif

@@ -74,6 +74,7 @@ struct HipApi {
     int (*amplicon_reference)(ampli_ctx *, const int64_t *, int32_t, int32_t, const uint8_t *, int32_t, int64_t *, double *, uint8_t *);
     int (*amplicon_ratio)(ampli_ctx *, const int64_t *, int32_t, int32_t, const uint8_t *, const double *, const uint8_t *, int64_t *, double *, int32_t *,
                           double *, double *);
+    int (*spectrum_records)(ampli_ctx *, const ampli_records *, int64_t, const uint8_t *, const uint8_t *, int32_t, int32_t, int32_t, int64_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

@@ -355,6 +355,42 @@ extern "C" int ampli_host_amplicon_gene_status(int64_t n, double median_ratio, d
     return ampli_amplicon_gene_status(n, median_ratio, median_z, min_amplicons, gain_ratio, loss_ratio, z_cutoff);
 }
 
+extern "C" int ampli_host_spectrum_enters_batch(const int32_t *recs, int64_t count, const uint8_t *ref_code, const uint8_t *cls, int32_t C,
+                                                int32_t coverage_cutoff, int32_t max_alt_pm, uint8_t *enters)
+{
+    if (!recs || !ref_code || !cls || !enters || count < 0 || C < 1 || C > AMPLI_SPECTRUM_MAX_CLASSES || coverage_cutoff < 0 || max_alt_pm < 0 ||
+        max_alt_pm > 1000)
+        return AMPLI_E_INVALID;
+    for (int64_t i = 0; i < count; ++i)
+        enters[i] = (uint8_t)ampli_spectrum_enters(recs + i * 8, recs + i * 8 + 4, recs[i * 8] != AMPLI_ABSENT, ref_code[i], cls[i], C, coverage_cutoff,
+                                                   max_alt_pm);
+    return 0;
+}
+
+extern "C" int ampli_host_spectrum_class(int32_t r, int32_t l, int32_t t) { return (int)ampli_spectrum_class((uint32_t)r, (uint32_t)l, (uint32_t)t); }
+
+extern "C" int ampli_host_spectrum_fold(const int64_t *sums, int64_t S, int64_t *alt, int64_t *dep, int64_t *sites, int64_t *ctx_alt, int64_t *ctx_dep)
+{
+    if (!sums || !alt || !dep || !sites || S < 0) return AMPLI_E_INVALID;
+    const bool ctx = ctx_alt && ctx_dep;
+    for (int64_t s = 0; s < S; ++s)
+        ampli_spectrum_fold(sums + s * AMPLI_SPECTRUM_CLASSES * AMPLI_SPEC_SUMS, alt + s * 2 * AMPLI_SPECTRUM_TYPES, dep + s * 2 * AMPLI_SPECTRUM_TYPES,
+                            sites + s * AMPLI_SPECTRUM_TYPES, ctx ? ctx_alt + s * AMPLI_SPECTRUM_CHANNELS : nullptr,
+                            ctx ? ctx_dep + s * AMPLI_SPECTRUM_CHANNELS : nullptr);
+    return 0;
+}
+
+extern "C" int ampli_host_spectrum_score(const int64_t *alt, const int64_t *dep, const int64_t *sites, int64_t S, int64_t N, const ampli_spectrum_params *prm,
+                                         double *ref, int32_t *n_eff, uint8_t *status, double *rate2, double *ratio, double *z, double *asym, double *za,
+                                         uint8_t *flag)
+{
+    if (!alt || !dep || !sites || !prm || !ref || !n_eff || !status || !rate2 || !ratio || !z || !asym || !za || !flag || S <= 0 || N < 0 || N > S)
+        return AMPLI_E_INVALID;
+    std::vector<double> tmp((size_t)N + 1);
+    ampli_spectrum_score(alt, dep, sites, S, N, prm, tmp.data(), ref, n_eff, status, rate2, ratio, z, asym, za, flag);
+    return 0;
+}
+
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)
 {
     try {

@@ -1,4 +1,4 @@
-// amplisolve_amd/csrc/host/pipeline.hpp -- what the command lines (run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp) share.
+// amplisolve_amd/csrc/host/pipeline.hpp -- what the command lines (run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp, run_ct.cpp, run_ac.cpp, run_ss.cpp) share.
 // Internal to those files and pipeline.cpp; the commands themselves are declared in host.hpp.
 #pragma once
 #include <algorithm>
@@ -211,6 +211,16 @@ struct AcArgs {
                 z_cutoff = "3", gain_ratio = "1.3", loss_ratio = "0.7", exclude_chrom = "chrX,chrY";
 };
 int run_amplicon_coverage(const AcArgs &a);
+
+// AmpliSolveSubstitutionSpectrum (ss_main.cpp, run_ss.cpp): which kind of error a file makes more of than the panel of
+// normals does, per strand-resolved substitution type and per read strand.  tumour_dir "-" = the normals only; coverage_cutoff an
+// integer >= 0, max_alt_pm an integer in [0, 1000], min_sites and min_normals integers >= 1, excess_ratio > 1, z_cutoff >= 0,
+// asym_delta in [0, 1]; refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
+struct SsArgs {
+    std::string panel_design, reference_genome, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", max_alt_pm = "30",
+                min_sites = "200", min_normals = "5", excess_ratio = "3", z_cutoff = "10", asym_delta = "0.15", refbases_file;
+};
+int run_substitution_spectrum(const SsArgs &a);
 
 // ---- the emitted calls ----
 // Where a record of a chunk came from: the data line of its sample's file (-1: absent) and the panel position of record slot r in

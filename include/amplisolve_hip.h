@@ -119,6 +119,11 @@ extern "C" {
  *        else; d_sums and d_use stay as they are.
  *   (C15) amplicon ratios: ampli_amplicon_ratio FULLY OVERWRITES d_total [S], d_centre [S], d_k [S], d_ratio [S][A] and d_z [S][A]
  *        (a NaN is the quiet NaN 0x7FF8000000000000) and writes nothing else; d_sums, d_use, d_ref and d_status stay as they are.
+ *   (C16) substitution spectrum (tests/test_gpu_spectrum_contracts.py): d_sums of ampli_spectrum_records is FULLY OVERWRITTEN, all
+ *        [recs->n_samples][C][9] sums, whatever it held and however many position segments the launch is cut into (the call clears it
+ *        itself where segments are added into it); a class no position has gets nine zeros.  Nothing else is written -- the other
+ *        chunks' rows of a larger matrix included.  d_ref_code and d_class are read at [0, P), a record only at a position below P
+ *        whose reference code and class are valid, of a row below n_samples.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -727,6 +732,65 @@ int ampli_amplicon_reference(ampli_ctx *ctx, const int64_t *d_sums, int32_t N, i
                              int64_t *d_total, double *d_ref, uint8_t *d_status);
 int ampli_amplicon_ratio(ampli_ctx *ctx, const int64_t *d_sums, int32_t S, int32_t A, const uint8_t *d_use, const double *d_ref,
                          const uint8_t *d_status, int64_t *d_total, double *d_centre, int32_t *d_k, double *d_ratio, double *d_z);
+
+/*
+ * Substitution spectrum and strand asymmetry (the definition, in plain numpy, is tests/spectrum_model.py).
+ *
+ * spectrum_records -- for every sample s of the resident chunk and every class c < C, nine int64 sums over the positions p with
+ * d_class[p] == c whose PRIMARY record (s, p) ENTERS (slot p < P; extras and an RD plane have no effect), in the order AMPLI_SPEC_*:
+ *   SITES += 1        FW_A .. FW_T += fw[b]        BW_A .. BW_T += bw[b]        (the reference base's own counts included)
+ * With FW = sum fw[b], BW = sum bw[b], n_b = fw[b] + bw[b] and d = FW + BW, all in int64, the record enters iff it is present,
+ * d_ref_code[p] is 0..3 (A C G T) and d_class[p] < C, FW >= coverage_cutoff and BW >= coverage_cutoff, and 1000 n_b <= max_alt_pm d
+ * for every base b other than the reference: the position is background for this file, not a germline or a clear somatic variant.
+ * The gate is all or nothing per position; d == 0 passes its last clause and is stopped only by a positive cut-off.  This is
+ * csrc/ampli_math.h's ampli_spectrum_enters, which the host library exports (ampli_host_spectrum_enters_batch).
+ *   d_ref_code uint8 [P]; d_class uint8 [P]: a class in [0, C), or AMPLI_SPECTRUM_SKIP (255) -- any value at or above C skips the
+ *           position: no bin at or beyond C is ever addressed; C in [1, AMPLI_SPECTRUM_MAX_CLASSES]
+ *   d_sums  int64 [recs->n_samples][C][9], 8-byte aligned, FULLY OVERWRITTEN (C16).  A streamed cohort writes each chunk into its rows
+ *           of one matrix: pass d_sums + first_sample * C * 9.
+ * A field is below 2^24 with the 16- and 24-bit layouts and below 2^31 with int32 records, and P >= 2^31 is AMPLI_E_RANGE, so no sum
+ * can leave int64 and there is no data-dependent check.  AMPLI_E_RANGE too: C > AMPLI_SPECTRUM_MAX_CLASSES.  AMPLI_E_INVALID: a null
+ * pointer, a misaligned d_sums, P <= 0, C <= 0, a negative cut-off, max_alt_pm outside [0, 1000], broken records.  On every refusal
+ * the output is untouched.
+ * The form: a workgroup of four waves owns AMPLI_SPECTRUM_STRIP consecutive rows and one segment of the positions; its waves take
+ * the segment's 64-position tiles in turn, and an entering lane adds its values into the workgroup's LDS bins [row][class][9] with
+ * 64-bit LDS atomics.  With one segment the bins are stored; with several they are added with 64-bit integer atomics onto the
+ * matrix the call cleared.  The segments: a launch without them is strips = ceil(n_samples / AMPLI_SPECTRUM_STRIP) workgroups;
+ * while that is fewer than 8 per compute unit, the T = ceil(P / 64) tiles are cut into
+ *   segments = ceil(T / tps), tps = max(16, ceil(T / want)), want = min(64, ceil(8 n_cu / strips))
+ * -- so every panel of up to 1024 positions is one segment.  ampli_last_spectrum_segments: the number of the context's last launch
+ * (as ampli_last_reduce_kernel; AMPLI_E_INVALID before the first).  Integers only: the same inputs give the same bytes, whatever
+ * the order the segments arrive in.  Asynchronous on the context's stream.
+ */
+#ifndef AMPLI_SPEC_SUMS /* also in csrc/ampli_math.h */
+#define AMPLI_SPEC_SITES 0
+#define AMPLI_SPEC_FW_A 1
+#define AMPLI_SPEC_FW_C 2
+#define AMPLI_SPEC_FW_G 3
+#define AMPLI_SPEC_FW_T 4
+#define AMPLI_SPEC_BW_A 5
+#define AMPLI_SPEC_BW_C 6
+#define AMPLI_SPEC_BW_G 7
+#define AMPLI_SPEC_BW_T 8
+#define AMPLI_SPEC_SUMS 9
+#define AMPLI_SPECTRUM_MAX_CLASSES 128
+#define AMPLI_SPECTRUM_STRIP 4    /* rows per workgroup of spectrum_kernel */
+#define AMPLI_SPECTRUM_SKIP 255
+#define AMPLI_SPECTRUM_CLASSES 68 /* the command line's classes: 64 trinucleotide contexts and 4 edge classes */
+#define AMPLI_SPECTRUM_TYPES 13   /* twelve strand-resolved substitution types and ALL */
+#define AMPLI_SPECTRUM_ALL 12
+#define AMPLI_SPECTRUM_CHANNELS 96
+#define AMPLI_SPECTRUM_OK 0
+#define AMPLI_SPECTRUM_LOW_SITES 1
+#define AMPLI_SPECTRUM_NO_REFERENCE 2
+#define AMPLI_SPECTRUM_ELEVATED 3
+#define AMPLI_SPECTRUM_ASYMMETRIC 4
+#define AMPLI_SPECTRUM_REF_OK 0
+#define AMPLI_SPECTRUM_REF_FEW 1
+#endif
+int ampli_spectrum_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint8_t *d_ref_code, const uint8_t *d_class, int32_t C,
+                           int32_t coverage_cutoff, int32_t max_alt_pm, int64_t *d_sums);
+int ampli_last_spectrum_segments(const ampli_ctx *ctx);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

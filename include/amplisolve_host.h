@@ -214,6 +214,33 @@ double ampli_host_amplicon_share(int64_t d, int64_t total);
 int ampli_host_amplicon_gene_status(int64_t n, double median_ratio, double median_z, int64_t min_amplicons, double gain_ratio, double loss_ratio,
                                     double z_cutoff);
 
+/* Substitution spectrum (the definition is tests/spectrum_model.py): csrc/ampli_math.h's functions, integers and unfused doubles.
+ * _enters_batch: the gate of `count` records (int32 [count][8], absent: field 0 == INT32_MIN) with their positions' reference codes and
+ *   classes (uint8 [count] each) -- ampli_spectrum_enters, what spectrum_kernel runs -- as 0 / 1 in enters.  Returns 0, or
+ *   AMPLI_E_INVALID (-1) with nothing written for a null pointer, count < 0, C outside [1, 128], a negative cut-off or max_alt_pm
+ *   outside [0, 1000].
+ * _class: 16 r + 4 l + t, 64 + r where a neighbour's code is not 0..3, 255 where r is not.
+ * _fold: the sums of S samples, int64 [S][68][9] (the command line's classes), into alt and dep int64 [S][2][13] (strand, type; type 12
+ *   is ALL), sites int64 [S][13] and the 96 channels ctx_alt, ctx_dep int64 [S][96] (both may be NULL).
+ * _score: the reference from the first N samples (the normals) and the score of all S: ref double [13][4] = med, mad, med_a, mad_a;
+ *   n_eff int32 [13]; status uint8 [13] (AMPLI_SPECTRUM_REF_*); rate2, ratio, z, asym, za double [S][13]; flag uint8 [S][13]
+ *   (AMPLI_SPECTRUM_OK, _LOW_SITES, _NO_REFERENCE, _ELEVATED, _ASYMMETRIC of include/amplisolve_hip.h).  Returns 0, or AMPLI_E_INVALID
+ *   for a null pointer, S <= 0 or N outside [0, S]. */
+#ifndef AMPLI_SPECTRUM_PARAMS_DEFINED /* also in csrc/ampli_math.h */
+#define AMPLI_SPECTRUM_PARAMS_DEFINED
+typedef struct ampli_spectrum_params {
+    int64_t min_sites, min_normals;
+    double excess_ratio, z_cutoff, asym_delta;
+} ampli_spectrum_params;
+#endif
+int ampli_host_spectrum_enters_batch(const int32_t *recs, int64_t count, const uint8_t *ref_code, const uint8_t *cls, int32_t C, int32_t coverage_cutoff,
+                                     int32_t max_alt_pm, uint8_t *enters);
+int ampli_host_spectrum_class(int32_t r, int32_t l, int32_t t);
+int ampli_host_spectrum_fold(const int64_t *sums, int64_t S, int64_t *alt, int64_t *dep, int64_t *sites, int64_t *ctx_alt, int64_t *ctx_dep);
+int ampli_host_spectrum_score(const int64_t *alt, const int64_t *dep, const int64_t *sites, int64_t S, int64_t N, const ampli_spectrum_params *prm,
+                              double *ref, int32_t *n_eff, uint8_t *status, double *rate2, double *ratio, double *z, double *asym, double *za,
+                              uint8_t *flag);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
