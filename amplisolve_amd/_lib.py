@@ -152,6 +152,7 @@ HIP_SYMBOLS = {
     "ampli_amplicon_ratio": (C.c_int, [vp, vp, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ampli_spectrum_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, i32, i32, vp]),
     "ampli_last_spectrum_segments": (C.c_int, [vp]),
+    "ampli_exceedance_records": (C.c_int, [vp, C.POINTER(Records), C.POINTER(Records), i64, vp, i32, i32, i64, i64, i32, i32, vp, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -162,6 +163,11 @@ class GenotypeParams(C.Structure):
 class SpectrumParams(C.Structure):
     """mirror of ampli_spectrum_params (include/amplisolve_host.h)"""
     _fields_ = [("min_sites", i64), ("min_normals", i64), ("excess_ratio", C.c_double), ("z_cutoff", C.c_double), ("asym_delta", C.c_double)]
+
+
+class ExceedanceParams(C.Structure):
+    """mirror of ampli_exceedance_params (include/amplisolve_host.h)"""
+    _fields_ = [("min_alt_reads", i64), ("min_vaf_pm", i64), ("min_normals", i64), ("max_normals", i64)]
 
 
 class HostShard(C.Structure):
@@ -242,6 +248,7 @@ HOST_SYMBOLS = {
     "ampli_host_spectrum_class": (C.c_int, [i32, i32, i32]),
     "ampli_host_spectrum_fold": (C.c_int, [vp, i64, vp, vp, vp, vp, vp]),
     "ampli_host_spectrum_score": (C.c_int, [vp, vp, vp, i64, i64, C.POINTER(SpectrumParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
+    "ampli_host_exceedance_candidate_batch": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(ExceedanceParams), vp]),
 }
 
 _hip = None

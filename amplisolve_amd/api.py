@@ -52,6 +52,12 @@ SPECTRUM_SKIP = 255
 SPECTRUM_CLASSES, SPECTRUM_TYPES, SPECTRUM_ALL, SPECTRUM_CHANNELS = 68, 13, 12, 96
 SPECTRUM_OK, SPECTRUM_LOW_SITES, SPECTRUM_NO_REFERENCE, SPECTRUM_ELEVATED, SPECTRUM_ASYMMETRIC = range(5)
 SPECTRUM_REF_OK, SPECTRUM_REF_FEW = range(2)
+# Context.exceedance (AMPLI_EXCEEDANCE_*): the value of a cell that is not evaluated, the most normals of a panel, the normal rows the
+# kernel decodes into LDS at a time and the tumour rows of one of its workgroups
+EXCEEDANCE_NA = 0xFFFF
+EXCEEDANCE_MAX_NORMALS = 65534
+EXCEEDANCE_STRIP = 8
+EXCEEDANCE_ROWS = 8
 
 
 def _ptr(t):
@@ -588,6 +594,36 @@ class Context:
     def last_spectrum_segments(self) -> int:
         """the number of position segments the last spectrum() launch was cut into (ampli_last_spectrum_segments)"""
         return int(self.lib.ampli_last_spectrum_segments(self.h))
+
+    def exceedance(self, tumours: Records, normals: Records, P: int, ref_code, normal_cutoff: int = 100, calling_cutoff: int = 100, first_t: int = 0,
+                   first_n: int = 0, skip_same_index: bool = False, accumulate: bool = False, elig=None, ge=None):
+        """How many normals of one resident chunk reach every tumour row of another at every (position, base, strand)
+        (ampli_exceedance_records): (elig int16 [n_t, P], ge int16 [n_t, P, 4, 2]), to be read as unsigned 16-bit counts
+        (torch has no arithmetic on uint16: .cpu().numpy().view(numpy.uint16)); a cell of ge that is not evaluated holds EXCEEDANCE_NA.
+        ref_code is uint8 [P], a device tensor or a host array.  first_t, first_n: the global indices of the chunks' first rows;
+        skip_same_index leaves out the normal with a tumour row's own global index.  accumulate adds this chunk's normals onto the
+        elig and ge of the earlier chunks, which must then be given."""
+        import ctypes
+
+        import numpy as np
+        import torch
+
+        if not isinstance(ref_code, torch.Tensor):
+            ref_code = np.asarray(ref_code)
+            assert ref_code.dtype == np.uint8 and ref_code.shape == (P,)
+            ref_code = torch.from_numpy(np.ascontiguousarray(ref_code)).to(self.device)
+        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        n_t = tumours.n_samples
+        assert not accumulate or (elig is not None and ge is not None), "accumulate adds onto the outputs of the earlier chunks"
+        if elig is None:
+            elig = torch.empty((n_t, P), dtype=torch.int16, device=self.device)
+        if ge is None:
+            ge = torch.empty((n_t, P, 4, 2), dtype=torch.int16, device=self.device)
+        assert elig.dtype == torch.int16 and elig.is_cuda and elig.is_contiguous() and tuple(elig.shape) == (n_t, P)
+        assert ge.dtype == torch.int16 and ge.is_cuda and ge.is_contiguous() and tuple(ge.shape) == (n_t, P, 4, 2)
+        self._check(self.lib.ampli_exceedance_records(self.h, ctypes.byref(tumours), ctypes.byref(normals), P, _ptr(ref_code), normal_cutoff, calling_cutoff,
+                                                      first_t, first_n, int(bool(skip_same_index)), int(bool(accumulate)), _ptr(elig), _ptr(ge)))
+        return elig, ge
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

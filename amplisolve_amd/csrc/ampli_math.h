@@ -1099,4 +1099,43 @@ AMPLI_FN void ampli_spectrum_score(const int64_t *alt, const int64_t *dep, const
     }
 }
 
+// ---------------------------------------------------------------------------
+// Panel-of-normals exceedance (the definition is tests/exceedance_model.py): the candidate rule on top of the counts of
+// ampli_exceedance_records.  Integers only.  A cell (tumour row, position, base) with the tumour's alt reads x[st] and depths D[st]
+// per strand, the position's eligible normals and the cell's two counts ge[st] is a candidate iff it is evaluated (neither count is
+// AMPLI_EXCEEDANCE_NA) and
+//   x[0] >= min_alt_reads and x[1] >= min_alt_reads, 1000 (x[0] + x[1]) >= min_vaf_pm (D[0] + D[1]), elig >= min_normals,
+//   ge[0] <= max_normals and ge[1] <= max_normals
+// -- the PER-STRAND rule: at most max_normals normals reach on the forward strand and at most max_normals on the reverse.  ("No
+// normal reaches on both strands at once" is a different, far weaker rule and is not this one.)  A field is below 2^31 and a depth
+// below 2^33, min_vaf_pm at most 1000: no product leaves unsigned 64 bits.
+// ---------------------------------------------------------------------------
+#ifndef AMPLI_EXCEEDANCE_NA // also in include/amplisolve_hip.h, which this header does not need
+#define AMPLI_EXCEEDANCE_NA 0xFFFF
+#define AMPLI_EXCEEDANCE_MAX_NORMALS 65534
+#define AMPLI_EXCEEDANCE_STRIP 8
+#define AMPLI_EXCEEDANCE_ROWS 8
+#endif
+#ifndef AMPLI_EXCEEDANCE_PARAMS_DEFINED // also in include/amplisolve_host.h
+#define AMPLI_EXCEEDANCE_PARAMS_DEFINED
+typedef struct ampli_exceedance_params {
+    int64_t min_alt_reads, min_vaf_pm, min_normals, max_normals;
+} ampli_exceedance_params;
+#endif
+// every count >= 0 and min_vaf_pm at most 1000
+AMPLI_FN int ampli_exceedance_params_ok(const ampli_exceedance_params *q)
+{
+    return q->min_alt_reads >= 0 && q->min_vaf_pm >= 0 && q->min_vaf_pm <= 1000 && q->min_normals >= 0 && q->max_normals >= 0;
+}
+AMPLI_FN int ampli_exceedance_candidate(uint64_t x_fw, uint64_t x_bw, uint64_t d_fw, uint64_t d_bw, uint32_t elig, uint32_t ge_fw, uint32_t ge_bw,
+                                        const ampli_exceedance_params *q)
+{
+    const int evaluated = ge_fw != AMPLI_EXCEEDANCE_NA && ge_bw != AMPLI_EXCEEDANCE_NA;
+    const int reads = x_fw >= (uint64_t)q->min_alt_reads && x_bw >= (uint64_t)q->min_alt_reads;
+    const int vaf = 1000ull * (x_fw + x_bw) >= (uint64_t)q->min_vaf_pm * (d_fw + d_bw);
+    const int normals = (int64_t)elig >= q->min_normals;
+    const int top = (int64_t)ge_fw <= q->max_normals && (int64_t)ge_bw <= q->max_normals;
+    return evaluated & reads & vaf & normals & top;
+}
+
 #endif

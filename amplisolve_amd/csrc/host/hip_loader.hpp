@@ -75,6 +75,8 @@ struct HipApi {
     int (*amplicon_ratio)(ampli_ctx *, const int64_t *, int32_t, int32_t, const uint8_t *, const double *, const uint8_t *, int64_t *, double *, int32_t *,
                           double *, double *);
     int (*spectrum_records)(ampli_ctx *, const ampli_records *, int64_t, const uint8_t *, const uint8_t *, int32_t, int32_t, int32_t, int64_t *);
+    int (*exceedance_records)(ampli_ctx *, const ampli_records *, const ampli_records *, int64_t, const uint8_t *, int32_t, int32_t, int64_t, int64_t, int32_t,
+                              int32_t, uint16_t *, uint16_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

@@ -391,6 +391,15 @@ extern "C" int ampli_host_spectrum_score(const int64_t *alt, const int64_t *dep,
     return 0;
 }
 
+extern "C" int ampli_host_exceedance_candidate_batch(const uint64_t *x, const uint64_t *depth, const uint16_t *elig, const uint16_t *ge, int64_t count,
+                                                     const ampli_exceedance_params *prm, uint8_t *candidate)
+{
+    if (!x || !depth || !elig || !ge || !prm || !candidate || count < 0 || !ampli_exceedance_params_ok(prm)) return AMPLI_E_INVALID;
+    for (int64_t i = 0; i < count; ++i)
+        candidate[i] = (uint8_t)ampli_exceedance_candidate(x[2 * i], x[2 * i + 1], depth[2 * i], depth[2 * i + 1], elig[i], ge[2 * i], ge[2 * i + 1], prm);
+    return 0;
+}
+
 extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)
 {
     try {

@@ -1,4 +1,4 @@
-// amplisolve_amd/csrc/host/pipeline.hpp -- what the command lines (run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp, run_ct.cpp, run_ac.cpp, run_ss.cpp) share.
+// amplisolve_amd/csrc/host/pipeline.hpp -- what the command lines (run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp, run_ct.cpp, run_ac.cpp, run_ss.cpp, run_ex.cpp) share.
 // Internal to those files and pipeline.cpp; the commands themselves are declared in host.hpp.
 #pragma once
 #include <algorithm>
@@ -221,6 +221,16 @@ struct SsArgs {
                 min_sites = "200", min_normals = "5", excess_ratio = "3", z_cutoff = "10", asym_delta = "0.15", refbases_file;
 };
 int run_substitution_spectrum(const SsArgs &a);
+
+// AmpliSolveNormalExceedance (ex_main.cpp, run_ex.cpp): how many normals of the panel show an allele at a tumour's fraction
+// or above, and which cells top (nearly) all of them on both strands.  tumour_dir "-" = the normals against themselves, each without
+// its own file; coverage_cutoff, calling_cutoff, min_alt_reads and min_normals integers >= 0, min_vaf_pm an integer in [0, 1000],
+// max_normals an integer in [0, 65534]; refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
+struct ExArgs {
+    std::string panel_design, reference_genome, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", calling_cutoff = "100",
+                min_alt_reads = "3", min_vaf_pm = "0", min_normals = "10", max_normals = "0", refbases_file;
+};
+int run_normal_exceedance(const ExArgs &a);
 
 // ---- the emitted calls ----
 // Where a record of a chunk came from: the data line of its sample's file (-1: absent) and the panel position of record slot r in

@@ -1,0 +1,217 @@
+// amplisolve_amd/csrc/host/run_ex.cpp -- run_normal_exceedance, one of the project's own command lines
+// AmpliSolveNormalExceedance: for every cell (file, position, alternative base) of the tumours, how many normals of the
+// panel show the allele at the file's fraction or above on each strand, and which cells are candidates: enough reads on both strands,
+// enough eligible normals, and at most max_normals of them reaching on either strand.  Every chunk of the normals stays resident on
+// the device; the tumours stream chunk by chunk, each against every resident chunk into the same two count arrays (the first
+// overwrites, the others accumulate); the candidate rule (ampli_exceedance_candidate, ampli_math.h) and the four files here.
+// tumour_dir=- runs the normals against themselves, each without its own file: the leave-self-out false-candidate rate of the panel.
+#include "pipeline.hpp"
+
+#include "../ampli_math.h"
+
+namespace ampli {
+
+namespace {
+
+// a whole decimal integer in [lo, hi]
+int parse_int(const std::string &s, const char *what, const long lo, const long hi = 0x7FFFFFFFl)
+{
+    char *end = nullptr;
+    const long v = std::strtol(s.c_str(), &end, 10);
+    if (s.empty() || *end || v < lo || v > hi) {
+        const std::string range = hi == 0x7FFFFFFFl ? ">= " + std::to_string(lo) : "in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]";
+        throw Error{AMPLI_E_INVALID, std::string(what) + " must be an integer " + range + ", got '" + s + "'"};
+    }
+    return (int)v;
+}
+
+struct Resident { // a chunk of the normals that stays on the device; with tumour_dir=- also the host's copy of its primary records
+    ampli_records r;
+    int first, n, layout;
+    std::vector<char> prim;
+};
+
+std::string per_1000(const long long c, const long long e)
+{
+    char b[64];
+    snprintf(b, sizeof b, "%.4f", e ? 1000.0 * (double)c / (double)e : 0.0);
+    return b;
+}
+
+} // namespace
+
+int run_normal_exceedance(const ExArgs &a)
+{
+    try {
+        const int cov = parse_int(a.coverage_cutoff, "coverage_cutoff", 0);
+        const int call_cov = parse_int(a.calling_cutoff, "calling_cutoff", 0);
+        ampli_exceedance_params prm;
+        prm.min_alt_reads = parse_int(a.min_alt_reads, "min_alt_reads", 0);
+        prm.min_vaf_pm = parse_int(a.min_vaf_pm, "min_vaf_pm", 0, 1000);
+        prm.min_normals = parse_int(a.min_normals, "min_normals", 0);
+        prm.max_normals = parse_int(a.max_normals, "max_normals", 0, AMPLI_EXCEEDANCE_MAX_NORMALS);
+        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
+            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveNormalExceedance runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        const bool with_tumours = a.tumour_dir != "-";
+        std::cout << "AmpliSolveNormalExceedance: panel " << a.panel_design << ", normals " << a.germline_dir << ", tumours "
+                  << (with_tumours ? a.tumour_dir : std::string("the normals themselves")) << ", coverage_cutoff " << cov << ", calling_cutoff " << call_cov
+                  << ", min_alt_reads " << prm.min_alt_reads << ", min_vaf_pm " << prm.min_vaf_pm << ", min_normals " << prm.min_normals << ", max_normals "
+                  << prm.max_normals << ", output " << a.output_dir << std::endl;
+        DevAsync dev_async;
+        dev_async.start();
+        Panel panel;
+        panel_from_bed(a.panel_design, panel);
+        if (!a.refbases_file.empty()) panel_load_refbases_file(panel, a.refbases_file);
+        else panel_load_fasta(panel, a.reference_genome);
+        const auto normals = list_count_files(a.germline_dir, std::string());
+        std::vector<std::pair<std::string, std::string>> tumours;
+        if (with_tumours) tumours = list_count_files(a.tumour_dir, std::string());
+        const int n_normals = (int)normals.size(), n_tumours = (int)tumours.size();
+        const int64_t P = panel.P();
+        if (P <= 0) throw Error{AMPLI_E_INVALID, "the panel has no positions"};
+        if (n_normals <= 0) throw Error{AMPLI_E_INVALID, "no count files in " + a.germline_dir};
+        if (n_normals > AMPLI_EXCEEDANCE_MAX_NORMALS)
+            throw Error{AMPLI_E_RANGE, "a panel of at most " + std::to_string(AMPLI_EXCEEDANCE_MAX_NORMALS) + " normals is supported, " + a.germline_dir + " has " +
+                                           std::to_string(n_normals)};
+        const auto &files = with_tumours ? tumours : normals; // the files under test
+        const int F = (int)files.size();
+        Dev &dev = dev_async.get();
+        size_t free_b = 0, total_b = 0;
+        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
+        // every chunk of the normals stays resident: refuse before the device runs out (beside them one chunk of tumours and its counts)
+        const size_t reserve = (size_t)1 << 30;
+        std::vector<DevSlot> slots;
+        slots.reserve(4096);
+        std::vector<Resident> res;
+        size_t resident_bytes = 0;
+        {
+            const std::unique_ptr<ChunkStream> cs = open_stream(panel, normals, false);
+            for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
+                const size_t b = (size_t)c->n * (size_t)(P + c->E) * record_bytes(c->layout) + (size_t)c->n * (size_t)(P + c->E) * 5;
+                if (resident_bytes + b + reserve > free_b)
+                    throw Error{AMPLI_E_NOMEM, "the normals do not fit the device: " + std::to_string(resident_bytes + b + reserve) +
+                                                   " bytes of records and buffers needed so far, " + std::to_string(free_b) + " bytes free"};
+                resident_bytes += b;
+                slots.emplace_back();
+                Resident x;
+                x.r = upload_chunk(dev, slots.back(), *c, false);
+                x.first = c->first; x.n = c->n; x.layout = c->layout;
+                if (!with_tumours) x.prim.assign((const char *)c->prim, (const char *)c->prim + (size_t)c->n * (size_t)P * record_bytes(c->layout));
+                dev.sync(); // the chunk's host buffers go back to the parsers
+                res.push_back(std::move(x));
+                cs->release(c);
+            }
+        }
+        const uint8_t *d_ref = dev.upload(panel.ref_code.data(), panel.ref_code.size());
+
+        std::string candidates = "sample\tchrom\tposition\tsubstitution\tXfw\tXrs\tFW\tBW\tAF\tElig\tGE_fw\tGE_rs\n";
+        std::vector<long long> evaluated_of((size_t)F, 0), candidates_of((size_t)F, 0), cand_pos((size_t)P * 4, 0);
+        std::vector<uint16_t> elig_all((size_t)F * (size_t)P);
+        DevBuf b_elig, b_ge;
+        std::vector<uint16_t> elig, ge;
+        char b[512];
+        // one chunk of the files under test: its counts against every resident chunk, then the candidate rule on the host
+        auto test_chunk = [&](const ampli_records &tr, const int first, const int n, const int layout, const char *prim) {
+            const size_t cells = (size_t)n * (size_t)P;
+            uint16_t *d_elig = (uint16_t *)b_elig.ensure(dev, cells * sizeof(uint16_t));
+            uint16_t *d_ge = (uint16_t *)b_ge.ensure(dev, cells * 8 * sizeof(uint16_t));
+            for (size_t k = 0; k < res.size(); ++k)
+                dev.check(dev.api->exceedance_records(dev.ctx, &tr, &res[k].r, P, d_ref, cov, call_cov, (with_tumours ? n_normals : 0) + first, res[k].first,
+                                                      with_tumours ? 0 : 1, k ? 1 : 0, d_elig, d_ge),
+                          "ampli_exceedance_records");
+            elig.resize(cells);
+            ge.resize(cells * 8);
+            dev.download(elig.data(), (const uint16_t *)d_elig, cells);
+            dev.download(ge.data(), (const uint16_t *)d_ge, cells * 8);
+            dev.sync();
+            const size_t rb = record_bytes(layout);
+            for (int s = 0; s < n; ++s) {
+                const size_t f = (size_t)(first + s);
+                std::copy(elig.begin() + (size_t)s * P, elig.begin() + (size_t)(s + 1) * P, elig_all.begin() + f * (size_t)P);
+                for (int64_t p = 0; p < P; ++p) {
+                    const size_t cell = (size_t)s * (size_t)P + (size_t)p;
+                    const uint16_t *g = ge.data() + cell * 8;
+                    int32_t rec[8];
+                    bool have = false;
+                    for (int y = 0; y < 4; ++y) {
+                        if (g[2 * y] == AMPLI_EXCEEDANCE_NA) continue;
+                        ++evaluated_of[f];
+                        if (!have) { record_unpack(layout, prim + cell * rb, rec); have = true; }
+                        const uint64_t d_fw = (uint64_t)rec[0] + (uint64_t)rec[1] + (uint64_t)rec[2] + (uint64_t)rec[3];
+                        const uint64_t d_bw = (uint64_t)rec[4] + (uint64_t)rec[5] + (uint64_t)rec[6] + (uint64_t)rec[7];
+                        const uint64_t x_fw = (uint64_t)rec[y], x_bw = (uint64_t)rec[4 + y];
+                        if (!ampli_exceedance_candidate(x_fw, x_bw, d_fw, d_bw, elig[cell], g[2 * y], g[2 * y + 1], &prm)) continue;
+                        ++candidates_of[f];
+                        ++cand_pos[(size_t)p * 4 + y];
+                        const uint64_t d = d_fw + d_bw;
+                        char af[64] = "NA";
+                        if (d) snprintf(af, sizeof af, "%.6f", (double)(x_fw + x_bw) / (double)d);
+                        snprintf(b, sizeof b, "\t%d\t%c->%c\t%llu\t%llu\t%llu\t%llu\t%s\t%u\t%u\t%u\n", panel.pos_coord[(size_t)p], "ACGT"[panel.ref_code[(size_t)p]],
+                                 "ACGT"[y], (unsigned long long)x_fw, (unsigned long long)x_bw, (unsigned long long)d_fw, (unsigned long long)d_bw, af,
+                                 (unsigned)elig[cell], (unsigned)g[2 * y], (unsigned)g[2 * y + 1]);
+                        candidates += files[f].second + "\t" + panel.chroms[(size_t)panel.pos_chrom[(size_t)p]] + b;
+                    }
+                }
+            }
+        };
+        if (with_tumours) {
+            if (n_tumours > 0) {
+                DevSlot slot;
+                const std::unique_ptr<ChunkStream> cs = open_stream(panel, tumours, false);
+                for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
+                    const ampli_records r = upload_chunk(dev, slot, *c, false);
+                    test_chunk(r, c->first, c->n, c->layout, (const char *)c->prim);
+                    cs->release(c);
+                }
+            }
+        } else {
+            for (const Resident &x : res) test_chunk(x.r, x.first, x.n, x.layout, x.prim.data());
+        }
+
+        // Exceedance_Samples.txt, Exceedance_Positions.txt, Exceedance_Summary.txt
+        std::string samples = "sample\tEvaluated\tCandidates\tCandidates_per_1000\n";
+        long long evaluated = 0, n_candidates = 0;
+        for (int f = 0; f < F; ++f) {
+            samples += files[(size_t)f].second + "\t" + std::to_string(evaluated_of[(size_t)f]) + "\t" + std::to_string(candidates_of[(size_t)f]) + "\t" +
+                       per_1000(candidates_of[(size_t)f], evaluated_of[(size_t)f]) + "\n";
+            evaluated += evaluated_of[(size_t)f];
+            n_candidates += candidates_of[(size_t)f];
+        }
+        std::string positions = "chrom\tposition\treference\tMedianElig\tCand_A\tCand_C\tCand_G\tCand_T\n";
+        std::vector<uint16_t> col((size_t)F);
+        long long with_reference = 0;
+        for (int64_t p = 0; p < P; ++p) {
+            std::string median = "NA"; // the median of the files' eligible normals: the mean of the two middle ones when F is even
+            if (F > 0) {
+                for (int f = 0; f < F; ++f) col[(size_t)f] = elig_all[(size_t)f * (size_t)P + (size_t)p];
+                std::sort(col.begin(), col.end());
+                snprintf(b, sizeof b, "%.1f", ((double)col[(size_t)(F - 1) / 2] + (double)col[(size_t)F / 2]) / 2.0);
+                median = b;
+            }
+            with_reference += panel.ref_code[(size_t)p] <= 3 ? 1 : 0;
+            positions += panel.chroms[(size_t)panel.pos_chrom[(size_t)p]] + "\t" + std::to_string(panel.pos_coord[(size_t)p]) + "\t" + panel.ref_base[(size_t)p] + "\t" +
+                         median;
+            for (int y = 0; y < 4; ++y) positions += "\t" + std::to_string(cand_pos[(size_t)p * 4 + y]);
+            positions += "\n";
+        }
+        snprintf(b, sizeof b,
+                 "normals=%d\ntumours=%d\npositions=%lld\npositions_with_reference=%lld\ncoverage_cutoff=%d\ncalling_cutoff=%d\nmin_alt_reads=%lld\n"
+                 "min_vaf_pm=%lld\nmin_normals=%lld\nmax_normals=%lld\nskip_same_index=%d\nevaluated=%lld\ncandidates=%lld\ncandidates_per_1000=%s\n",
+                 n_normals, n_tumours, (long long)P, with_reference, cov, call_cov, (long long)prm.min_alt_reads, (long long)prm.min_vaf_pm,
+                 (long long)prm.min_normals, (long long)prm.max_normals, with_tumours ? 0 : 1, evaluated, n_candidates, per_1000(n_candidates, evaluated).c_str());
+        mkdir_p(a.output_dir);
+        std::ofstream(a.output_dir + "/Exceedance_Candidates.txt") << candidates;
+        std::ofstream(a.output_dir + "/Exceedance_Samples.txt") << samples;
+        std::ofstream(a.output_dir + "/Exceedance_Positions.txt") << positions;
+        std::ofstream(a.output_dir + "/Exceedance_Summary.txt") << b;
+        std::cout << F << " files against " << n_normals << " normals, " << P << " positions: " << n_candidates << " candidates in " << evaluated
+                  << " evaluated cells" << std::endl;
+        return 0;
+    } catch (const Error &e) {
+        return fail_line("AmpliSolveNormalExceedance", e.msg);
+    } catch (const std::exception &e) {
+        return fail_line("AmpliSolveNormalExceedance", e.what());
+    }
+}
+
+} // namespace ampli

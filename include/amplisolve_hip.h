@@ -124,6 +124,10 @@ extern "C" {
  *        itself where segments are added into it); a class no position has gets nine zeros.  Nothing else is written -- the other
  *        chunks' rows of a larger matrix included.  d_ref_code and d_class are read at [0, P), a record only at a position below P
  *        whose reference code and class are valid, of a row below n_samples.
+ *   (C17) panel-of-normals exceedance (tests/test_gpu_exceedance_contracts.py): ampli_exceedance_records with accumulate == 0 FULLY
+ *        OVERWRITES d_elig, all [n_t][P] counts, and d_ge, all [n_t][P][4][2] cells, AMPLI_EXCEEDANCE_NA included, whatever they held;
+ *        with accumulate != 0 it ADDS TO d_elig and to the evaluated cells of d_ge and writes NA to the others.  Nothing else is
+ *        written.  d_ref_code is read at [0, P), a record only at a position below P of a row below n_t / n_n.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -791,6 +795,50 @@ int ampli_amplicon_ratio(ampli_ctx *ctx, const int64_t *d_sums, int32_t S, int32
 int ampli_spectrum_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint8_t *d_ref_code, const uint8_t *d_class, int32_t C,
                            int32_t coverage_cutoff, int32_t max_alt_pm, int64_t *d_sums);
 int ampli_last_spectrum_segments(const ampli_ctx *ctx);
+
+/*
+ * Panel-of-normals exceedance (the definition, in plain numpy, is tests/exceedance_model.py): how many of the normals show
+ * an allele at a position at the tumour's fraction or above.
+ *
+ * Inputs.  recs_t, a chunk of n_t "tumour" rows, and recs_n, a chunk of n_n "normal" rows: both ampli_records in any of the three
+ * layouts, and the two may differ.  P, and d_ref_code uint8 [P].  normal_cutoff >= 0 and calling_cutoff >= 0.  first_t and first_n
+ * (>= 0), the global indices of each chunk's first row.  skip_same_index (0 / not 0) and accumulate (0 / not 0).  Only the PRIMARY
+ * record of (row, position) enters, slot r < P; extras and an RD plane have no effect.
+ * Per record.  For strand st (0 forward, 1 reverse) x[st][b] is the count of base b and D[st] the sum of the strand's four counts,
+ * all unsigned 64-bit; an absent record has no counts.
+ * Eligible normal.  Normal s is eligible at p iff its record is present, D_s[0] >= normal_cutoff and D_s[1] >= normal_cutoff (the
+ * two-strand depth clause of EE:1592), and not (skip_same_index and first_n + s == first_t + t).  There is no allele-fraction
+ * clause: a germline-heterozygous normal is supposed to count.
+ * Reaching.  Normal s reaches tumour t at (p, b, st) iff it is eligible and x_s[st][b] D_t[st] >= x_t[st][b] D_s[st]: x_s / D_s >=
+ * x_t / D_t by cross-multiplication.  Both products are formed in unsigned 64 bits: a field is below 2^31 and a depth below 2^33,
+ * so no product reaches 2^64.  x_t == 0 makes every eligible normal reach (an absent tumour record too, whose cells are NA anyway).
+ * Outputs.
+ *   d_elig uint16 [n_t][P]: the eligible normals for (t, p), whatever t's own record is.
+ *   d_ge   uint16 [n_t][P][4][2], 16-byte aligned: per base b and strand, the number of normals that reach.  A cell is EVALUATED iff
+ *          t's record is present, D_t[0] >= calling_cutoff and D_t[1] >= calling_cutoff, d_ref_code[p] is 0..3 and b is not
+ *          d_ref_code[p]; every other cell holds AMPLI_EXCEEDANCE_NA (0xFFFF) on both strands.
+ * accumulate == 0 overwrites every cell of both outputs.  accumulate != 0 adds this chunk's normals onto d_elig and onto the cells
+ * this call's arguments make evaluated (modulo 2^16: what they held is taken as a count) and writes NA to the others: called with
+ * the same tumours, reference codes and calling_cutoff, NA cells stay NA, and any chunking of the normals gives the bytes of the
+ * single pass (C17).
+ * Refusals, every output untouched.  AMPLI_E_RANGE: first_n + n_n > AMPLI_EXCEEDANCE_MAX_NORMALS (65534), so that no count can
+ * reach the sentinel; P >= 2^31.  AMPLI_E_INVALID: a null pointer, a misaligned d_elig or d_ge, P <= 0, a negative cut-off or first
+ * index, broken records (n_t or n_n < 1, an unknown layout, a row stride below P + E, misaligned records).
+ * The form: a workgroup of four waves owns one 64-position tile and AMPLI_EXCEEDANCE_ROWS tumour rows, two per wave, a lane a
+ * position; the normals pass through LDS in strips of AMPLI_EXCEEDANCE_STRIP decoded rows, the next strip's loads in flight while
+ * this one is compared.  The normals are never split across workgroups: every (t, p) cell has exactly one owning lane per launch,
+ * the accumulate form is a plain read-modify-write, there are no atomics and the bytes are the same in any launch order.
+ * Integers only.  Asynchronous on the context's stream.
+ */
+#ifndef AMPLI_EXCEEDANCE_NA /* also in csrc/ampli_math.h */
+#define AMPLI_EXCEEDANCE_NA 0xFFFF
+#define AMPLI_EXCEEDANCE_MAX_NORMALS 65534
+#define AMPLI_EXCEEDANCE_STRIP 8 /* normal rows decoded into LDS at a time */
+#define AMPLI_EXCEEDANCE_ROWS 8  /* tumour rows per workgroup of exceedance_kernel */
+#endif
+int ampli_exceedance_records(ampli_ctx *ctx, const ampli_records *recs_t, const ampli_records *recs_n, int64_t P, const uint8_t *d_ref_code,
+                             int32_t normal_cutoff, int32_t calling_cutoff, int64_t first_t, int64_t first_n, int32_t skip_same_index,
+                             int32_t accumulate, uint16_t *d_elig, uint16_t *d_ge);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

@@ -241,6 +241,22 @@ int ampli_host_spectrum_score(const int64_t *alt, const int64_t *dep, const int6
                               double *ref, int32_t *n_eff, uint8_t *status, double *rate2, double *ratio, double *z, double *asym, double *za,
                               uint8_t *flag);
 
+/* Panel-of-normals exceedance (the definition is tests/exceedance_model.py): csrc/ampli_math.h's ampli_exceedance_candidate
+ * on `count` cells, integers only.  x and depth uint64 [count][2]: the tumour's reads of the cell's base and its depth per strand
+ * (forward, reverse); elig uint16 [count]: the eligible normals of the cell's (row, position); ge uint16 [count][2]: the cell's two
+ * counts of ampli_exceedance_records.  A cell is a candidate (1 in candidate, else 0) iff neither count is AMPLI_EXCEEDANCE_NA (0xFFFF),
+ * x[0] >= min_alt_reads and x[1] >= min_alt_reads, 1000 (x[0] + x[1]) >= min_vaf_pm (depth[0] + depth[1]), elig >= min_normals, and
+ * ge[0] <= max_normals and ge[1] <= max_normals: the per-strand rule.  Returns 0, or AMPLI_E_INVALID (-1) with nothing written for a
+ * null pointer, count < 0, a negative parameter or min_vaf_pm above 1000. */
+#ifndef AMPLI_EXCEEDANCE_PARAMS_DEFINED /* also in csrc/ampli_math.h */
+#define AMPLI_EXCEEDANCE_PARAMS_DEFINED
+typedef struct ampli_exceedance_params {
+    int64_t min_alt_reads, min_vaf_pm, min_normals, max_normals;
+} ampli_exceedance_params;
+#endif
+int ampli_host_exceedance_candidate_batch(const uint64_t *x, const uint64_t *depth, const uint16_t *elig, const uint16_t *ge, int64_t count,
+                                          const ampli_exceedance_params *prm, uint8_t *candidate);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
