@@ -4,20 +4,12 @@
 //                              min_amplicons=<i> z_cutoff=<f> gain_ratio=<f> loss_ratio=<f> exclude_chrom=<comma list|->
 // Exactly 11 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
-#include "pipeline.hpp"
+#include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -41,8 +33,5 @@ int main(int argc, char **argv)
     a.gain_ratio = token(argv[9], "gain_ratio");
     a.loss_ratio = token(argv[10], "loss_ratio");
     a.exclude_chrom = token(argv[11], "exclude_chrom");
-    const int rc = ampli::run_amplicon_coverage(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_amplicon_coverage(a));
 }

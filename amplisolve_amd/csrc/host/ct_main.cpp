@@ -3,20 +3,12 @@
 //   AmpliSolveContamination panel_design=<bed> germline_dir=<dir> tumour_dir=<dir|-> output_dir=<dir> min_depth=<i> min_sites=<i> min_fraction=<f>
 // Exactly 7 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
-#include "pipeline.hpp"
+#include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -35,8 +27,5 @@ int main(int argc, char **argv)
     a.min_depth = token(argv[5], "min_depth");
     a.min_sites = token(argv[6], "min_sites");
     a.min_fraction = token(argv[7], "min_fraction");
-    const int rc = ampli::run_contamination(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_contamination(a));
 }

@@ -2,20 +2,12 @@
 //   AmpliSolveDetectionLimit errorFile=<table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<int> levels=<f>[,<f>...]
 // Exactly 5 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
 #include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -31,8 +23,5 @@ int main(int argc, char **argv)
     a.output_dir = token(argv[3], "output_dir");
     a.coverage_cutoff = token(argv[4], "coverage_cutoff");
     a.levels = token(argv[5], "levels");
-    const int rc = ampli::run_detection_limits(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_detection_limits(a));
 }

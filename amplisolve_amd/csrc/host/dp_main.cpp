@@ -3,20 +3,12 @@
 //   AmpliSolveDetectionPower errorFile=<table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<int> levels=<f>[,<f>...] confidence=<f>
 // Exactly 6 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
 #include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -33,8 +25,5 @@ int main(int argc, char **argv)
     a.coverage_cutoff = token(argv[4], "coverage_cutoff");
     a.levels = token(argv[5], "levels");
     a.confidence = token(argv[6], "confidence");
-    const int rc = ampli::run_detection_power(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_detection_power(a));
 }

@@ -4,20 +4,12 @@
 // Exactly 7 key=value tokens in this order (EE:266, EE:300-326).  Like the reference, the process exits 0 on
 // every path (EE:272, EE:3057-3074); set AMPLISOLVE_STRICT_EXIT=1 to get a non-zero status on failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
 #include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s"; // sscanf(argv[i], "key=%s", ...) (EE:300-326)
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {

@@ -4,20 +4,12 @@
 //                              coverage_cutoff=<i> calling_cutoff=<i> min_alt_reads=<i> min_vaf_pm=<i> min_normals=<i> max_normals=<i>
 // Exactly 11 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
-#include "pipeline.hpp"
+#include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -42,8 +34,5 @@ int main(int argc, char **argv)
     a.min_normals = token(argv[10], "min_normals");
     a.max_normals = token(argv[11], "max_normals");
     if (const char *e = getenv("AMPLISOLVE_REFBASES_FILE")) a.refbases_file = e; // pre-computed chrom/pos/base table instead of the FASTA
-    const int rc = ampli::run_normal_exceedance(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_normal_exceedance(a));
 }

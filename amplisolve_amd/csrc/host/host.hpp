@@ -216,7 +216,8 @@ void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // without the static destructors and atexit handlers of the HIP runtime (queue / signal / pool teardown that only serves a
 // process that lives on; the driver reclaims everything at exit either way).  AMPLISOLVE_EXIT=orderly returns instead.
 void finish_process(int status);
-// ---- run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp ----
+// ---- run_ee.cpp, run_vc.cpp, and the project's own commands: run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp, run_ct.cpp,
+// run_ac.cpp, run_ss.cpp, run_ex.cpp (what those nine share: command.hpp) ----
 int run_error_estimation(const EeArgs &a);
 int run_variant_calling(const VcArgs &a);
 // AmpliSolveLeaveOneOut (loo_main.cpp): C_value is one value or a comma-separated list; exit status 0 / 1
@@ -241,6 +242,49 @@ struct PdArgs {
     std::string refbases_file;
 };
 int run_panel_dispersion(const PdArgs &a);
+// AmpliSolveSampleConcordance (sc_main.cpp, run_sc.cpp): are the count files who they say they are.  tumour_dir "-" = the
+// normals only; min_depth, min_sites integers >= 1, same_fraction in (0, 1]; exit status 0 / 1
+struct ScArgs {
+    std::string panel_design, germline_dir, tumour_dir = "-", min_depth = "100", min_sites = "20", same_fraction = "0.8", output_dir;
+};
+int run_sample_concordance(const ScArgs &a);
+
+// AmpliSolveContamination (ct_main.cpp, run_ct.cpp): which count file leaks into which, and how much.  tumour_dir "-" = the
+// normals only; min_depth, min_sites integers >= 1, min_fraction in (0, 1]; exit status 0 / 1
+struct CtArgs {
+    std::string panel_design, germline_dir, tumour_dir = "-", output_dir, min_depth = "100", min_sites = "20", min_fraction = "0.005";
+};
+int run_contamination(const CtArgs &a);
+
+// AmpliSolveAmpliconCoverage (ac_main.cpp, run_ac.cpp): which amplicons failed, and where the copy number is off against
+// the panel of normals.  tumour_dir "-" = the normals only; exclude_chrom: a comma list of chromosomes left out of library size and
+// centring, "-" = none; coverage_cutoff an integer >= 0, min_normals and min_amplicons integers >= 1, z_cutoff >= 0, gain_ratio > 1,
+// loss_ratio in (0, 1); exit status 0 / 1
+struct AcArgs {
+    std::string panel_design, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", min_normals = "5", min_amplicons = "3",
+                z_cutoff = "3", gain_ratio = "1.3", loss_ratio = "0.7", exclude_chrom = "chrX,chrY";
+};
+int run_amplicon_coverage(const AcArgs &a);
+
+// AmpliSolveSubstitutionSpectrum (ss_main.cpp, run_ss.cpp): which kind of error a file makes more of than the panel of
+// normals does, per strand-resolved substitution type and per read strand.  tumour_dir "-" = the normals only; coverage_cutoff an
+// integer >= 0, max_alt_pm an integer in [0, 1000], min_sites and min_normals integers >= 1, excess_ratio > 1, z_cutoff >= 0,
+// asym_delta in [0, 1]; refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
+struct SsArgs {
+    std::string panel_design, reference_genome, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", max_alt_pm = "30",
+                min_sites = "200", min_normals = "5", excess_ratio = "3", z_cutoff = "10", asym_delta = "0.15", refbases_file;
+};
+int run_substitution_spectrum(const SsArgs &a);
+
+// AmpliSolveNormalExceedance (ex_main.cpp, run_ex.cpp): how many normals of the panel show an allele at a tumour's fraction
+// or above, and which cells top (nearly) all of them on both strands.  tumour_dir "-" = the normals against themselves, each without
+// its own file; coverage_cutoff, calling_cutoff, min_alt_reads and min_normals integers >= 0, min_vaf_pm an integer in [0, 1000],
+// max_normals an integer in [0, 65534]; refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
+struct ExArgs {
+    std::string panel_design, reference_genome, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", calling_cutoff = "100",
+                min_alt_reads = "3", min_vaf_pm = "0", min_normals = "10", max_normals = "0", refbases_file;
+};
+int run_normal_exceedance(const ExArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

@@ -3,20 +3,12 @@
 //                         calling_cutoff=<i> output_dir=<dir>
 // Exactly 7 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
 #include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -35,8 +27,5 @@ int main(int argc, char **argv)
     a.calling_cutoff = token(argv[6], "calling_cutoff");
     a.output_dir = token(argv[7], "output_dir");
     if (const char *e = getenv("AMPLISOLVE_REFBASES_FILE")) a.refbases_file = e;
-    const int rc = ampli::run_leave_one_out(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_leave_one_out(a));
 }

@@ -3,20 +3,12 @@
 //   AmpliSolvePanelDispersion panel_design=<bed> reference_genome=<fa> germline_dir=<dir> coverage_cutoff=<i> z_cutoff=<f> output_dir=<dir>
 // Exactly 6 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
 #include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -34,8 +26,5 @@ int main(int argc, char **argv)
     a.z_cutoff = token(argv[5], "z_cutoff");
     a.output_dir = token(argv[6], "output_dir");
     if (const char *e = getenv("AMPLISOLVE_REFBASES_FILE")) a.refbases_file = e;
-    const int rc = ampli::run_panel_dispersion(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_panel_dispersion(a));
 }

@@ -1,5 +1,8 @@
-// amplisolve_amd/csrc/host/pipeline.hpp -- what the command lines (run_ee.cpp, run_vc.cpp, run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp, run_ct.cpp, run_ac.cpp, run_ss.cpp, run_ex.cpp) share.
-// Internal to those files and pipeline.cpp; the commands themselves are declared in host.hpp.
+// amplisolve_amd/csrc/host/pipeline.hpp -- the device plumbing every command line shares: the context, the chunk stream, the call list.
+// Internal to run_ee.cpp, run_vc.cpp, pipeline.cpp and command.hpp / command.cpp, through which the project's own nine commands
+// (run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp, run_ct.cpp, run_ac.cpp, run_ss.cpp, run_ex.cpp) take it together with
+// what only they share.  All eleven commands and their arguments are declared in host.hpp; the *_main.cpp files need no more than
+// that and main_args.hpp.
 #pragma once
 #include <algorithm>
 #include <cmath>
@@ -187,50 +190,6 @@ void parallel_rows(size_t n, size_t grain, const std::function<void(size_t, size
 // what a failed command prints, and its exit status: the reference's banner (EE / VC) or one line (LOO / DL)
 int fail_banner(const Error &e);
 inline int fail_line(const char *program, const std::string &why) { std::cout << program << " failed: " << why << std::endl; return 1; }
-
-// AmpliSolveSampleConcordance (sc_main.cpp, run_sc.cpp): are the count files who they say they are.  tumour_dir "-" = the
-// normals only; min_depth, min_sites integers >= 1, same_fraction in (0, 1]; exit status 0 / 1
-struct ScArgs {
-    std::string panel_design, germline_dir, tumour_dir = "-", min_depth = "100", min_sites = "20", same_fraction = "0.8", output_dir;
-};
-int run_sample_concordance(const ScArgs &a);
-
-// AmpliSolveContamination (ct_main.cpp, run_ct.cpp): which count file leaks into which, and how much.  tumour_dir "-" = the
-// normals only; min_depth, min_sites integers >= 1, min_fraction in (0, 1]; exit status 0 / 1
-struct CtArgs {
-    std::string panel_design, germline_dir, tumour_dir = "-", output_dir, min_depth = "100", min_sites = "20", min_fraction = "0.005";
-};
-int run_contamination(const CtArgs &a);
-
-// AmpliSolveAmpliconCoverage (ac_main.cpp, run_ac.cpp): which amplicons failed, and where the copy number is off against
-// the panel of normals.  tumour_dir "-" = the normals only; exclude_chrom: a comma list of chromosomes left out of library size and
-// centring, "-" = none; coverage_cutoff an integer >= 0, min_normals and min_amplicons integers >= 1, z_cutoff >= 0, gain_ratio > 1,
-// loss_ratio in (0, 1); exit status 0 / 1
-struct AcArgs {
-    std::string panel_design, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", min_normals = "5", min_amplicons = "3",
-                z_cutoff = "3", gain_ratio = "1.3", loss_ratio = "0.7", exclude_chrom = "chrX,chrY";
-};
-int run_amplicon_coverage(const AcArgs &a);
-
-// AmpliSolveSubstitutionSpectrum (ss_main.cpp, run_ss.cpp): which kind of error a file makes more of than the panel of
-// normals does, per strand-resolved substitution type and per read strand.  tumour_dir "-" = the normals only; coverage_cutoff an
-// integer >= 0, max_alt_pm an integer in [0, 1000], min_sites and min_normals integers >= 1, excess_ratio > 1, z_cutoff >= 0,
-// asym_delta in [0, 1]; refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
-struct SsArgs {
-    std::string panel_design, reference_genome, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", max_alt_pm = "30",
-                min_sites = "200", min_normals = "5", excess_ratio = "3", z_cutoff = "10", asym_delta = "0.15", refbases_file;
-};
-int run_substitution_spectrum(const SsArgs &a);
-
-// AmpliSolveNormalExceedance (ex_main.cpp, run_ex.cpp): how many normals of the panel show an allele at a tumour's fraction
-// or above, and which cells top (nearly) all of them on both strands.  tumour_dir "-" = the normals against themselves, each without
-// its own file; coverage_cutoff, calling_cutoff, min_alt_reads and min_normals integers >= 0, min_vaf_pm an integer in [0, 1000],
-// max_normals an integer in [0, 65534]; refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
-struct ExArgs {
-    std::string panel_design, reference_genome, germline_dir, tumour_dir = "-", output_dir, coverage_cutoff = "100", calling_cutoff = "100",
-                min_alt_reads = "3", min_vaf_pm = "0", min_normals = "10", max_normals = "0", refbases_file;
-};
-int run_normal_exceedance(const ExArgs &a);
 
 // ---- the emitted calls ----
 // Where a record of a chunk came from: the data line of its sample's file (-1: absent) and the panel position of record slot r in

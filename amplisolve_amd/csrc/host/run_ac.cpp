@@ -3,9 +3,8 @@
 // file's copy number is off.  One pass over the normals and then over the tumours: every chunk's primary records are summed along the
 // amplicons' position lists into its rows of the one resident S x A x 4 matrix; then the reference from the normals' rows and the
 // ratios of all rows, both on the device; the gene level and the four files here.  Records never stay on the device.
-#include "pipeline.hpp"
+#include "command.hpp"
 
-#include <cmath>
 #include <map>
 
 #include "../ampli_math.h"
@@ -14,39 +13,13 @@ namespace ampli {
 
 namespace {
 
-// a whole decimal integer >= lo
-int parse_int(const std::string &s, const char *what, const long lo)
-{
-    char *end = nullptr;
-    const long v = std::strtol(s.c_str(), &end, 10);
-    if (s.empty() || *end || v < lo || v > 0x7FFFFFFFl)
-        throw Error{AMPLI_E_INVALID, std::string(what) + " must be an integer >= " + std::to_string(lo) + ", got '" + s + "'"};
-    return (int)v;
-}
-
-double parse_number(const std::string &s, const char *what, const char *range, bool (*ok)(double))
-{
-    char *end = nullptr;
-    const double v = std::strtod(s.c_str(), &end);
-    if (s.empty() || *end || !std::isfinite(v) || !ok(v)) throw Error{AMPLI_E_INVALID, std::string(what) + " must be a number " + range + ", got '" + s + "'"};
-    return v;
-}
-
-// the one printf format of each kind of number; NA for a NaN
-std::string num(const char *fmt, const double x)
-{
-    if (std::isnan(x)) return "NA";
-    char b[64];
-    snprintf(b, sizeof b, fmt, x);
-    return b;
-}
 const char *const kShare = "%.6e", *const kRatio = "%.5f", *const kZ = "%.3f", *const kFraction = "%.4f";
 
 } // namespace
 
 int run_amplicon_coverage(const AcArgs &a)
 {
-    try {
+    return run_command("AmpliSolveAmpliconCoverage", [&]() -> int {
         const int cov = parse_int(a.coverage_cutoff, "coverage_cutoff", 0);
         const int min_normals = parse_int(a.min_normals, "min_normals", 1);
         const int min_amplicons = parse_int(a.min_amplicons, "min_amplicons", 1);
@@ -63,8 +36,7 @@ int run_amplicon_coverage(const AcArgs &a)
                 at = comma + 1;
             }
         }
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveAmpliconCoverage runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        require_single_gpu("AmpliSolveAmpliconCoverage");
         const bool with_tumours = a.tumour_dir != "-";
         std::cout << "AmpliSolveAmpliconCoverage: panel " << a.panel_design << ", normals " << a.germline_dir << ", tumours "
                   << (with_tumours ? a.tumour_dir : std::string("none")) << ", coverage_cutoff " << cov << ", min_normals " << min_normals
@@ -72,15 +44,12 @@ int run_amplicon_coverage(const AcArgs &a)
                   << ", exclude_chrom " << a.exclude_chrom << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
         dev_async.start();
-        Panel panel;
-        panel_from_bed(a.panel_design, panel); // no reference base is needed: the packer keys a line by chromosome and coordinate
-        std::vector<std::pair<std::string, std::string>> sets[2];
-        sets[0] = list_count_files(a.germline_dir, std::string());
-        if (with_tumours) sets[1] = list_count_files(a.tumour_dir, std::string());
-        const int n_normals = (int)sets[0].size(), n_tumours = (int)sets[1].size(), S = n_normals + n_tumours;
-        const int64_t P = panel.P();
-        if (P <= 0) throw Error{AMPLI_E_INVALID, "the panel has no positions"};
-        if (n_normals <= 0) throw Error{AMPLI_E_INVALID, "no count files in " + a.germline_dir};
+        CohortInputs in;
+        load_cohort(in, a.panel_design, nullptr, std::string(), a.germline_dir, a.tumour_dir, true);
+        const Panel &panel = in.panel;
+        const std::vector<std::string> &names = in.names;
+        const int n_normals = in.n_normals, n_tumours = in.n_tumours, S = n_normals + n_tumours;
+        const int64_t P = in.P;
         // the amplicons' lists: a BED row's walk entries whose position is listed once in the BED -- a position under two overlapping
         // amplicons carries both amplicons' reads and would count towards neither cleanly -- or all its entries if none is left
         const int A = (int)panel.rows.size();
@@ -104,37 +73,24 @@ int run_amplicon_coverage(const AcArgs &a)
             throw Error{AMPLI_E_RANGE, "at most " + std::to_string(AMPLI_AMPLICON_MAX) + " amplicons and as many normals are supported, got " +
                                            std::to_string(A) + " amplicons and " + std::to_string(n_normals) + " normals"};
         Dev &dev = dev_async.get();
-        size_t free_b = 0, total_b = 0;
-        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
+        const size_t free_b = device_free_bytes(dev);
         // what stays resident: the sums, the ratios and z of every (sample, amplicon), and the lists; beside them one chunk of records
         const size_t cells = (size_t)S * (size_t)A;
         const size_t resident = cells * (AMPLI_AMP_SUMS * sizeof(int64_t) + 2 * sizeof(double)) + (size_t)(W + A + 1) * sizeof(uint32_t);
         const size_t reserve = (size_t)1 << 30;
-        if (resident + reserve > free_b)
-            throw Error{AMPLI_E_NOMEM, "the samples do not fit the device: " + std::to_string(resident) + " bytes of amplicon sums and ratios for " +
-                                           std::to_string(S) + " samples and " + std::to_string(A) + " amplicons, " + std::to_string(reserve) +
-                                           " bytes kept for the streamed records, " + std::to_string(free_b) + " bytes free"};
+        require_fits(resident, reserve, free_b,
+                     "the samples do not fit the device: " + std::to_string(resident) + " bytes of amplicon sums and ratios for " + std::to_string(S) +
+                         " samples and " + std::to_string(A) + " amplicons, " + std::to_string(reserve) + " bytes kept for the streamed records, " +
+                         std::to_string(free_b) + " bytes free");
         int64_t *d_sums = dev.alloc<int64_t>(cells * AMPLI_AMP_SUMS);
         const uint32_t *d_off = dev.upload(amp_off.data(), amp_off.size());
         const uint32_t *d_pos = dev.upload(amp_pos.data(), amp_pos.size());
         const uint8_t *d_use = dev.upload(use.data(), use.size());
-        std::vector<std::string> names;
         DevSlot slot;
-        int base = 0;
-        for (int set = 0; set < 2; ++set) {
-            if (sets[set].empty()) continue;
-            const std::unique_ptr<ChunkStream> cs = open_stream(panel, sets[set], false);
-            for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
-                const ampli_records r = upload_chunk(dev, slot, *c, false);
-                dev.check(dev.api->amplicon_depth_records(dev.ctx, &r, P, A, d_off, d_pos, W, cov,
-                                                          d_sums + (size_t)(base + c->first) * (size_t)A * AMPLI_AMP_SUMS),
-                          "ampli_amplicon_depth_records");
-                dev.sync(); // the chunk's host buffers go back to the parsers, its device buffers to the next chunk
-                cs->release(c);
-            }
-            for (const auto &f : sets[set]) names.push_back(f.second);
-            base += (int)sets[set].size();
-        }
+        for_each_chunk(dev, in, slot, [&](const ampli_records &r, Chunk &, const int first) {
+            dev.check(dev.api->amplicon_depth_records(dev.ctx, &r, P, A, d_off, d_pos, W, cov, d_sums + (size_t)first * (size_t)A * AMPLI_AMP_SUMS),
+                      "ampli_amplicon_depth_records");
+        });
         int64_t *d_total_n = dev.alloc<int64_t>((size_t)n_normals), *d_total = dev.alloc<int64_t>((size_t)S);
         double *d_ref = dev.alloc<double>((size_t)A * 2), *d_centre = dev.alloc<double>((size_t)S);
         uint8_t *d_status = dev.alloc<uint8_t>((size_t)A);
@@ -226,19 +182,12 @@ int run_amplicon_coverage(const AcArgs &a)
             summary += names[(size_t)s] + (s < n_normals ? "\tN\t" : "\tT\t") + std::to_string((long long)total[(size_t)s]) + "\t" +
                        num(kRatio, centre[(size_t)s]) + "\t" + std::to_string(kk[(size_t)s]) + "\t" + std::to_string(below) + "\n";
         }
-        mkdir_p(a.output_dir);
-        std::ofstream(a.output_dir + "/Amplicon_Reference.txt") << reference;
-        std::ofstream(a.output_dir + "/Amplicon_Ratios.txt") << ratios;
-        std::ofstream(a.output_dir + "/Amplicon_Genes.txt") << gene_rows;
-        std::ofstream(a.output_dir + "/Amplicon_Summary.txt") << summary;
+        write_files(a.output_dir,
+                    {{"Amplicon_Reference.txt", reference}, {"Amplicon_Ratios.txt", ratios}, {"Amplicon_Genes.txt", gene_rows}, {"Amplicon_Summary.txt", summary}});
         std::cout << S << " samples, " << A << " amplicons: " << by_status[AMPLI_AMPLICON_OK] << " OK, " << by_status[AMPLI_AMPLICON_FEW] << " FEW, "
                   << by_status[AMPLI_AMPLICON_DARK] << " DARK; " << gains << " (sample, gene) GAIN, " << losses << " LOSS" << std::endl;
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveAmpliconCoverage", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveAmpliconCoverage", e.what());
-    }
+    });
 }
 
 } // namespace ampli

@@ -4,101 +4,55 @@
 // source, and the fraction of an ordered pair is estimated here from the pair's nine sums.  Two passes over the files: the first
 // encodes every chunk into its rows of the one resident plane buffer (as AmpliSolveSampleConcordance does), the second streams
 // every chunk again and fills its rows of the resident N x N x 9 matrix.  Records never stay on the device.
-#include "pipeline.hpp"
-
-#include <cmath>
+#include "command.hpp"
 
 #include "../ampli_math.h"
 
 namespace ampli {
 
-namespace {
-
-// a whole decimal integer >= 1
-int parse_count(const std::string &s, const char *what)
-{
-    char *end = nullptr;
-    const long v = std::strtol(s.c_str(), &end, 10);
-    if (s.empty() || *end || v < 1 || v > 0x7FFFFFFFl) throw Error{AMPLI_E_INVALID, std::string(what) + " must be an integer >= 1, got '" + s + "'"};
-    return (int)v;
-}
-
-// "%.5f", or NA for the NaN of a pair without depth
-std::string f5(double x)
-{
-    if (std::isnan(x)) return "NA";
-    char b[64];
-    snprintf(b, sizeof b, "%.5f", x);
-    return b;
-}
-
-} // namespace
-
 int run_contamination(const CtArgs &a)
 {
-    try {
+    return run_command("AmpliSolveContamination", [&]() -> int {
+        const char *const kFraction = "%.5f"; // NA for the NaN of a pair without depth
         ampli_genotype_params prm{100, 100, 250, 750, 900};
-        prm.min_depth = parse_count(a.min_depth, "min_depth");
-        const int min_sites = parse_count(a.min_sites, "min_sites");
-        char *end = nullptr;
-        const double min_fraction = std::strtod(a.min_fraction.c_str(), &end);
-        if (a.min_fraction.empty() || *end || !(min_fraction > 0.0 && min_fraction <= 1.0))
-            throw Error{AMPLI_E_INVALID, "min_fraction must be a number in (0, 1], got '" + a.min_fraction + "'"};
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveContamination runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        prm.min_depth = parse_int(a.min_depth, "min_depth", 1);
+        const int min_sites = parse_int(a.min_sites, "min_sites", 1);
+        const double min_fraction = parse_number(a.min_fraction, "min_fraction", "in (0, 1]", [](double v) { return v > 0.0 && v <= 1.0; });
+        require_single_gpu("AmpliSolveContamination");
         const bool with_tumours = a.tumour_dir != "-";
         std::cout << "AmpliSolveContamination: panel " << a.panel_design << ", normals " << a.germline_dir << ", tumours "
                   << (with_tumours ? a.tumour_dir : std::string("none")) << ", min_depth " << prm.min_depth << ", min_sites " << min_sites
                   << ", min_fraction " << min_fraction << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
         dev_async.start();
-        Panel panel;
-        panel_from_bed(a.panel_design, panel); // no reference base is needed: the packer keys a line by chromosome and coordinate
-        std::vector<std::pair<std::string, std::string>> sets[2];
-        sets[0] = list_count_files(a.germline_dir, std::string());
-        if (with_tumours) sets[1] = list_count_files(a.tumour_dir, std::string());
-        const int n_normals = (int)sets[0].size(), n_tumours = (int)sets[1].size(), N = n_normals + n_tumours;
-        const int64_t P = panel.P();
-        if (P <= 0) throw Error{AMPLI_E_INVALID, "the panel has no positions"};
+        CohortInputs in;
+        load_cohort(in, a.panel_design, nullptr, std::string(), a.germline_dir, a.tumour_dir, false);
+        const std::vector<std::string> &names = in.names;
+        const int n_normals = in.n_normals, n_tumours = in.n_tumours, N = n_normals + n_tumours;
+        const int64_t P = in.P;
         const size_t W = (size_t)((P + 63) / 64);
         Dev &dev = dev_async.get();
-        size_t free_b = 0, total_b = 0;
-        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
+        const size_t free_b = device_free_bytes(dev);
         // what stays resident: the planes and the N x N x 9 matrix of sums; beside them one chunk of records at a time
         const size_t plane_bytes = (size_t)N * AMPLI_GENO_PLANES * W * 8, sum_bytes = (size_t)N * (size_t)N * AMPLI_CONTAM_SUMS * sizeof(int64_t);
         const size_t reserve = (size_t)1 << 30;
-        if (plane_bytes + sum_bytes + reserve > free_b)
-            throw Error{AMPLI_E_NOMEM, "the samples do not fit the device: " + std::to_string(plane_bytes) + " bytes of genotype planes and " +
-                                           std::to_string(sum_bytes) + " bytes of pair sums for " + std::to_string(N) + " samples, " +
-                                           std::to_string(reserve) + " bytes kept for the streamed records, " + std::to_string(free_b) + " bytes free"};
+        require_fits(plane_bytes + sum_bytes, reserve, free_b,
+                     "the samples do not fit the device: " + std::to_string(plane_bytes) + " bytes of genotype planes and " + std::to_string(sum_bytes) +
+                         " bytes of pair sums for " + std::to_string(N) + " samples, " + std::to_string(reserve) +
+                         " bytes kept for the streamed records, " + std::to_string(free_b) + " bytes free");
         uint64_t *d_planes = dev.alloc<uint64_t>((size_t)N * AMPLI_GENO_PLANES * W);
         int64_t *d_sums = dev.alloc<int64_t>((size_t)N * (size_t)N * AMPLI_CONTAM_SUMS);
         // normals, then tumours, each in its visit order, twice: 1. encode the chunk into its rows of the planes; 2. once every source
         // is encoded, the chunk's recipients against all N sources into its rows of the matrix
-        std::vector<std::string> names;
         DevSlot slot;
-        for (int pass = 0; pass < 2; ++pass) {
-            int base = 0;
-            for (int set = 0; set < 2; ++set) {
-                if (sets[set].empty()) continue;
-                const std::unique_ptr<ChunkStream> cs = open_stream(panel, sets[set], false);
-                for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
-                    const ampli_records r = upload_chunk(dev, slot, *c, false);
-                    uint64_t *rows = d_planes + (size_t)(base + c->first) * AMPLI_GENO_PLANES * W;
-                    if (pass == 0)
-                        dev.check(dev.api->genotype_planes_records(dev.ctx, &r, P, &prm, rows), "ampli_genotype_planes_records");
-                    else
-                        dev.check(dev.api->contamination_records(dev.ctx, &r, P, rows, d_planes, N,
-                                                                 d_sums + (size_t)(base + c->first) * (size_t)N * AMPLI_CONTAM_SUMS),
-                                  "ampli_contamination_records");
-                    dev.sync(); // the chunk's host buffers go back to the parsers, its device buffers to the next chunk
-                    cs->release(c);
-                }
-                if (pass == 0)
-                    for (const auto &f : sets[set]) names.push_back(f.second);
-                base += (int)sets[set].size();
-            }
-        }
+        for_each_chunk(dev, in, slot, [&](const ampli_records &r, Chunk &, const int first) {
+            dev.check(dev.api->genotype_planes_records(dev.ctx, &r, P, &prm, d_planes + (size_t)first * AMPLI_GENO_PLANES * W), "ampli_genotype_planes_records");
+        });
+        for_each_chunk(dev, in, slot, [&](const ampli_records &r, Chunk &, const int first) {
+            dev.check(dev.api->contamination_records(dev.ctx, &r, P, d_planes + (size_t)first * AMPLI_GENO_PLANES * W, d_planes, N,
+                                                     d_sums + (size_t)first * (size_t)N * AMPLI_CONTAM_SUMS),
+                      "ampli_contamination_records");
+        });
         std::vector<int64_t> sums((size_t)N * (size_t)N * AMPLI_CONTAM_SUMS);
         if (N > 0) dev.download(sums.data(), (const int64_t *)d_sums, sums.size());
         dev.sync();
@@ -126,7 +80,7 @@ int run_contamination(const CtArgs &a)
                         const int64_t *s = at(i, j);
                         snprintf(b, sizeof b, "\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t%lld\t", (long long)s[0], (long long)s[1], (long long)s[2],
                                  (long long)s[3], (long long)s[4], (long long)s[5], (long long)s[6], (long long)s[7], (long long)s[8]);
-                        pairs += names[(size_t)i] + "\t" + names[(size_t)j] + b + f5(x.fraction) + "\t" + f5(x.se) + "\n";
+                        pairs += names[(size_t)i] + "\t" + names[(size_t)j] + b + num(kFraction, x.fraction) + "\t" + num(kFraction, x.se) + "\n";
                     }
                 }
                 if (x.status == AMPLI_CONTAM_STATUS_UNDETERMINED) continue;
@@ -140,7 +94,7 @@ int run_contamination(const CtArgs &a)
             } else {
                 const Est x = est(i, best);
                 snprintf(b, sizeof b, "\t%lld\t", (long long)(at(i, best)[AMPLI_CONTAM_SITES_HOM] + at(i, best)[AMPLI_CONTAM_SITES_HET]));
-                samples += names[(size_t)best] + b + f5(x.fraction) + "\t" + f5(x.se) + "\t" + kStatus[x.status] + "\n";
+                samples += names[(size_t)best] + b + num(kFraction, x.fraction) + "\t" + num(kFraction, x.se) + "\t" + kStatus[x.status] + "\n";
             }
         }
         snprintf(b, sizeof b,
@@ -148,18 +102,11 @@ int run_contamination(const CtArgs &a)
                  "pairs_contaminated=%lld\npairs_clean=%lld\npairs_undetermined=%lld\n",
                  n_normals, n_tumours, prm.min_depth, prm.absent_max_pm, prm.het_min_pm, prm.het_max_pm, prm.hom_min_pm, min_sites, min_fraction,
                  by_status[AMPLI_CONTAM_STATUS_CONTAMINATED], by_status[AMPLI_CONTAM_STATUS_CLEAN], by_status[AMPLI_CONTAM_STATUS_UNDETERMINED]);
-        mkdir_p(a.output_dir);
-        std::ofstream(a.output_dir + "/Contamination_Samples.txt") << samples;
-        std::ofstream(a.output_dir + "/Contamination_Pairs.txt") << pairs;
-        std::ofstream(a.output_dir + "/Contamination_Summary.txt") << b;
+        write_files(a.output_dir, {{"Contamination_Samples.txt", samples}, {"Contamination_Pairs.txt", pairs}, {"Contamination_Summary.txt", b}});
         std::cout << N << " samples: " << by_status[AMPLI_CONTAM_STATUS_CONTAMINATED] << " ordered pairs CONTAMINATED, "
                   << by_status[AMPLI_CONTAM_STATUS_CLEAN] << " CLEAN, " << by_status[AMPLI_CONTAM_STATUS_UNDETERMINED] << " UNDETERMINED" << std::endl;
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveContamination", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveContamination", e.what());
-    }
+    });
 }
 
 } // namespace ampli

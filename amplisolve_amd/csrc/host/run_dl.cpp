@@ -3,7 +3,7 @@
 // alternative counts with which the calling gate would pass on that line's own depths.  The error table and the tumour files are read
 // and streamed exactly as run_variant_calling does; one ampli_limit_records per chunk; the cells the device leaves open (RECHECK) are
 // settled by the literal scan; one file per tumour file and a summary.
-#include "pipeline.hpp"
+#include "command.hpp"
 
 namespace ampli {
 
@@ -18,7 +18,7 @@ const char *dl_name(int status)
 
 int run_detection_limits(const DlArgs &a)
 {
-    try {
+    return run_command("AmpliSolveDetectionLimit", [&]() -> int {
         int cov = std::atoi(a.coverage_cutoff.c_str());
         if (cov <= 0) cov = 100; // VC:262-275
         std::vector<float> levels;
@@ -33,8 +33,7 @@ int run_detection_limits(const DlArgs &a)
             if (levels.empty() || levels.size() > AMPLI_LIMIT_MAX_LEVELS) throw Error{AMPLI_E_INVALID, "levels: one to 8 allele fractions are required"};
         }
         const int L = (int)levels.size(), NC = AMPLI_LIMIT_COUNTERS + L;
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveDetectionLimit runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        require_single_gpu("AmpliSolveDetectionLimit");
         const char *ve = getenv("AMPLISOLVE_LIMIT_VERIFY");
         const bool verify_all = ve && std::string(ve) == "all";
         std::cout << "AmpliSolveDetectionLimit: table " << a.error_file << ", tumours " << a.tumour_dir << ", coverage_cutoff " << cov << ", output "
@@ -187,11 +186,7 @@ int run_detection_limits(const DlArgs &a)
         std::cout << std::endl;
         if (n_diff) throw Error{AMPLI_E_INVALID, "AMPLISOLVE_LIMIT_VERIFY=all: device and host differ"};
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveDetectionLimit", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveDetectionLimit", e.what());
-    }
+    });
 }
 
 } // namespace ampli

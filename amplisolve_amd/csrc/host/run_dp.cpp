@@ -6,7 +6,7 @@
 // file per tumour file and a summary.  The probabilities are the device's: 28 M pairs at config 3 are not scored twice.
 #include <algorithm>
 
-#include "pipeline.hpp"
+#include "command.hpp"
 
 namespace ampli {
 
@@ -20,7 +20,7 @@ struct DpCounts { int64_t lines = 0, pairs = 0, ok = 0; double median_lod = 0; s
 
 int run_detection_power(const DpArgs &a)
 {
-    try {
+    return run_command("AmpliSolveDetectionPower", [&]() -> int {
         int cov = std::atoi(a.coverage_cutoff.c_str());
         if (cov <= 0) cov = 100; // VC:262-275
         std::vector<float> levels;
@@ -44,8 +44,7 @@ int run_detection_power(const DpArgs &a)
                 throw Error{AMPLI_E_INVALID, "confidence: '" + a.confidence + "' is not a probability in [0.5, 0.99]"};
         }
         const int L = (int)levels.size(), NC = 1 + L, NLC = AMPLI_LIMIT_COUNTERS;
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveDetectionPower runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        require_single_gpu("AmpliSolveDetectionPower");
         std::cout << "AmpliSolveDetectionPower: table " << a.error_file << ", tumours " << a.tumour_dir << ", coverage_cutoff " << cov << ", confidence "
                   << conf << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
@@ -201,11 +200,7 @@ int run_detection_power(const DpArgs &a)
         if (sum.fail()) throw Error{AMPLI_E_INVALID, "could not write Summary_Detection_Power.txt"};
         std::cout << "AmpliSolveDetectionPower: " << T << " files, " << n_recheck << " cells settled on the host" << std::endl;
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveDetectionPower", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveDetectionPower", e.what());
-    }
+    });
 }
 
 } // namespace ampli

@@ -5,7 +5,7 @@
 // the device; the tumours stream chunk by chunk, each against every resident chunk into the same two count arrays (the first
 // overwrites, the others accumulate); the candidate rule (ampli_exceedance_candidate, ampli_math.h) and the four files here.
 // tumour_dir=- runs the normals against themselves, each without its own file: the leave-self-out false-candidate rate of the panel.
-#include "pipeline.hpp"
+#include "command.hpp"
 
 #include "../ampli_math.h"
 
@@ -13,21 +13,8 @@ namespace ampli {
 
 namespace {
 
-// a whole decimal integer in [lo, hi]
-int parse_int(const std::string &s, const char *what, const long lo, const long hi = 0x7FFFFFFFl)
-{
-    char *end = nullptr;
-    const long v = std::strtol(s.c_str(), &end, 10);
-    if (s.empty() || *end || v < lo || v > hi) {
-        const std::string range = hi == 0x7FFFFFFFl ? ">= " + std::to_string(lo) : "in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]";
-        throw Error{AMPLI_E_INVALID, std::string(what) + " must be an integer " + range + ", got '" + s + "'"};
-    }
-    return (int)v;
-}
-
-struct Resident { // a chunk of the normals that stays on the device; with tumour_dir=- also the host's copy of its primary records
-    ampli_records r;
-    int first, n, layout;
+struct ExResident : Resident { // a chunk of the normals that stays on the device; with tumour_dir=- also the host's copy of its primary records
+    int layout;
     std::vector<char> prim;
 };
 
@@ -42,7 +29,7 @@ std::string per_1000(const long long c, const long long e)
 
 int run_normal_exceedance(const ExArgs &a)
 {
-    try {
+    return run_command("AmpliSolveNormalExceedance", [&]() -> int {
         const int cov = parse_int(a.coverage_cutoff, "coverage_cutoff", 0);
         const int call_cov = parse_int(a.calling_cutoff, "calling_cutoff", 0);
         ampli_exceedance_params prm;
@@ -50,8 +37,7 @@ int run_normal_exceedance(const ExArgs &a)
         prm.min_vaf_pm = parse_int(a.min_vaf_pm, "min_vaf_pm", 0, 1000);
         prm.min_normals = parse_int(a.min_normals, "min_normals", 0);
         prm.max_normals = parse_int(a.max_normals, "max_normals", 0, AMPLI_EXCEEDANCE_MAX_NORMALS);
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveNormalExceedance runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        require_single_gpu("AmpliSolveNormalExceedance");
         const bool with_tumours = a.tumour_dir != "-";
         std::cout << "AmpliSolveNormalExceedance: panel " << a.panel_design << ", normals " << a.germline_dir << ", tumours "
                   << (with_tumours ? a.tumour_dir : std::string("the normals themselves")) << ", coverage_cutoff " << cov << ", calling_cutoff " << call_cov
@@ -59,49 +45,24 @@ int run_normal_exceedance(const ExArgs &a)
                   << prm.max_normals << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
         dev_async.start();
-        Panel panel;
-        panel_from_bed(a.panel_design, panel);
-        if (!a.refbases_file.empty()) panel_load_refbases_file(panel, a.refbases_file);
-        else panel_load_fasta(panel, a.reference_genome);
-        const auto normals = list_count_files(a.germline_dir, std::string());
-        std::vector<std::pair<std::string, std::string>> tumours;
-        if (with_tumours) tumours = list_count_files(a.tumour_dir, std::string());
-        const int n_normals = (int)normals.size(), n_tumours = (int)tumours.size();
-        const int64_t P = panel.P();
-        if (P <= 0) throw Error{AMPLI_E_INVALID, "the panel has no positions"};
-        if (n_normals <= 0) throw Error{AMPLI_E_INVALID, "no count files in " + a.germline_dir};
+        CohortInputs in;
+        load_cohort(in, a.panel_design, &a.reference_genome, a.refbases_file, a.germline_dir, a.tumour_dir, true);
+        const Panel &panel = in.panel;
+        const int n_normals = in.n_normals, n_tumours = in.n_tumours;
+        const int64_t P = in.P;
         if (n_normals > AMPLI_EXCEEDANCE_MAX_NORMALS)
             throw Error{AMPLI_E_RANGE, "a panel of at most " + std::to_string(AMPLI_EXCEEDANCE_MAX_NORMALS) + " normals is supported, " + a.germline_dir + " has " +
                                            std::to_string(n_normals)};
-        const auto &files = with_tumours ? tumours : normals; // the files under test
+        const FileSet &files = in.sets[with_tumours ? 1 : 0]; // the files under test
         const int F = (int)files.size();
         Dev &dev = dev_async.get();
-        size_t free_b = 0, total_b = 0;
-        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
         // every chunk of the normals stays resident: refuse before the device runs out (beside them one chunk of tumours and its counts)
-        const size_t reserve = (size_t)1 << 30;
-        std::vector<DevSlot> slots;
-        slots.reserve(4096);
-        std::vector<Resident> res;
-        size_t resident_bytes = 0;
-        {
-            const std::unique_ptr<ChunkStream> cs = open_stream(panel, normals, false);
-            for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
-                const size_t b = (size_t)c->n * (size_t)(P + c->E) * record_bytes(c->layout) + (size_t)c->n * (size_t)(P + c->E) * 5;
-                if (resident_bytes + b + reserve > free_b)
-                    throw Error{AMPLI_E_NOMEM, "the normals do not fit the device: " + std::to_string(resident_bytes + b + reserve) +
-                                                   " bytes of records and buffers needed so far, " + std::to_string(free_b) + " bytes free"};
-                resident_bytes += b;
-                slots.emplace_back();
-                Resident x;
-                x.r = upload_chunk(dev, slots.back(), *c, false);
-                x.first = c->first; x.n = c->n; x.layout = c->layout;
-                if (!with_tumours) x.prim.assign((const char *)c->prim, (const char *)c->prim + (size_t)c->n * (size_t)P * record_bytes(c->layout));
-                dev.sync(); // the chunk's host buffers go back to the parsers
-                res.push_back(std::move(x));
-                cs->release(c);
-            }
-        }
+        std::vector<ExResident> res;
+        upload_resident(dev, panel, in.sets[0], false, 5, (size_t)1 << 30, device_free_bytes(dev), "the normals do not fit the device",
+                        [&](const Resident &x, Chunk &c) {
+                            res.push_back(ExResident{x, c.layout, {}});
+                            if (!with_tumours) res.back().prim.assign((const char *)c.prim, (const char *)c.prim + (size_t)c.n * (size_t)P * record_bytes(c.layout));
+                        });
         const uint8_t *d_ref = dev.upload(panel.ref_code.data(), panel.ref_code.size());
 
         std::string candidates = "sample\tchrom\tposition\tsubstitution\tXfw\tXrs\tFW\tBW\tAF\tElig\tGE_fw\tGE_rs\n";
@@ -155,17 +116,10 @@ int run_normal_exceedance(const ExArgs &a)
             }
         };
         if (with_tumours) {
-            if (n_tumours > 0) {
-                DevSlot slot;
-                const std::unique_ptr<ChunkStream> cs = open_stream(panel, tumours, false);
-                for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
-                    const ampli_records r = upload_chunk(dev, slot, *c, false);
-                    test_chunk(r, c->first, c->n, c->layout, (const char *)c->prim);
-                    cs->release(c);
-                }
-            }
+            DevSlot slot;
+            for_each_chunk(dev, in, slot, [&](const ampli_records &r, Chunk &c, int) { test_chunk(r, c.first, c.n, c.layout, (const char *)c.prim); }, 1);
         } else {
-            for (const Resident &x : res) test_chunk(x.r, x.first, x.n, x.layout, x.prim.data());
+            for (const ExResident &x : res) test_chunk(x.r, x.first, x.n, x.layout, x.prim.data());
         }
 
         // Exceedance_Samples.txt, Exceedance_Positions.txt, Exceedance_Summary.txt
@@ -199,19 +153,12 @@ int run_normal_exceedance(const ExArgs &a)
                  "min_vaf_pm=%lld\nmin_normals=%lld\nmax_normals=%lld\nskip_same_index=%d\nevaluated=%lld\ncandidates=%lld\ncandidates_per_1000=%s\n",
                  n_normals, n_tumours, (long long)P, with_reference, cov, call_cov, (long long)prm.min_alt_reads, (long long)prm.min_vaf_pm,
                  (long long)prm.min_normals, (long long)prm.max_normals, with_tumours ? 0 : 1, evaluated, n_candidates, per_1000(n_candidates, evaluated).c_str());
-        mkdir_p(a.output_dir);
-        std::ofstream(a.output_dir + "/Exceedance_Candidates.txt") << candidates;
-        std::ofstream(a.output_dir + "/Exceedance_Samples.txt") << samples;
-        std::ofstream(a.output_dir + "/Exceedance_Positions.txt") << positions;
-        std::ofstream(a.output_dir + "/Exceedance_Summary.txt") << b;
+        write_files(a.output_dir, {{"Exceedance_Candidates.txt", candidates}, {"Exceedance_Samples.txt", samples}, {"Exceedance_Positions.txt", positions},
+                                   {"Exceedance_Summary.txt", b}});
         std::cout << F << " files against " << n_normals << " normals, " << P << " positions: " << n_candidates << " candidates in " << evaluated
                   << " evaluated cells" << std::endl;
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveNormalExceedance", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveNormalExceedance", e.what());
-    }
+    });
 }
 
 } // namespace ampli

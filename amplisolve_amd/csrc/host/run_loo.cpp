@@ -2,15 +2,13 @@
 // AmpliSolveLeaveOneOut: for every normal of germline_dir, the calling gate on its own file against the error table of the
 // other S-1 normals, for each C of a list.  Every chunk of the cohort stays resident on the device; per C one reduce over the chunks,
 // one leave-one-out launch per chunk, the emitted pairs re-scored with the reference's operation sequence, three files.
-#include "pipeline.hpp"
+#include "command.hpp"
 
 namespace ampli {
 
 namespace {
 struct LooRow : CallBase { long double q_fw, q_bw; float thr_fw, thr_bw; int code; };
-struct Resident { // a chunk that stays on the device, with what maps its records back to lines and positions (record_line)
-    ampli_records r;
-    int first, n;
+struct LooResident : Resident { // a chunk that stays on the device, with what maps its records back to lines and positions (record_line)
     int64_t P, E;
     std::vector<uint32_t> ext_pos;
     std::vector<int32_t> line_prim, line_ext;
@@ -26,7 +24,7 @@ std::string thr_text(float thr, int code)
 
 int run_leave_one_out(const LooArgs &a)
 {
-    try {
+    return run_command("AmpliSolveLeaveOneOut", [&]() -> int {
         std::vector<float> Cs;
         {
             std::stringstream ss(a.C_value);
@@ -40,8 +38,7 @@ int run_leave_one_out(const LooArgs &a)
         if (cov <= 0) cov = 100; // EE:380-388
         int call_cov = std::atoi(a.calling_cutoff.c_str());
         if (call_cov <= 0) call_cov = 100; // VC:262-275
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveLeaveOneOut runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        require_single_gpu("AmpliSolveLeaveOneOut");
         std::cout << "AmpliSolveLeaveOneOut: panel " << a.panel_design << ", normals " << a.germline_dir << ", coverage_cutoff " << cov
                   << ", calling_cutoff " << call_cov << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
@@ -55,32 +52,12 @@ int run_leave_one_out(const LooArgs &a)
         if (S == 0) throw Error{AMPLI_E_INVALID, "no count files in " + a.germline_dir};
         const int64_t P = panel.P();
         Dev &dev = dev_async.get();
-        size_t free_b = 0, total_b = 0;
-        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
+        const size_t free_b = device_free_bytes(dev);
         // every chunk stays resident: refuse before the device runs out (the records, plus the table, masks and lists the passes add)
-        const size_t reserve = dev.api->acc_bytes(P) + ((size_t)64 << 20);
-        std::vector<DevSlot> slots;
-        slots.reserve(4096);
-        std::vector<Resident> res;
-        size_t resident_bytes = 0;
-        {
-            const std::unique_ptr<ChunkStream> cs = open_stream(panel, files, true);
-            for (Chunk *c; (c = cs->next()) != nullptr;) {
-                const size_t b = (size_t)c->n * (size_t)(P + c->E) * record_bytes(c->layout) + (size_t)c->n * (size_t)(P + c->E) * 5;
-                if (resident_bytes + b + reserve > free_b)
-                    throw Error{AMPLI_E_NOMEM, "the cohort does not fit the device: " + std::to_string(resident_bytes + b + reserve) +
-                                                   " bytes of records and buffers needed so far, " + std::to_string(free_b) + " bytes free"};
-                resident_bytes += b;
-                slots.emplace_back();
-                Resident x;
-                x.r = upload_chunk(dev, slots.back(), *c, false);
-                x.first = c->first; x.n = c->n; x.P = P; x.E = c->E;
-                x.ext_pos = c->ext_pos; x.line_prim = c->line_prim; x.line_ext = c->line_ext;
-                dev.sync(); // the chunk's host buffers go back to the parsers
-                res.push_back(std::move(x));
-                cs->release(c);
-            }
-        }
+        std::vector<LooResident> res;
+        std::vector<DevSlot> slots =
+            upload_resident(dev, panel, files, true, 5, dev.api->acc_bytes(P) + ((size_t)64 << 20), free_b, "the cohort does not fit the device",
+                            [&](const Resident &x, Chunk &c) { res.push_back(LooResident{x, P, c.E, c.ext_pos, c.line_prim, c.line_ext}); });
         uint8_t *d_ref = dev.upload(panel.ref_code.data(), panel.ref_code.size());
         void *d_accbuf = dev.alloc<char>(dev.api->acc_bytes(P));
         ampli_acc_table acc{};
@@ -106,7 +83,7 @@ int run_leave_one_out(const LooArgs &a)
             // 2. one leave-one-out launch per resident chunk
             std::vector<LooRow> rows;
             for (size_t k = 0; k < res.size(); ++k) {
-                const Resident &x = res[k];
+                const LooResident &x = res[k];
                 const int64_t R = P + x.E;
                 uint8_t *d_mask = (uint8_t *)slots[k].mask.ensure(dev, (size_t)x.n * R + 4);
                 std::vector<int32_t> cpos_before((size_t)P);
@@ -213,11 +190,7 @@ int run_leave_one_out(const LooArgs &a)
             std::cout << outs[i].line << std::endl;
         }
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveLeaveOneOut", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveLeaveOneOut", e.what());
-    }
+    });
 }
 
 } // namespace ampli

@@ -3,20 +3,19 @@
 // records' alternative counts against the pooled rate the error table would use, its z-score under Haldane's exact moments, and per
 // normal its share of the statistic against the null mean.  The cohort is loaded and streamed as run_loo.cpp does: every chunk stays
 // resident on the device; pass 1 is the reduce with C = 0 over the chunks (the totals), pass 2 one dispersion launch per chunk.
-#include "pipeline.hpp"
+#include "command.hpp"
 
 namespace ampli {
 
 int run_panel_dispersion(const PdArgs &a)
 {
-    try {
+    return run_command("AmpliSolvePanelDispersion", [&]() -> int {
         int cov = std::atoi(a.coverage_cutoff.c_str());
         if (cov <= 0) cov = 100; // EE:380-388
         char *end = nullptr;
         const double z_cutoff = std::strtod(a.z_cutoff.c_str(), &end);
         if (a.z_cutoff.empty() || *end || !std::isfinite(z_cutoff)) throw Error{AMPLI_E_INVALID, "z_cutoff must be a number, got '" + a.z_cutoff + "'"};
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolvePanelDispersion runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        require_single_gpu("AmpliSolvePanelDispersion");
         std::cout << "AmpliSolvePanelDispersion: panel " << a.panel_design << ", normals " << a.germline_dir << ", coverage_cutoff " << cov
                   << ", z_cutoff " << z_cutoff << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
@@ -30,32 +29,11 @@ int run_panel_dispersion(const PdArgs &a)
         if (S == 0) throw Error{AMPLI_E_INVALID, "no count files in " + a.germline_dir};
         const int64_t P = panel.P();
         Dev &dev = dev_async.get();
-        size_t free_b = 0, total_b = 0;
-        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
+        const size_t free_b = device_free_bytes(dev);
         // every chunk stays resident: refuse before the device runs out (the records, plus the table, the planes and the partials)
-        const size_t reserve = dev.api->acc_bytes(P) + (size_t)P * 8 * 30 + ((size_t)64 << 20);
-        struct Resident { ampli_records r; int first, n; };
-        std::vector<DevSlot> slots;
-        slots.reserve(4096);
         std::vector<Resident> res;
-        size_t resident_bytes = 0;
-        {
-            const std::unique_ptr<ChunkStream> cs = open_stream(panel, files, false);
-            for (Chunk *c; (c = cs->next()) != nullptr;) {
-                const size_t b = (size_t)c->n * (size_t)(P + c->E) * record_bytes(c->layout) + (size_t)c->n * (size_t)(P + c->E) * 4;
-                if (resident_bytes + b + reserve > free_b)
-                    throw Error{AMPLI_E_NOMEM, "the cohort does not fit the device: " + std::to_string(resident_bytes + b + reserve) +
-                                                   " bytes of records and buffers needed so far, " + std::to_string(free_b) + " bytes free"};
-                resident_bytes += b;
-                slots.emplace_back();
-                Resident x;
-                x.r = upload_chunk(dev, slots.back(), *c, false);
-                x.first = c->first; x.n = c->n;
-                dev.sync(); // the chunk's host buffers go back to the parsers
-                res.push_back(x);
-                cs->release(c);
-            }
-        }
+        upload_resident(dev, panel, files, false, 4, dev.api->acc_bytes(P) + (size_t)P * 8 * 30 + ((size_t)64 << 20), free_b,
+                        "the cohort does not fit the device", [&](const Resident &x, Chunk &) { res.push_back(x); });
         void *d_accbuf = dev.alloc<char>(dev.api->acc_bytes(P));
         ampli_acc_table acc{};
         dev.check(dev.api->acc_bind(d_accbuf, P, &acc), "ampli_acc_bind");
@@ -118,18 +96,11 @@ int run_panel_dispersion(const PdArgs &a)
         }
         snprintf(b, sizeof b, "normals=%d\ncoverage_cutoff=%d\nz_cutoff=%g\ncells_ok=%lld\ncells_few=%lld\ncells_high=%lld\npositions_high=%lld\n", S, cov,
                  z_cutoff, (long long)counts[0], (long long)counts[1], (long long)counts[2], (long long)counts[3]);
-        mkdir_p(a.output_dir);
-        std::ofstream(a.output_dir + "/panelDispersion.txt") << cellsf;
-        std::ofstream(a.output_dir + "/panelDispersion_samples.txt") << samples;
-        std::ofstream(a.output_dir + "/panelDispersion_summary.txt") << b;
+        write_files(a.output_dir, {{"panelDispersion.txt", cellsf}, {"panelDispersion_samples.txt", samples}, {"panelDispersion_summary.txt", b}});
         std::cout << counts[0] << " cells OK, " << counts[1] << " with too few reads or records, " << counts[2] << " HIGH at " << counts[3] << " positions"
                   << std::endl;
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolvePanelDispersion", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolvePanelDispersion", e.what());
-    }
+    });
 }
 
 } // namespace ampli

@@ -4,81 +4,48 @@
 // the same person, different people, too few het sites to tell -- is decided here from two of the pair's five counts.  The cohorts
 // are streamed: a chunk is uploaded, encoded straight into its rows of the one resident plane buffer and released; records never
 // stay on the device.
-#include "pipeline.hpp"
+#include "command.hpp"
 
 #include "../ampli_math.h"
 
 namespace ampli {
 
-namespace {
-
-// a whole decimal integer >= 1
-int parse_count(const std::string &s, const char *what)
-{
-    char *end = nullptr;
-    const long v = std::strtol(s.c_str(), &end, 10);
-    if (s.empty() || *end || v < 1 || v > 0x7FFFFFFFl) throw Error{AMPLI_E_INVALID, std::string(what) + " must be an integer >= 1, got '" + s + "'"};
-    return (int)v;
-}
-
-} // namespace
-
 int run_sample_concordance(const ScArgs &a)
 {
-    try {
+    return run_command("AmpliSolveSampleConcordance", [&]() -> int {
         ampli_genotype_params prm{100, 100, 250, 750, 900};
-        prm.min_depth = parse_count(a.min_depth, "min_depth");
-        const int min_sites = parse_count(a.min_sites, "min_sites");
-        char *end = nullptr;
-        const double same_fraction = std::strtod(a.same_fraction.c_str(), &end);
-        if (a.same_fraction.empty() || *end || !(same_fraction > 0.0 && same_fraction <= 1.0))
-            throw Error{AMPLI_E_INVALID, "same_fraction must be a number in (0, 1], got '" + a.same_fraction + "'"};
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveSampleConcordance runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        prm.min_depth = parse_int(a.min_depth, "min_depth", 1);
+        const int min_sites = parse_int(a.min_sites, "min_sites", 1);
+        const double same_fraction = parse_number(a.same_fraction, "same_fraction", "in (0, 1]", [](double v) { return v > 0.0 && v <= 1.0; });
+        require_single_gpu("AmpliSolveSampleConcordance");
         const bool with_tumours = a.tumour_dir != "-";
         std::cout << "AmpliSolveSampleConcordance: panel " << a.panel_design << ", normals " << a.germline_dir << ", tumours "
                   << (with_tumours ? a.tumour_dir : std::string("none")) << ", min_depth " << prm.min_depth << ", min_sites " << min_sites
                   << ", same_fraction " << same_fraction << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
         dev_async.start();
-        Panel panel;
-        panel_from_bed(a.panel_design, panel); // no reference base is needed: the packer keys a line by chromosome and coordinate
-        std::vector<std::pair<std::string, std::string>> sets[2];
-        sets[0] = list_count_files(a.germline_dir, std::string());
-        if (with_tumours) sets[1] = list_count_files(a.tumour_dir, std::string());
-        const int n_normals = (int)sets[0].size(), n_tumours = (int)sets[1].size(), N = n_normals + n_tumours;
-        const int64_t P = panel.P();
-        if (P <= 0) throw Error{AMPLI_E_INVALID, "the panel has no positions"};
+        CohortInputs in;
+        load_cohort(in, a.panel_design, nullptr, std::string(), a.germline_dir, a.tumour_dir, false);
+        const std::vector<std::string> &names = in.names;
+        const int n_normals = in.n_normals, n_tumours = in.n_tumours, N = n_normals + n_tumours;
+        const int64_t P = in.P;
         const size_t W = (size_t)((P + 63) / 64);
         Dev &dev = dev_async.get();
-        size_t free_b = 0, total_b = 0;
-        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
+        const size_t free_b = device_free_bytes(dev);
         // what stays resident: the planes and the N x N count matrix; beside them one chunk of records at a time
         const size_t plane_bytes = (size_t)N * AMPLI_GENO_PLANES * W * 8, count_bytes = (size_t)N * (size_t)N * 5 * sizeof(int32_t);
         const size_t reserve = (size_t)1 << 30;
-        if (plane_bytes + count_bytes + reserve > free_b)
-            throw Error{AMPLI_E_NOMEM, "the samples do not fit the device: " + std::to_string(plane_bytes) + " bytes of genotype planes and " +
-                                           std::to_string(count_bytes) + " bytes of pair counts for " + std::to_string(N) + " samples, " +
-                                           std::to_string(reserve) + " bytes kept for the streamed records, " + std::to_string(free_b) + " bytes free"};
+        require_fits(plane_bytes + count_bytes, reserve, free_b,
+                     "the samples do not fit the device: " + std::to_string(plane_bytes) + " bytes of genotype planes and " + std::to_string(count_bytes) +
+                         " bytes of pair counts for " + std::to_string(N) + " samples, " + std::to_string(reserve) +
+                         " bytes kept for the streamed records, " + std::to_string(free_b) + " bytes free");
         uint64_t *d_planes = dev.alloc<uint64_t>((size_t)N * AMPLI_GENO_PLANES * W);
         int32_t *d_counts = dev.alloc<int32_t>((size_t)N * (size_t)N * 5);
         // 1. normals, then tumours, each in its visit order: upload, encode into the chunk's rows, release
-        std::vector<std::string> names;
         DevSlot slot;
-        int base = 0;
-        for (int set = 0; set < 2; ++set) {
-            if (sets[set].empty()) continue;
-            const std::unique_ptr<ChunkStream> cs = open_stream(panel, sets[set], false);
-            for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
-                const ampli_records r = upload_chunk(dev, slot, *c, false);
-                dev.check(dev.api->genotype_planes_records(dev.ctx, &r, P, &prm, d_planes + (size_t)(base + c->first) * AMPLI_GENO_PLANES * W),
-                          "ampli_genotype_planes_records");
-                dev.sync(); // the chunk's host buffers go back to the parsers, its device buffers to the next chunk
-                cs->release(c);
-            }
-            for (const auto &f : sets[set]) names.push_back(f.second);
-            base += (int)sets[set].size();
-        }
+        for_each_chunk(dev, in, slot, [&](const ampli_records &r, Chunk &, const int first) {
+            dev.check(dev.api->genotype_planes_records(dev.ctx, &r, P, &prm, d_planes + (size_t)first * AMPLI_GENO_PLANES * W), "ampli_genotype_planes_records");
+        });
         // 2. every pair at once, the relations here
         dev.check(dev.api->concordance_pairs(dev.ctx, P, d_planes, N, d_planes, N, d_counts), "ampli_concordance_pairs");
         std::vector<int32_t> cnt((size_t)N * (size_t)N * 5);
@@ -127,18 +94,11 @@ int run_sample_concordance(const ScArgs &a)
                  "pairs_same=%lld\npairs_different=%lld\npairs_undetermined=%lld\n",
                  n_normals, n_tumours, prm.min_depth, prm.absent_max_pm, prm.het_min_pm, prm.het_max_pm, prm.hom_min_pm, min_sites, same_fraction,
                  by_relation[AMPLI_RELATION_SAME], by_relation[AMPLI_RELATION_DIFFERENT], by_relation[AMPLI_RELATION_UNDETERMINED]);
-        mkdir_p(a.output_dir);
-        std::ofstream(a.output_dir + "/Concordance_Samples.txt") << samples;
-        std::ofstream(a.output_dir + "/Concordance_Pairs.txt") << pairs;
-        std::ofstream(a.output_dir + "/Concordance_Summary.txt") << b;
+        write_files(a.output_dir, {{"Concordance_Samples.txt", samples}, {"Concordance_Pairs.txt", pairs}, {"Concordance_Summary.txt", b}});
         std::cout << N << " samples: " << by_relation[AMPLI_RELATION_SAME] << " pairs SAME, " << by_relation[AMPLI_RELATION_DIFFERENT] << " DIFFERENT, "
                   << by_relation[AMPLI_RELATION_UNDETERMINED] << " UNDETERMINED" << std::endl;
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveSampleConcordance", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveSampleConcordance", e.what());
-    }
+    });
 }
 
 } // namespace ampli

@@ -4,9 +4,7 @@
 // forward strand in it.  One pass over the normals and then over the tumours: every chunk's primary records are binned by the
 // trinucleotide class of their position into its rows of the one resident S x 68 x 9 matrix; one download; the folds, the reference,
 // the scores and the four files here.  Records never stay on the device.
-#include "pipeline.hpp"
-
-#include <cmath>
+#include "command.hpp"
 
 #include "../ampli_math.h"
 
@@ -14,34 +12,6 @@ namespace ampli {
 
 namespace {
 
-// a whole decimal integer in [lo, hi]
-int parse_int(const std::string &s, const char *what, const long lo, const long hi = 0x7FFFFFFFl)
-{
-    char *end = nullptr;
-    const long v = std::strtol(s.c_str(), &end, 10);
-    if (s.empty() || *end || v < lo || v > hi) {
-        const std::string range = hi == 0x7FFFFFFFl ? ">= " + std::to_string(lo) : "in [" + std::to_string(lo) + ", " + std::to_string(hi) + "]";
-        throw Error{AMPLI_E_INVALID, std::string(what) + " must be an integer " + range + ", got '" + s + "'"};
-    }
-    return (int)v;
-}
-
-double parse_number(const std::string &s, const char *what, const char *range, bool (*ok)(double))
-{
-    char *end = nullptr;
-    const double v = std::strtod(s.c_str(), &end);
-    if (s.empty() || *end || !std::isfinite(v) || !ok(v)) throw Error{AMPLI_E_INVALID, std::string(what) + " must be a number " + range + ", got '" + s + "'"};
-    return v;
-}
-
-// the one printf format of each kind of number; NA for a NaN
-std::string num(const char *fmt, const double x)
-{
-    if (std::isnan(x)) return "NA";
-    char b[64];
-    snprintf(b, sizeof b, fmt, x);
-    return b;
-}
 const char *const kRate = "%.6e", *const kRatio = "%.5f", *const kZ = "%.3f";
 const char kNt[] = "ACGT";
 
@@ -62,7 +32,7 @@ std::string channel_name(const int ch)
 
 int run_substitution_spectrum(const SsArgs &a)
 {
-    try {
+    return run_command("AmpliSolveSubstitutionSpectrum", [&]() -> int {
         const int cov = parse_int(a.coverage_cutoff, "coverage_cutoff", 0);
         const int max_alt_pm = parse_int(a.max_alt_pm, "max_alt_pm", 0, 1000);
         ampli_spectrum_params prm;
@@ -71,8 +41,7 @@ int run_substitution_spectrum(const SsArgs &a)
         prm.excess_ratio = parse_number(a.excess_ratio, "excess_ratio", "> 1", [](double v) { return v > 1.0; });
         prm.z_cutoff = parse_number(a.z_cutoff, "z_cutoff", ">= 0", [](double v) { return v >= 0.0; });
         prm.asym_delta = parse_number(a.asym_delta, "asym_delta", "in [0, 1]", [](double v) { return v >= 0.0 && v <= 1.0; });
-        if (const char *e = getenv("AMPLISOLVE_WORLD_SIZE"))
-            if (atoi(e) > 1) throw Error{AMPLI_E_INVALID, "AmpliSolveSubstitutionSpectrum runs on one GPU: AMPLISOLVE_WORLD_SIZE > 1 is not supported"};
+        require_single_gpu("AmpliSolveSubstitutionSpectrum");
         const bool with_tumours = a.tumour_dir != "-";
         std::cout << "AmpliSolveSubstitutionSpectrum: panel " << a.panel_design << ", normals " << a.germline_dir << ", tumours "
                   << (with_tumours ? a.tumour_dir : std::string("none")) << ", coverage_cutoff " << cov << ", max_alt_pm " << max_alt_pm << ", min_sites "
@@ -80,17 +49,12 @@ int run_substitution_spectrum(const SsArgs &a)
                   << ", asym_delta " << prm.asym_delta << ", output " << a.output_dir << std::endl;
         DevAsync dev_async;
         dev_async.start();
-        Panel panel;
-        panel_from_bed(a.panel_design, panel);
-        if (!a.refbases_file.empty()) panel_load_refbases_file(panel, a.refbases_file);
-        else panel_load_fasta(panel, a.reference_genome);
-        std::vector<std::pair<std::string, std::string>> sets[2];
-        sets[0] = list_count_files(a.germline_dir, std::string());
-        if (with_tumours) sets[1] = list_count_files(a.tumour_dir, std::string());
-        const int n_normals = (int)sets[0].size(), n_tumours = (int)sets[1].size(), S = n_normals + n_tumours;
-        const int64_t P = panel.P();
-        if (P <= 0) throw Error{AMPLI_E_INVALID, "the panel has no positions"};
-        if (n_normals <= 0) throw Error{AMPLI_E_INVALID, "no count files in " + a.germline_dir};
+        CohortInputs in;
+        load_cohort(in, a.panel_design, &a.reference_genome, a.refbases_file, a.germline_dir, a.tumour_dir, true);
+        const Panel &panel = in.panel;
+        const std::vector<std::string> &names = in.names;
+        const int n_normals = in.n_normals, n_tumours = in.n_tumours, S = n_normals + n_tumours;
+        const int64_t P = in.P;
         // the class of every position from the panel's own reference bases: the lookup kmer_down / kmer_up use, upper-cased
         const int C = AMPLI_SPECTRUM_CLASSES;
         std::vector<uint8_t> cls((size_t)P);
@@ -111,36 +75,22 @@ int run_substitution_spectrum(const SsArgs &a)
         int classes_used = 0;
         for (const uint8_t u : used) classes_used += u;
         Dev &dev = dev_async.get();
-        size_t free_b = 0, total_b = 0;
-        dev.check(dev.api->mem_info(dev.ctx, &free_b, &total_b), "ampli_mem_info");
+        const size_t free_b = device_free_bytes(dev);
         // what stays resident: the sums of every (sample, class) and the two byte arrays; beside them one chunk of records
         const size_t cells = (size_t)S * (size_t)C * AMPLI_SPEC_SUMS;
         const size_t resident = cells * sizeof(int64_t) + 2 * (size_t)P;
         const size_t reserve = (size_t)1 << 30;
-        if (resident + reserve > free_b)
-            throw Error{AMPLI_E_NOMEM, "the samples do not fit the device: " + std::to_string(resident) + " bytes of class sums for " + std::to_string(S) +
-                                           " samples, " + std::to_string(reserve) + " bytes kept for the streamed records, " + std::to_string(free_b) +
-                                           " bytes free"};
+        require_fits(resident, reserve, free_b,
+                     "the samples do not fit the device: " + std::to_string(resident) + " bytes of class sums for " + std::to_string(S) + " samples, " +
+                         std::to_string(reserve) + " bytes kept for the streamed records, " + std::to_string(free_b) + " bytes free");
         int64_t *d_sums = dev.alloc<int64_t>(cells);
         const uint8_t *d_ref = dev.upload(panel.ref_code.data(), panel.ref_code.size());
         const uint8_t *d_cls = dev.upload(cls.data(), cls.size());
-        std::vector<std::string> names;
         DevSlot slot;
-        int base = 0;
-        for (int set = 0; set < 2; ++set) {
-            if (sets[set].empty()) continue;
-            const std::unique_ptr<ChunkStream> cs = open_stream(panel, sets[set], false);
-            for (Chunk *c; (c = next_chunk(*cs)) != nullptr;) {
-                const ampli_records r = upload_chunk(dev, slot, *c, false);
-                dev.check(dev.api->spectrum_records(dev.ctx, &r, P, d_ref, d_cls, C, cov, max_alt_pm,
-                                                    d_sums + (size_t)(base + c->first) * (size_t)C * AMPLI_SPEC_SUMS),
-                          "ampli_spectrum_records");
-                dev.sync(); // the chunk's host buffers go back to the parsers, its device buffers to the next chunk
-                cs->release(c);
-            }
-            for (const auto &f : sets[set]) names.push_back(f.second);
-            base += (int)sets[set].size();
-        }
+        for_each_chunk(dev, in, slot, [&](const ampli_records &r, Chunk &, const int first) {
+            dev.check(dev.api->spectrum_records(dev.ctx, &r, P, d_ref, d_cls, C, cov, max_alt_pm, d_sums + (size_t)first * (size_t)C * AMPLI_SPEC_SUMS),
+                      "ampli_spectrum_records");
+        });
         std::vector<int64_t> sums(cells);
         dev.download(sums.data(), (const int64_t *)d_sums, sums.size());
         dev.sync();
@@ -198,20 +148,13 @@ int run_substitution_spectrum(const SsArgs &a)
                  "asym_delta=%g\npositions_trinucleotide=%lld\npositions_edge=%lld\npositions_skipped=%lld\nclasses_used=%d\n",
                  n_normals, n_tumours, (long long)P, cov, max_alt_pm, (long long)prm.min_sites, (long long)prm.min_normals, prm.excess_ratio, prm.z_cutoff,
                  prm.asym_delta, census[0], census[1], census[2], classes_used);
-        mkdir_p(a.output_dir);
-        std::ofstream(a.output_dir + "/Spectrum_Reference.txt") << reference;
-        std::ofstream(a.output_dir + "/Spectrum_Samples.txt") << samples;
-        std::ofstream(a.output_dir + "/Spectrum_Contexts.txt") << contexts;
-        std::ofstream(a.output_dir + "/Spectrum_Summary.txt") << b << summary_rows;
+        write_files(a.output_dir, {{"Spectrum_Reference.txt", reference}, {"Spectrum_Samples.txt", samples}, {"Spectrum_Contexts.txt", contexts},
+                                   {"Spectrum_Summary.txt", b + summary_rows}});
         std::cout << S << " samples, " << P << " positions in " << classes_used << " classes: " << by_flag[AMPLI_SPECTRUM_ELEVATED] << " (sample, type) ELEVATED, "
                   << by_flag[AMPLI_SPECTRUM_ASYMMETRIC] << " ASYMMETRIC, " << by_flag[AMPLI_SPECTRUM_LOW_SITES] << " LOW_SITES, "
                   << by_flag[AMPLI_SPECTRUM_NO_REFERENCE] << " NO_REFERENCE" << std::endl;
         return 0;
-    } catch (const Error &e) {
-        return fail_line("AmpliSolveSubstitutionSpectrum", e.msg);
-    } catch (const std::exception &e) {
-        return fail_line("AmpliSolveSubstitutionSpectrum", e.what());
-    }
+    });
 }
 
 } // namespace ampli

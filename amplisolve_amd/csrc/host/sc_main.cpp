@@ -3,20 +3,12 @@
 //   AmpliSolveSampleConcordance panel_design=<bed> germline_dir=<dir> tumour_dir=<dir|-> min_depth=<i> min_sites=<i> same_fraction=<f> output_dir=<dir>
 // Exactly 7 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
-#include "pipeline.hpp"
+#include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -34,8 +26,5 @@ int main(int argc, char **argv)
     a.min_sites = token(argv[5], "min_sites");
     a.same_fraction = token(argv[6], "same_fraction");
     a.output_dir = token(argv[7], "output_dir");
-    const int rc = ampli::run_sample_concordance(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_sample_concordance(a));
 }

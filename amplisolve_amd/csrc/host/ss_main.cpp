@@ -4,20 +4,12 @@
 //                                  coverage_cutoff=<i> max_alt_pm=<i> min_sites=<i> min_normals=<i> excess_ratio=<f> z_cutoff=<f> asym_delta=<f>
 // Exactly 12 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
-#include "pipeline.hpp"
+#include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
@@ -43,8 +35,5 @@ int main(int argc, char **argv)
     a.z_cutoff = token(argv[11], "z_cutoff");
     a.asym_delta = token(argv[12], "asym_delta");
     if (const char *e = getenv("AMPLISOLVE_REFBASES_FILE")) a.refbases_file = e; // pre-computed chrom/pos/base table instead of the FASTA
-    const int rc = ampli::run_substitution_spectrum(a);
-    std::cout.flush();
-    ampli::finish_process(rc ? 1 : 0);
-    return rc ? 1 : 0;
+    return ampli::finish(ampli::run_substitution_spectrum(a));
 }

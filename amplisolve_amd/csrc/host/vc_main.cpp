@@ -2,20 +2,12 @@
 //   AmpliSolveVariantCalling errorFile=<table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<i> p_value=<f>
 // Exactly 5 key=value tokens in this order (VC:216, VC:242-260).  Exit status as for AmpliSolveErrorEstimation.
 #include <clocale>
-#include <cstdio>
 #include <cstdlib>
-#include <iostream>
 
 #include "host.hpp"
+#include "main_args.hpp"
 
-static std::string token(const char *arg, const char *key)
-{
-    char buf[4096];
-    buf[0] = 0;
-    std::string fmt = std::string(key) + "=%4000s";
-    sscanf(arg, fmt.c_str(), buf);
-    return buf;
-}
+using ampli::token;
 
 int main(int argc, char **argv)
 {
