@@ -153,6 +153,9 @@ HIP_SYMBOLS = {
     "ampli_spectrum_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, i32, i32, i32, vp]),
     "ampli_last_spectrum_segments": (C.c_int, [vp]),
     "ampli_exceedance_records": (C.c_int, [vp, C.POINTER(Records), C.POINTER(Records), i64, vp, i32, i32, i64, i64, i32, i32, vp, vp]),
+    "ampli_overdispersion_records": (C.c_int, [vp, C.POINTER(Records), i64, C.POINTER(AccTable), i32, vp, i32]),
+    "ampli_overdispersion_finalize": (C.c_int, [vp, i64, C.POINTER(AccTable), vp, vp, vp, vp]),
+    "ampli_nb_score_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, vp, i32, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -249,6 +252,9 @@ HOST_SYMBOLS = {
     "ampli_host_spectrum_fold": (C.c_int, [vp, i64, vp, vp, vp, vp, vp]),
     "ampli_host_spectrum_score": (C.c_int, [vp, vp, vp, i64, i64, C.POINTER(SpectrumParams), vp, vp, vp, vp, vp, vp, vp, vp, vp]),
     "ampli_host_exceedance_candidate_batch": (C.c_int, [vp, vp, vp, vp, i64, C.POINTER(ExceedanceParams), vp]),
+    "ampli_host_overdispersion_cell_batch": (None, [vp, vp, vp, vp, vp, vp, i64, vp]),
+    "ampli_host_nb_score_batch": (C.c_int, [vp, vp, vp, vp, i64, vp]),
+    "ampli_host_nb_tail": (C.c_double, [C.c_double, C.c_double, C.c_double, C.POINTER(i32)]),
 }
 
 _hip = None

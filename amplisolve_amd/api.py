@@ -58,6 +58,7 @@ EXCEEDANCE_NA = 0xFFFF
 EXCEEDANCE_MAX_NORMALS = 65534
 EXCEEDANCE_STRIP = 8
 EXCEEDANCE_ROWS = 8
+NB_NA = -1.0  # a cell of nb_score that is not evaluated (AMPLI_NB_NA)
 
 
 def _ptr(t):
@@ -624,6 +625,51 @@ class Context:
         self._check(self.lib.ampli_exceedance_records(self.h, ctypes.byref(tumours), ctypes.byref(normals), P, _ptr(ref_code), normal_cutoff, calling_cutoff,
                                                       first_t, first_n, int(bool(skip_same_index)), int(bool(accumulate)), _ptr(elig), _ptr(ge)))
         return elig, ge
+
+    def overdispersion_sums(self, chunks, P: int, acc0: Acc, cov: int = 100, s2=None, accumulate: bool = False):
+        """S2 = sum of d_i^2 over every cell's qualifying records (ampli_overdispersion_records): float64 [2, 4, P].
+        chunks: one Records or the Records of the resident cohort in visit order; acc0: the cohort's C_value = 0 table of P positions.
+        accumulate adds onto an s2 of earlier chunks, which must then be given."""
+        import torch
+
+        if isinstance(chunks, Records):
+            chunks = [chunks]
+        assert not accumulate or s2 is not None, "accumulate adds onto the sums of the earlier chunks"
+        if s2 is None:
+            s2 = torch.empty((2, 4, P), dtype=torch.float64, device=self.device)
+        assert s2.dtype == torch.float64 and s2.is_cuda and s2.is_contiguous() and tuple(s2.shape) == (2, 4, P)
+        for i, rec in enumerate(chunks):
+            self._check(self.lib.ampli_overdispersion_records(self.h, C.byref(rec), P, C.byref(acc0.struct), cov, _ptr(s2),
+                                                              int(bool(accumulate) or i > 0)))
+        return s2
+
+    def overdispersion_fit(self, P: int, acc0: Acc, x2, s2, status, omega=None):
+        """omega float64 [2, 4, P] from dispersion's x2 and status (panel_dispersion) and s2 (overdispersion_sums)
+        (ampli_overdispersion_finalize): 0 in every cell that is not DISPERSION_HIGH."""
+        import torch
+
+        if omega is None:
+            omega = torch.empty((2, 4, P), dtype=torch.float64, device=self.device)
+        for t, dt in ((x2, torch.float64), (s2, torch.float64), (status, torch.uint8), (omega, torch.float64)):
+            assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (2, 4, P)
+        self._check(self.lib.ampli_overdispersion_finalize(self.h, P, C.byref(acc0.struct), _ptr(x2), _ptr(s2), _ptr(status), _ptr(omega)))
+        return omega
+
+    def nb_score(self, tumours: Records, P: int, thr, ref_code, omega=None, calling_cutoff: int = 100, q=None):
+        """The negative-binomial score of every cell of a resident chunk of tumours (ampli_nb_score_records): q float32
+        [n_t, P, 4, 2] per base and strand, NB_NA (-1) in a cell that is not evaluated.  thr: the error table's float32 [2, 4, P];
+        omega: float64 [2, 4, P] of overdispersion_fit, or None for 0 everywhere -- the exact Poisson tail; ref_code: uint8 [P]."""
+        import torch
+
+        n_t = tumours.n_samples
+        if q is None:
+            q = torch.empty((n_t, P, 4, 2), dtype=torch.float32, device=self.device)
+        assert q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == (n_t, P, 4, 2)
+        assert thr.dtype == torch.float32 and thr.is_cuda and thr.is_contiguous() and thr.numel() == 8 * P
+        assert omega is None or (omega.dtype == torch.float64 and omega.is_cuda and omega.is_contiguous() and omega.numel() == 8 * P)
+        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        self._check(self.lib.ampli_nb_score_records(self.h, C.byref(tumours), P, _ptr(thr), _ptr(omega), _ptr(ref_code), calling_cutoff, _ptr(q)))
+        return q
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

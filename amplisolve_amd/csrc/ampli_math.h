@@ -1138,4 +1138,199 @@ AMPLI_FN int ampli_exceedance_candidate(uint64_t x_fw, uint64_t x_bw, uint64_t d
     return evaluated & reads & vaf & normals & top;
 }
 
+// ---------------------------------------------------------------------------
+// Overdispersion-aware calling (the definition is tests/overdispersion_model.py).
+//
+// The fit.  A cell (strand, base, position) of the panel with its n qualifying records (dispersion's set), K = sum k_i, D = sum d_i,
+// S2 = sum d_i^2, Pearson's X2 and dispersion's status.  Under k_i ~ Poisson(lambda_i d_i), E lambda_i = r, Var lambda_i = omega r^2:
+//   E[X2] = (n - 1) + omega r (D - S2 / D),  so  omega = (X2 - (n - 1)) D / (K (D - S2 / D))
+// where the status carries AMPLI_DISPERSION_HIGH and D - S2 / D > 0; every other cell, and a quotient that is not above 0 (a negative
+// z_cutoff), has omega = 0: the reference's Poisson model.  A HIGH status comes from an OK cell, so n >= 2 and K >= 2 are assumed: planes that
+// do not belong together (HIGH with K = 0) give an infinite or NaN omega, which the score answers with AMPLI_NB_NA.  Five roundings and the subtraction: within 16 * 2^-53 * omega * (2 + S2 /
+// (D^2 - S2)) of the exact quotient of the same X2.
+//
+// The score.  p = P[X >= k] for X negative binomial with mean m = double(d) * double(e) and variance m + omega m^2:
+//   pmf(0) = (1 + m omega)^(-1 / omega),  pmf(j + 1) / pmf(j) = (1 + j omega) / (j + 1) * m / (1 + m omega);
+// omega = 0 is the Poisson law itself, and omega below AMPLI_NB_POISSON_BELOW is taken as 0.  This is the mathematical tail: it is NOT
+// the reference's kf_gammaq with its 100-term cut-offs, and at omega = 0 it differs from ampli_poisson_score wherever those cut-offs bite.
+//   * ONE term starts a sum, in the saddle-point form (as ampli_binom_logpmf): with s = 1 / omega, N = j + s, a = 1 + m omega,
+//       ln pmf(j) = -1/2 ln(2 pi j (1 + j omega)) + d(N) - d(j) - d(s) - bd0(j, N m omega / a) - bd0(s, N / a),
+//     d = Stirling's error and both deviances taken from the difference (j - m) / a, which is formed without cancellation: no lgamma
+//     difference at large s, and pmf(0) is never the start of a sum that goes up, so it cannot underflow one.
+//   * k > m, upwards from k: every later ratio is below rb = max(the next ratio, m omega / a) < 1, so what is left after a term t with
+//     next ratio r is below t r / (1 - rb); the sum ends once that is below AMPLI_NB_EPS of the sum (RELATIVE: p is wanted down to
+//     1e-10).  That takes at most AMPLI_NB_TERMS_UP(m, omega) terms.  A first term below e^-80 ends the tail at once: it is below
+//     5e-31 and returned as 0.
+//   * otherwise, and where k terms are fewer than that bound, the complement: downwards from k - 1, to 0 or -- for omega < 1, where the
+//     ratios fall on the way down -- until what is left is below AMPLI_NB_EPS_DOWN.  A complement that comes out below AMPLI_NB_SWITCH
+//     has lost digits to 1 - sum and is summed again upwards where AMPLI_NB_TERMS_UP(m, omega) <= AMPLI_NB_MAX_TERMS.
+//   * no sum is longer than AMPLI_NB_MAX_TERMS terms, a tail never more than twice that (asserted in tests/test_overdispersion_host.py).
+//     A tail that would need more -- k > 2^20 with 40 (1 + m omega) > 2^20, or omega >= 1 with k - 1 <= m beyond 2^20 -- is a NaN and
+//     its score AMPLI_NB_NA.  A complement below AMPLI_NB_SWITCH whose upward sum does not fit (m omega > 26 000 and k in the hundreds
+//     of thousands) keeps its lost digits.
+// |Q - exact| <= 1e-5 for m in [1e-3, 1e4], omega = 0 or in [1e-8, 1e4] and k <= 10 m + 2 (tests/test_overdispersion_host.py); the same
+// arithmetic, and on the samples tested the same bound, between 0 and 1e-8.
+// One ampli_nb_step is a short run of terms, so that a kernel runs the tails of a lane in a single loop (as ampli_tail_step).
+// ---------------------------------------------------------------------------
+#define AMPLI_NB_NA (-1.0f) // also in include/amplisolve_hip.h, token for token and unguarded: a copy that drifts is a macro redefinition
+#define AMPLI_NB_POISSON_BELOW 1e-290
+#define AMPLI_NB_EPS 1e-9
+#define AMPLI_NB_EPS_DOWN 1e-18
+#define AMPLI_NB_SWITCH 1e-4
+#define AMPLI_NB_LOG_FLOOR (-80.0)       // an upward sum whose first term is below e^-80 is 0
+#define AMPLI_NB_RUN 8                   // terms per ampli_nb_step
+#define AMPLI_NB_MAX_TERMS (1 << 20)     // of one sum: the loop's own bound
+#define AMPLI_NB_TERMS_UP(m, w) (8.0 * sqrt((m) + (w) * (m) * (m)) + 40.0 * (1.0 + (m) * (w)) + 64.0)
+
+AMPLI_FN double ampli_overdispersion_cell(uint8_t status, int32_t n, double K, double D, double x2, double s2)
+{
+    if (!(status & AMPLI_DISPERSION_HIGH)) return 0.0;
+    const double den = D - s2 / D;
+    if (!(den > 0.0)) return 0.0;
+    const double w = (x2 - ((double)n - 1.0)) * D / (K * den);
+    return w > 0.0 ? w : 0.0;
+}
+
+// d(x) for a real x > 0
+AMPLI_FN double ampli_stirling_err_real(double x)
+{
+    if (x >= 16.0) {
+        const double r = 1.0 / (x * x);
+        return (1.0 / 12 - (1.0 / 360 - (1.0 / 1260 - 1.0 / 1680 * r) * r) * r) / x;
+    }
+    return lgamma(x + 1.0) - ((x + 0.5) * log(x) - x + 0.918938533204672742);
+}
+
+// x ln(x / mu) + mu - x for x, mu > 0 with diff = x - mu given
+AMPLI_FN double ampli_bd0_diff(double x, double mu, double diff)
+{
+    if (fabs(diff) < 0.1 * mu) {
+        const double t = diff / mu;
+        return mu * ((1.0 + t) * log1p(t) - t);
+    }
+    return x * log(x / mu) - diff;
+}
+
+// ln pmf(j), j >= 0 an integer, m > 0, w >= 0
+AMPLI_FN double ampli_nb_logpmf(double j, double m, double w)
+{
+    if (!(w >= AMPLI_NB_POISSON_BELOW)) {
+        if (j <= 0.0) return -m;
+        return -0.5 * log(6.283185307179586477 * j) - ampli_stirling_err_real(j) - ampli_bd0_diff(j, m, j - m);
+    }
+    const double mw = m * w, a = 1.0 + mw;
+    if (j <= 0.0) return -log1p(mw) / w;
+    const double s = 1.0 / w, N = j + s, delta = (j - m) / a;
+    return -0.5 * log(6.283185307179586477 * j * (1.0 + j * w)) + ampli_stirling_err_real(N) - ampli_stirling_err_real(j) - ampli_stirling_err_real(s) -
+           ampli_bd0_diff(j, N * mw / a, delta) - ampli_bd0_diff(s, N / a, -delta);
+}
+
+typedef struct {
+    double k, m, w;  // the tail's count, mean and omega
+    double qq, lim;  // m / (1 + m omega); m omega / (1 + m omega), the limit of the ratios going up
+    double j, t, sum; // index of the latest term; the term; the terms so far
+    double res;      // the tail, once live == 0 (a NaN: not computable within the bound)
+    int32_t up;      // the sum is the tail (from k upwards) / its complement (from k - 1 downwards)
+    int32_t retry;   // a complement below AMPLI_NB_SWITCH is summed again upwards
+    int32_t terms;   // pmf terms formed in this sum, the first one included
+    int32_t total;   // ... in every sum of this tail
+    int32_t live;
+} ampli_nb_sum;
+
+AMPLI_FN void ampli_nb_start(ampli_nb_sum *s, int up)
+{
+    const double j = up ? s->k : s->k - 1.0;
+    const double lp = ampli_nb_logpmf(j, s->m, s->w);
+    s->up = up; s->j = j; s->terms = 1; s->total += 1; s->live = 1;
+    s->t = s->sum = exp(lp);
+    // upwards what follows the first term is below t / (1 - rb) <= t (1 + m omega) <= 2.7e4 t: a tail below 5e-31 is returned as 0, and
+    // no sum starts among the denormals, where the terms cannot fall any more
+    if (up && !(lp >= AMPLI_NB_LOG_FLOOR)) { s->res = 0.0; s->live = 0; }
+    if (!up && j > s->m && lp < -600.0) { s->res = 0.0; s->live = 0; } // far above the mean: the terms below would all be lost
+}
+
+AMPLI_FN void ampli_nb_init(ampli_nb_sum *s, double k, double m, double w)
+{
+    s->k = k; s->m = m; s->w = w; s->qq = 0; s->lim = 0; s->j = 0; s->t = 0; s->sum = 0; s->res = 0;
+    s->up = 0; s->retry = 0; s->terms = 0; s->total = 0; s->live = 0;
+    if (k <= 0.0) { s->res = 1.0; return; }
+    if (!(m > 0.0)) { s->res = 0.0; return; }
+    if (!(w >= AMPLI_NB_POISSON_BELOW)) s->w = w = 0.0;
+    const double a = 1.0 + m * w, est_up = AMPLI_NB_TERMS_UP(m, w);
+    s->qq = m / a; s->lim = m * w / a;
+    const int up_ok = k > m && est_up <= (double)AMPLI_NB_MAX_TERMS;
+    if (up_ok && est_up < k) { ampli_nb_start(s, 1); return; }
+    if (!up_ok && k > (double)AMPLI_NB_MAX_TERMS && w >= 1.0) { s->res = NAN; return; }
+    s->retry = up_ok;
+    ampli_nb_start(s, 0);
+}
+
+AMPLI_FN void ampli_nb_step(ampli_nb_sum *s)
+{
+    double j = s->j, t = s->t, sum = s->sum;
+    const double w = s->w, qq = s->qq, lim = s->lim;
+    int terms = s->terms, end = 0; // 1: the sum is complete, 2: the bound
+    for (int i = 0; i < AMPLI_NB_RUN; ++i) {
+        double r;
+        if (s->up) {
+            r = (1.0 + j * w) / (j + 1.0) * qq;
+            const double rb = r > lim ? r : lim;
+            if (!(t * r > AMPLI_NB_EPS * sum * (1.0 - rb))) { end = 1; break; }
+        } else {
+            if (j <= 0.0) { end = 1; break; }
+            r = j / ((1.0 + (j - 1.0) * w) * qq);
+            if (w < 1.0 && r < 1.0 && t * r < AMPLI_NB_EPS_DOWN * (1.0 - r)) { end = 1; break; }
+        }
+        if (terms >= AMPLI_NB_MAX_TERMS) { end = 2; break; }
+        t *= r;
+        sum += t;
+        j += s->up ? 1.0 : -1.0;
+        ++terms;
+    }
+    s->total += terms - s->terms;
+    s->j = j; s->t = t; s->sum = sum; s->terms = terms;
+    if (!end) return;
+    s->live = 0;
+    if (end == 2) { s->res = NAN; return; }
+    if (s->up) { s->res = sum < 1.0 ? sum : 1.0; return; }
+    s->res = sum < 1.0 ? 1.0 - sum : 0.0;
+    if (s->retry && s->res < AMPLI_NB_SWITCH) { s->retry = 0; ampli_nb_start(s, 1); }
+}
+
+// Q of a tail: 0 for p >= 1, -10 log10(max(p, 1e-10)) as a float, AMPLI_NB_NA for a NaN
+AMPLI_FN float ampli_nb_q_from_p(double p)
+{
+    if (p != p) return AMPLI_NB_NA;
+    if (p >= 1.0) return 0.0f;
+    return (float)(-10.0 * log10(p > 1e-10 ? p : 1e-10));
+}
+
+// what a score needs before its sum: returns 1 with *s ready for ampli_nb_step while s->live, else 0 with *q the score.  k alternative
+// reads of d on the strand, e the table's threshold (-1: Q = -888; 0: 0.0010008f, VC:3844-3856); a negative, NaN or infinite omega
+// gives AMPLI_NB_NA.
+AMPLI_FN int ampli_nb_score_begin(ampli_nb_sum *s, int32_t k, int32_t d, float e, double w, float *q)
+{
+    s->live = 0; s->total = 0;
+    if (!(w >= 0.0) || w > 1.79769313486231570815e308) { *q = AMPLI_NB_NA; return 0; }
+    if (e == -1.0f) { *q = -888.0f; return 0; }
+    if (e == 0.0f) e = 0.0010008f;
+    if (k == 0) { *q = 0.0f; return 0; }
+    ampli_nb_init(s, (double)k, (double)d * (double)e, w);
+    if (!s->live) { *q = ampli_nb_q_from_p(s->res); return 0; }
+    return 1;
+}
+
+// the whole of one score (host, tests); *terms (optional) = pmf terms formed
+AMPLI_FN float ampli_nb_score(int32_t k, int32_t d, float e, double w, int32_t *terms)
+{
+    ampli_nb_sum s;
+    float q;
+    if (ampli_nb_score_begin(&s, k, d, e, w, &q)) {
+        while (s.live) ampli_nb_step(&s);
+        q = ampli_nb_q_from_p(s.res);
+    }
+    if (terms) *terms = s.total;
+    return q;
+}
+
 #endif

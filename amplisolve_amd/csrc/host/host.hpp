@@ -285,6 +285,15 @@ struct ExArgs {
                 min_alt_reads = "3", min_vaf_pm = "0", min_normals = "10", max_normals = "0", refbases_file;
 };
 int run_normal_exceedance(const ExArgs &a);
+// AmpliSolveOverdispersedCalling (od_main.cpp, run_od.cpp): the dispersion omega of every cell of the panel, every tumour cell
+// scored under the Poisson law and under the negative binomial, and the cells that pass the first at q_min and not the second.  C_value
+// in [0, 1], coverage_cutoff an integer >= 1, calling_cutoff an integer >= 0, z_cutoff a number, q_min in (0, 100]; refbases_file: a
+// chrom / pos / base table instead of the FASTA; exit status 0 / 1
+struct OdArgs {
+    std::string panel_design, reference_genome, germline_dir, tumour_dir, C_value = "0.002", coverage_cutoff = "100", calling_cutoff = "100",
+                z_cutoff = "4", q_min = "13", output_dir, refbases_file;
+};
+int run_overdispersed_calling(const OdArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

@@ -288,6 +288,28 @@ extern "C" void ampli_host_dispersion_cell_batch(const int32_t *n, const double 
     for (int64_t i = 0; i < count; ++i) status[i] = ampli_dispersion_cell(n[i], K[i], D[i], x2[i], rinv[i], z_cutoff, &z[i], &phi[i]);
 }
 
+extern "C" void ampli_host_overdispersion_cell_batch(const uint8_t *status, const int32_t *n, const double *K, const double *D, const double *x2,
+                                                     const double *s2, int64_t count, double *omega)
+{
+    for (int64_t i = 0; i < count; ++i) omega[i] = ampli_overdispersion_cell(status[i], n[i], K[i], D[i], x2[i], s2[i]);
+}
+
+extern "C" int ampli_host_nb_score_batch(const int32_t *k, const int32_t *d, const float *e, const double *omega, int64_t n, float *q)
+{
+    if (!k || !d || !e || !q || n < 1) return AMPLI_E_INVALID;
+    for (int64_t i = 0; i < n; ++i) q[i] = ampli_nb_score(k[i], d[i], e[i], omega ? omega[i] : 0.0, nullptr);
+    return 0;
+}
+
+extern "C" double ampli_host_nb_tail(double k, double m, double omega, int32_t *terms)
+{
+    ampli_nb_sum s;
+    ampli_nb_init(&s, k, m, omega);
+    while (s.live) ampli_nb_step(&s);
+    if (terms) *terms = s.total;
+    return s.res;
+}
+
 extern "C" int ampli_host_genotype_classify_batch(const int32_t *recs, int64_t count, const ampli_genotype_params *prm, uint8_t *bits)
 {
     if (!recs || !prm || !bits || count < 0 || !ampli_genotype_params_ok(prm)) return AMPLI_E_INVALID;

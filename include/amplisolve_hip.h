@@ -128,6 +128,11 @@ extern "C" {
  *        OVERWRITES d_elig, all [n_t][P] counts, and d_ge, all [n_t][P][4][2] cells, AMPLI_EXCEEDANCE_NA included, whatever they held;
  *        with accumulate != 0 it ADDS TO d_elig and to the evaluated cells of d_ge and writes NA to the others.  Nothing else is
  *        written.  d_ref_code is read at [0, P), a record only at a position below P of a row below n_t / n_n.
+ *   (C18) overdispersion-aware calling (tests/test_gpu_overdispersion_contracts.py): d_s2 of ampli_overdispersion_records is FULLY
+ *        OVERWRITTEN (accumulate == 0) or ADDED TO (accumulate != 0) over its [2][4][P] extent; d_omega of ampli_overdispersion_finalize
+ *        is FULLY OVERWRITTEN, all [2][4][P] cells; d_q of ampli_nb_score_records is FULLY OVERWRITTEN, all [n_t][P][4][2] cells,
+ *        AMPLI_NB_NA included, whatever it held.  Nothing else is written -- the other chunks' rows of a larger matrix included.  d_thr
+ *        and d_omega are read at [0, 8 P) at most, d_ref_code at [0, P), a record only at a position below P of a row below n_t.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -839,6 +844,57 @@ int ampli_last_spectrum_segments(const ampli_ctx *ctx);
 int ampli_exceedance_records(ampli_ctx *ctx, const ampli_records *recs_t, const ampli_records *recs_n, int64_t P, const uint8_t *d_ref_code,
                              int32_t normal_cutoff, int32_t calling_cutoff, int64_t first_t, int64_t first_n, int32_t skip_same_index,
                              int32_t accumulate, uint16_t *d_elig, uint16_t *d_ge);
+
+/*
+ * Overdispersion-aware calling (the definition is tests/overdispersion_model.py): the dispersion omega of every cell of the
+ * panel of normals, and the score of a tumour's cell under the negative binomial with the error table's own mean.
+ *
+ * The fit.  A cell is (strand, base, position).  Its qualifying records are dispersion's (above): the ones cnt of the accumulator table
+ * counts, primary and extra occurrences, an RD plane honoured.  With n, K = sum k_i, D = sum d_i of the C = 0 table, X2 and the status
+ * of ampli_dispersion_records / _finalize and S2 = sum d_i^2 over the same records:
+ *   omega = (X2 - (n - 1)) D / (K (D - S2 / D))   where the status carries AMPLI_DISPERSION_HIGH and D - S2 / D > 0,
+ *   omega = 0                                      everywhere else, and where the quotient is not above 0 (a negative z_cutoff).
+ * A pre-test moment estimator: E[X2] = (n - 1) + omega r (D - S2 / D) under k_i ~ Poisson(lambda_i d_i), E lambda_i = r = K / D,
+ * Var lambda_i = omega r^2.  A cell the panel cannot show to be overdispersed keeps the reference's Poisson model.
+ *   ampli_overdispersion_records   one resident chunk (any layout, dup_off required when E > 0, rd / rd_ext as for error_reduce) into
+ *               d_s2 double [2][4][P], overwritten (accumulate == 0) or ADDED to.  Squares and sums are integers (two 64-bit words per
+ *               cell), converted once: exact whenever S2 < 2^53 -- every uint16 cohort -- and then the same for any chunking.  No
+ *               atomics: the same inputs in the same chunks give the same bytes.  d_acc0 (the C = 0 table of P positions, as for
+ *               ampli_dispersion_records) is checked and not read: S2 is formed for every cell, OK or not.
+ *   ampli_overdispersion_finalize  d_x2 and d_status as ampli_dispersion_* left them, d_s2 complete: d_omega double [2][4][P], overwritten.
+ *               A HIGH status comes from an OK cell (n >= 2, K >= 2) and that is assumed: planes that do not belong together (HIGH with
+ *               K = 0) give an infinite or NaN omega, which ampli_nb_score_records answers with AMPLI_NB_NA.
+ *
+ * The score.  Only the PRIMARY record of (row, position) enters, slot r < P; extras and an RD plane have no effect.  For strand st
+ * and base b: k = x[st][b], d = D_t[st] (the sum of the strand's four counts), e = d_thr[st][b][p], omega = d_omega[st][b][p] (d_omega ==
+ * NULL: 0 everywhere).
+ *   Q = AMPLI_NB_NA          for a negative, NaN or infinite omega; else
+ *   Q = -888                 for e == -1 (VC:3844-3849); else
+ *   Q = 0                    for k == 0; else, with e == 0 replaced by 0.0010008f (VC:3852-3856) and m = double(d) * double(e),
+ *   p = P[X >= k], X negative binomial of mean m and variance m + omega m^2 (pmf(0) = (1 + m omega)^(-1 / omega), pmf(j + 1) / pmf(j)
+ *       = (1 + j omega) / (j + 1) * m / (1 + m omega)); at omega = 0, and below 1e-290, the exact Poisson tail;
+ *   Q = 0 for p >= 1, else (float)(-10 log10(max(p, 1e-10))).
+ * p is the mathematical tail, NOT the reference's kf_gammaq with its 100-term cut-offs: at omega = 0 the score differs from
+ * ampli_poisson_call's wherever those cut-offs bite.  |Q - exact| <= 1e-5 for m in [1e-3, 1e4], omega = 0 or in [1e-8, 1e4] and
+ * k <= 10 m + 2; between 0 and 1e-8 the arithmetic is the same and so was the error where it was tested.  A sum has at most 2^20
+ * terms: a tail that needs more (k beyond 2^20 with m omega beyond 26 000, csrc/ampli_math.h) gives AMPLI_NB_NA.
+ *   d_q float [n_t][P][4][2], 16-byte aligned, fully overwritten.  A cell is EVALUATED iff t's record is present, D_t[0] >=
+ *   calling_cutoff and D_t[1] >= calling_cutoff, d_ref_code[p] is 0..3 and b is not d_ref_code[p]; every other cell holds AMPLI_NB_NA
+ *   (-1.0f) on both strands.
+ * Refusals, every output untouched.  AMPLI_E_INVALID: a null or misaligned pointer (d_omega of ampli_nb_score_records may be NULL),
+ * P <= 0, coverage_cutoff < 1, calling_cutoff < 0, a table that is not bound to P positions, broken records (n < 1, an unknown layout,
+ * a row stride below P + E, misaligned records, E > 0 without dup_off for the fit).  AMPLI_E_RANGE: P >= 2^31.
+ * The form: the S2 kernel has dispersion_stream_kernel's shape (a 64-position tile, four waves over the rows, LDS hand-over in wave
+ * order); the score kernel gives a wave one tumour row of a tile, a lane a position, and walks the lane's six cells in one loop.
+ * Asynchronous on the context's stream.
+ */
+#define AMPLI_NB_NA (-1.0f) /* also in csrc/ampli_math.h, token for token and unguarded: a copy that drifts is a macro redefinition */
+int ampli_overdispersion_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_acc_table *d_acc0, int32_t coverage_cutoff,
+                                 double *d_s2, int32_t accumulate);
+int ampli_overdispersion_finalize(ampli_ctx *ctx, int64_t P, const ampli_acc_table *d_acc0, const double *d_x2, const double *d_s2,
+                                  const uint8_t *d_status, double *d_omega);
+int ampli_nb_score_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, const float *d_thr, const double *d_omega,
+                           const uint8_t *d_ref_code, int32_t calling_cutoff, float *d_q);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

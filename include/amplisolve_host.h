@@ -257,6 +257,23 @@ typedef struct ampli_exceedance_params {
 int ampli_host_exceedance_candidate_batch(const uint64_t *x, const uint64_t *depth, const uint16_t *elig, const uint16_t *ge, int64_t count,
                                           const ampli_exceedance_params *prm, uint8_t *candidate);
 
+/* Overdispersion-aware calling (the definition is tests/overdispersion_model.py): csrc/ampli_math.h's functions, in double,
+ * unfused -- what overdispersion_finalize_kernel and nb_score_kernel run.
+ * _overdispersion_cell_batch: omega of `count` cells from dispersion's status and X2, the cell's n, K, D and S2 = sum d_i^2:
+ *   (X2 - (n - 1)) D / (K (D - S2 / D)) where the status carries AMPLI_DISPERSION_HIGH, D - S2 / D > 0 and the quotient is above 0,
+ *   else 0.
+ * _nb_score_batch: Q of n (k, d, e, omega) quadruples, omega == NULL meaning 0 everywhere: AMPLI_NB_NA (-1) for a negative, NaN or
+ *   infinite omega, else -888 for e == -1, else 0 for k == 0, else with m = double(d) * double(e == 0 ? 0.0010008f : e) and p =
+ *   P[X >= k] under the negative binomial of mean m and variance m + omega m^2 (the Poisson law at omega = 0): 0 for p >= 1, else
+ *   (float)(-10 log10(max(p, 1e-10))).  The mathematical tail, not the reference's kf_gammaq; AMPLI_NB_NA too where the tail needs
+ *   more than 2^20 terms (csrc/ampli_math.h says when).  Returns 0, or AMPLI_E_INVALID (-1) with nothing written for a null k, d, e
+ *   or q or n < 1.
+ * _nb_tail: p itself (a NaN beyond the term bound); *terms (optional) = pmf terms formed. */
+void ampli_host_overdispersion_cell_batch(const uint8_t *status, const int32_t *n, const double *K, const double *D, const double *x2, const double *s2,
+                                          int64_t count, double *omega);
+int ampli_host_nb_score_batch(const int32_t *k, const int32_t *d, const float *e, const double *omega, int64_t n, float *q);
+double ampli_host_nb_tail(double k, double m, double omega, int32_t *terms);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
