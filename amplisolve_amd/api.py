@@ -59,6 +59,7 @@ EXCEEDANCE_MAX_NORMALS = 65534
 EXCEEDANCE_STRIP = 8
 EXCEEDANCE_ROWS = 8
 NB_NA = -1.0  # a cell of nb_score that is not evaluated (AMPLI_NB_NA)
+PAIR_NA = -999.0  # a cell of pair_score that is not evaluated (AMPLI_PAIR_NA)
 
 
 def _ptr(t):
@@ -670,6 +671,23 @@ class Context:
         assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
         self._check(self.lib.ampli_nb_score_records(self.h, C.byref(tumours), P, _ptr(thr), _ptr(omega), _ptr(ref_code), calling_cutoff, _ptr(q)))
         return q
+
+    def pair_score(self, recs_a: Records, recs_b: Records, P: int, pairs, ref_code, depth_cutoff: int = 100, s=None):
+        """The exact conditional test of two count files at every cell (ampli_pair_score_records): s float32
+        [n_pairs, P, 4, 2] per base and strand, positive where a's allele fraction is the higher, PAIR_NA (-999) in a cell that is not
+        evaluated.  pairs: int32 [n_pairs, 2] on the device, a row of recs_a and a row of recs_b (which may be the same chunk); a row
+        index outside its chunk makes the pair all NA.  ref_code: uint8 [P]."""
+        import torch
+
+        assert pairs.dtype == torch.int32 and pairs.is_cuda and pairs.is_contiguous() and pairs.dim() == 2 and pairs.shape[1] == 2
+        n_pairs = int(pairs.shape[0])
+        if s is None:
+            s = torch.empty((n_pairs, P, 4, 2), dtype=torch.float32, device=self.device)
+        assert s.dtype == torch.float32 and s.is_cuda and s.is_contiguous() and tuple(s.shape) == (n_pairs, P, 4, 2)
+        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        self._check(self.lib.ampli_pair_score_records(self.h, C.byref(recs_a), C.byref(recs_b), P, _ptr(pairs), n_pairs, _ptr(ref_code),
+                                                      depth_cutoff, _ptr(s)))
+        return s
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

@@ -1333,4 +1333,115 @@ AMPLI_FN float ampli_nb_score(int32_t k, int32_t d, float e, double w, int32_t *
     return q;
 }
 
+// ---------------------------------------------------------------------------
+// Paired comparison (the definition is tests/paired_model.py): the exact conditional test of two count files at one cell.
+//
+// File a shows k_a alternative reads among d_a on a strand, file b k_b among d_b.  N = d_a + d_b, K = k_a + k_b, n = d_a, and X is
+// hypergeometric: the number of alternative reads among a's n when K alternative reads are dealt among N.  The side is decided in
+// integers by c = k_a N - K n = k_a d_b - k_b d_a -- two products below 2^64 for any int32 record, compared as unsigned 64-bit words:
+//   K == 0 or c == 0:  S = +0;   c > 0:  p = P[X >= k_a], S = +Q(p);   c < 0:  p = P[X <= k_a], S = -Q(p),
+//   Q(p) = (float)(-10 log10(max(p, 1e-10))), +0 for p >= 1; -0 is never stored.
+// Only the tail on the observation's own side of the mean is ever summed: the short sum, never a complement (no digits lost to 1 - sum).
+//   * ONE term starts the sum, from three binomial terms in the saddle-point form (ampli_binom_logpmf) with v = n / N:
+//       ln pmf(x) = ln b(K, x, v) + ln b(N - K, n - x, v) - ln b(N, n, v)
+//     -- no lgamma difference, and the deviances are all non-negative and add (the third is 0: n is Bin(N, v)'s own mean).
+//   * the later terms come from the ratio, upwards (K - x)(n - x) / ((x + 1)(N - K - n + x + 1)), downwards its mirror
+//     x (N - K - n + x) / ((K - x + 1)(n - x + 1)).  Both are A B / (C D) with A and B falling and C and D rising by one per term, which
+//     is how the sum keeps them.  c != 0 puts k_a strictly beyond the mean on its side, hence at or beyond the mode: the ratio is below 1
+//     from the first step and falls from step to step; it is 0 at the end of the support, which ends the sum.
+//   * what is left after a term t with next ratio r is below t r / (1 - r): the sum ends once that is below AMPLI_HYPER_EPS of the sum
+//     (RELATIVE: p is wanted down to 1e-10, as for ampli_nb_step).  A first term with t / (1 - r) < 1e-10 decides the score without a
+//     sum: +-100.
+//   * terms.  The relative cut-off is reached within about 6.1 standard deviations of the mean when the sum starts there (what is left
+//     is 1e-9 of a sum of about 1/2) and sooner for a start farther out; sums never cross the mean.  With the hypergeometric variance
+//     var = n (K / N) (1 - K / N) (N - n) / (N - 1) a tail costs at most AMPLI_HYPER_TERMS(var) terms (asserted in
+//     tests/test_paired_host.py over the grid) -- below 2^18 for every int32 record.  The loop's own bound is AMPLI_HYPER_MAX_TERMS;
+//     a tail that would need more is a NaN and its score AMPLI_PAIR_NA, not a wrong number.
+// One ampli_hyper_step is AMPLI_TAIL_RUN terms, so that a kernel runs all of a lane's cells in a single loop (as ampli_nb_step).
+// ---------------------------------------------------------------------------
+#define AMPLI_PAIR_NA (-999.0f) // also in include/amplisolve_hip.h, token for token and unguarded: a copy that drifts is a macro redefinition
+#define AMPLI_HYPER_EPS 1e-9
+#define AMPLI_HYPER_MAX_TERMS (1 << 20)  // of one sum: the loop's own bound
+#define AMPLI_HYPER_TERMS(var) (8.0 * sqrt(var) + 64.0)
+
+typedef struct {
+    double A, B, C, D; // the next ratio is A B / (C D)
+    double t, sum;     // the latest term; the terms so far
+    double res;        // the tail, once live == 0 (a NaN: not computable within the bound)
+    int32_t terms;     // pmf terms formed, the first one included
+    int32_t live;
+} ampli_hyper_sum;
+
+// the tail of X from k upwards (up != 0) or from k downwards, for 0 < n < N, 0 <= K <= N and k in the support of X
+AMPLI_FN void ampli_hyper_init(ampli_hyper_sum *s, int64_t N, int64_t K, int64_t n, int64_t k, int up)
+{
+    const double dN = (double)N, dK = (double)K, dn = (double)n, x = (double)k, v = dn / dN;
+    const double rest = (double)(N - K - n + k); // b's other reads, formed in integers
+    double dev;
+    const double lp = ampli_binom_logpmf(dK, x, v, &dev) + ampli_binom_logpmf(dN - dK, dn - x, v, &dev) - ampli_binom_logpmf(dN, dn, v, &dev);
+    if (up) { s->A = dK - x; s->B = dn - x; s->C = x + 1.0; s->D = rest + 1.0; }
+    else { s->A = x; s->B = rest; s->C = dK - x + 1.0; s->D = dn - x + 1.0; }
+    s->t = s->sum = exp(lp);
+    s->res = 0.0; s->terms = 1; s->live = 1;
+    const double r = (s->A * s->B) / (s->C * s->D);
+    if (!(r < 1.0)) { s->res = 1.0; s->live = 0; return; }          // not beyond the mode: no caller with c != 0 comes here
+    if (s->t < 1e-10 * (1.0 - r)) { s->res = 0.0; s->live = 0; }     // the whole tail is below 1e-10: decided without a sum
+}
+
+AMPLI_FN void ampli_hyper_step(ampli_hyper_sum *s)
+{
+    double A = s->A, B = s->B, Cc = s->C, D = s->D, t = s->t, sum = s->sum;
+    int terms = s->terms, end = 0; // 1: the sum is complete, 2: the bound
+    for (int i = 0; i < AMPLI_TAIL_RUN; ++i) {
+        const double r = (A * B) / (Cc * D); // 0 at the end of the support
+        if (!(t * r >= AMPLI_HYPER_EPS * sum * (1.0 - r))) { end = 1; break; }
+        if (terms >= AMPLI_HYPER_MAX_TERMS) { end = 2; break; }
+        t *= r;
+        sum += t;
+        A -= 1.0; B -= 1.0; Cc += 1.0; D += 1.0;
+        ++terms;
+    }
+    s->A = A; s->B = B; s->C = Cc; s->D = D; s->t = t; s->sum = sum; s->terms = terms;
+    if (!end) return;
+    s->live = 0;
+    s->res = end == 2 ? (double)NAN : (sum < 1.0 ? sum : 1.0);
+}
+
+// the signed score of a tail p on side sign (+1: a's fraction is the higher): +0 for p >= 1, AMPLI_PAIR_NA for a NaN
+AMPLI_FN float ampli_pair_s_from_p(double p, int sign)
+{
+    if (p != p) return AMPLI_PAIR_NA;
+    if (p >= 1.0) return 0.0f;
+    const float q = (float)(-10.0 * log10(p > 1e-10 ? p : 1e-10));
+    if (q == 0.0f) return 0.0f;
+    return sign > 0 ? q : -q;
+}
+
+// what a cell needs before its sum: returns the side (+1 / -1) with *s ready for ampli_hyper_step while s->live, or 0 with *q the
+// score.  Counts and depths of one strand: 0 <= k_a <= d_a, 0 <= k_b <= d_b, below 2^33 (the four int32 counts of a strand).
+AMPLI_FN int ampli_pair_score_begin(ampli_hyper_sum *s, int64_t k_a, int64_t d_a, int64_t k_b, int64_t d_b, float *q)
+{
+    s->live = 0; s->terms = 0;
+    const uint64_t lhs = (uint64_t)k_a * (uint64_t)d_b, rhs = (uint64_t)k_b * (uint64_t)d_a; // c = lhs - rhs
+    if (k_a + k_b == 0 || lhs == rhs) { *q = 0.0f; return 0; }
+    const int sign = lhs > rhs ? 1 : -1;
+    ampli_hyper_init(s, d_a + d_b, k_a + k_b, d_a, k_a, sign > 0);
+    if (!s->live) { *q = ampli_pair_s_from_p(s->res, sign); return 0; }
+    return sign;
+}
+
+// the whole of one cell (host, tests); *terms (optional) = pmf terms formed
+AMPLI_FN float ampli_pair_score(int64_t k_a, int64_t d_a, int64_t k_b, int64_t d_b, int32_t *terms)
+{
+    ampli_hyper_sum s;
+    float q;
+    const int sign = ampli_pair_score_begin(&s, k_a, d_a, k_b, d_b, &q);
+    if (sign) {
+        while (s.live) ampli_hyper_step(&s);
+        q = ampli_pair_s_from_p(s.res, sign);
+    }
+    if (terms) *terms = s.terms;
+    return q;
+}
+
 #endif

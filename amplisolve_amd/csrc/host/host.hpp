@@ -294,6 +294,14 @@ struct OdArgs {
                 z_cutoff = "4", q_min = "13", output_dir, refbases_file;
 };
 int run_overdispersed_calling(const OdArgs &a);
+// AmpliSolvePairedComparison (pc_main.cpp, run_pc.cpp): the exact conditional test of two count files of sample_dir at every
+// cell, for every pair of the list `pairs` (nameA<TAB>nameB per line, the names as the Summary names samples), and the verdict of
+// every cell whose pooled VAF reaches min_vaf in either file.  depth_cutoff an integer >= 0, q_min in (0, 100], min_vaf in [0, 1];
+// refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
+struct PcArgs {
+    std::string panel_design, reference_genome, sample_dir, pairs, depth_cutoff = "100", q_min = "13", min_vaf = "0.005", output_dir, refbases_file;
+};
+int run_paired_comparison(const PcArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

@@ -310,6 +310,28 @@ extern "C" double ampli_host_nb_tail(double k, double m, double omega, int32_t *
     return s.res;
 }
 
+extern "C" int ampli_host_pair_score_batch(const int32_t *k_a, const int32_t *d_a, const int32_t *k_b, const int32_t *d_b, int64_t n, float *s)
+{
+    if (!k_a || !d_a || !k_b || !d_b || !s || n < 1) return AMPLI_E_INVALID;
+    for (int64_t i = 0; i < n; ++i) {
+        if (k_a[i] < 0 || k_b[i] < 0 || k_a[i] > d_a[i] || k_b[i] > d_b[i]) return AMPLI_E_INVALID;
+    }
+    for (int64_t i = 0; i < n; ++i) s[i] = ampli_pair_score(k_a[i], d_a[i], k_b[i], d_b[i], nullptr);
+    return 0;
+}
+
+extern "C" double ampli_host_hyper_tail(int64_t N, int64_t K, int64_t n, int64_t k, int32_t up, int32_t *terms)
+{
+    if (terms) *terms = 0;
+    const int64_t lo = n - (N - K) > 0 ? n - (N - K) : 0, hi = K < n ? K : n;
+    if (!(N >= 2 && n > 0 && n < N && K >= 0 && K <= N && k >= lo && k <= hi)) return (double)NAN;
+    ampli_hyper_sum s;
+    ampli_hyper_init(&s, N, K, n, k, up != 0);
+    while (s.live) ampli_hyper_step(&s);
+    if (terms) *terms = s.terms;
+    return s.res;
+}
+
 extern "C" int ampli_host_genotype_classify_batch(const int32_t *recs, int64_t count, const ampli_genotype_params *prm, uint8_t *bits)
 {
     if (!recs || !prm || !bits || count < 0 || !ampli_genotype_params_ok(prm)) return AMPLI_E_INVALID;

@@ -133,6 +133,9 @@ extern "C" {
  *        is FULLY OVERWRITTEN, all [2][4][P] cells; d_q of ampli_nb_score_records is FULLY OVERWRITTEN, all [n_t][P][4][2] cells,
  *        AMPLI_NB_NA included, whatever it held.  Nothing else is written -- the other chunks' rows of a larger matrix included.  d_thr
  *        and d_omega are read at [0, 8 P) at most, d_ref_code at [0, P), a record only at a position below P of a row below n_t.
+ *   (C19) paired comparison (tests/test_gpu_paired_contracts.py): d_s of ampli_pair_score_records is FULLY OVERWRITTEN, all
+ *        [n_pairs][P][4][2] cells, AMPLI_PAIR_NA included, whatever it held.  Nothing else is written.  d_pairs is read at [0, 2 n_pairs),
+ *        d_ref_code at [0, P), a record only at a position below P of a row that a pair names and that lies in its chunk.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -895,6 +898,39 @@ int ampli_overdispersion_finalize(ampli_ctx *ctx, int64_t P, const ampli_acc_tab
                                   const uint8_t *d_status, double *d_omega);
 int ampli_nb_score_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P, const float *d_thr, const double *d_omega,
                            const uint8_t *d_ref_code, int32_t calling_cutoff, float *d_q);
+
+/*
+ * Paired comparison (the definition is tests/paired_model.py): two count files of one patient -- tumour and matched normal,
+ * baseline and follow-up, two libraries of one sample -- tested against each other at every (pair, position, alternative base), per
+ * read strand, with the exact conditional test of the 2 x 2 table (alternative reads, other reads) x (file a, file b).
+ *
+ * A pair is (row a of recs_a, row b of recs_b).  Only the PRIMARY record of (row, position) enters, slot r < P; extras and an RD plane
+ * have no effect.  For strand st and base y: k_a = x_a[st][y], d_a = the sum of a's four counts on st, k_b and d_b likewise;
+ * N = d_a + d_b, K = k_a + k_b, n = d_a, and X is hypergeometric: the number of alternative reads among a's n when K alternative reads
+ * are dealt among N.  The side is decided in integers by c = k_a N - K n (= k_a d_b - k_b d_a: two products below 2^64):
+ *   S = +0                      for K == 0 or c == 0; else
+ *   S = +Q(P[X >= k_a])         for c > 0 (a's fraction is the higher),
+ *   S = -Q(P[X <= k_a])         for c < 0,      Q(p) = (float)(-10 log10(max(p, 1e-10))), +0 for p >= 1; -0 is never stored.
+ * Only the tail on the observation's own side of the mean is summed -- the short sum, never a complement.  |S - exact| <= 1e-5 for
+ * every strand depth up to 2^31 - 1 (tests/test_paired_host.py); the sign, +0, +-100 beyond the clamp and NA are exact.  A sum has at
+ * most 2^20 terms: a tail that needs more gives AMPLI_PAIR_NA (no int32 record does, csrc/ampli_math.h).
+ *   d_s float [n_pairs][P][4][2], 16-byte aligned, fully overwritten.  A cell is EVALUATED iff both records are present, all four
+ *   strand depths (a and b, forward and backward) are >= depth_cutoff, d_ref_code[p] is 0..3 and y is not d_ref_code[p]; every other
+ *   cell holds AMPLI_PAIR_NA (-999.0f) on both strands.
+ *   d_pairs int32 [n_pairs][2]: row in a, row in b.  recs_a and recs_b may be the same chunk, a row may occur in many pairs, and a pair
+ *   of a row with itself is legal: +0 in every evaluated cell.  Row indices cannot be checked on the host without a copy: an index
+ *   outside its chunk makes that pair all NA, and the kernel checks this before any load.
+ * Conditional on K; the strands are tested independently; nothing is corrected for the number of cells.
+ * Refusals, every output untouched.  AMPLI_E_INVALID: a null or misaligned pointer, P <= 0, n_pairs < 1, depth_cutoff < 0, broken
+ * records (n < 1, an unknown layout, a row stride below P + E, misaligned records), chunks of different layouts.  AMPLI_E_RANGE:
+ * P >= 2^31.
+ * The form: a wave owns one pair of a 64-position tile, a lane a position, and walks the lane's six cells in one loop.  Asynchronous on
+ * the context's stream.
+ */
+#define AMPLI_PAIR_NA (-999.0f) /* also in csrc/ampli_math.h, token for token and unguarded: a copy that drifts is a macro redefinition */
+int ampli_pair_score_records(ampli_ctx *ctx, const ampli_records *recs_a, const ampli_records *recs_b, int64_t P,
+                             const int32_t *d_pairs /* [n_pairs][2]: row in a, row in b */, int32_t n_pairs,
+                             const uint8_t *d_ref_code, int32_t depth_cutoff, float *d_s /* [n_pairs][P][4][2] */);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

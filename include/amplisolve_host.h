@@ -274,6 +274,20 @@ void ampli_host_overdispersion_cell_batch(const uint8_t *status, const int32_t *
 int ampli_host_nb_score_batch(const int32_t *k, const int32_t *d, const float *e, const double *omega, int64_t n, float *q);
 double ampli_host_nb_tail(double k, double m, double omega, int32_t *terms);
 
+/* Paired comparison (the definition is tests/paired_model.py): csrc/ampli_math.h's functions, in double, unfused -- what
+ * paired_score_kernel runs.
+ * _pair_score_batch: the signed score S of n strand cells, file a with k_a alternative reads among d_a, file b with k_b among d_b.
+ *   N = d_a + d_b, K = k_a + k_b, X hypergeometric (the alternative reads among a's d_a when K are dealt among N), c = k_a N - K d_a:
+ *   +0 for K == 0 or c == 0; c > 0: +Q(P[X >= k_a]); c < 0: -Q(P[X <= k_a]); Q(p) = (float)(-10 log10(max(p, 1e-10))), +0 for
+ *   p >= 1; -0 is never written.  AMPLI_PAIR_NA (-999) where the tail needs more than 2^20 terms (no int32 cell does).  Returns 0, or
+ *   AMPLI_E_INVALID (-1) with nothing written for a null pointer, n < 1 or a cell outside 0 <= k <= d.
+ * _hyper_tail: the tail itself, from k upwards (up != 0) or downwards, for 0 < n < N, 0 <= K <= N and k in the support on the far
+ *   side of the mean from the direction's start (the sum runs away from the mean: a k on the near side gives 1); exactly 0 where the
+ *   first term already bounds the tail below 1e-10; a NaN beyond the term bound or for arguments outside these; *terms (optional) = pmf
+ *   terms formed. */
+int ampli_host_pair_score_batch(const int32_t *k_a, const int32_t *d_a, const int32_t *k_b, const int32_t *d_b, int64_t n, float *s);
+double ampli_host_hyper_tail(int64_t N, int64_t K, int64_t n, int64_t k, int32_t up, int32_t *terms);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
