@@ -157,6 +157,8 @@ HIP_SYMBOLS = {
     "ampli_overdispersion_finalize": (C.c_int, [vp, i64, C.POINTER(AccTable), vp, vp, vp, vp]),
     "ampli_nb_score_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, vp, i32, vp]),
     "ampli_pair_score_records": (C.c_int, [vp, C.POINTER(Records), C.POINTER(Records), i64, vp, i32, vp, i32, vp]),
+    "ampli_fdr_workspace_bytes": (C.c_size_t, [i32, i64]),
+    "ampli_fdr_adjust": (C.c_int, [vp, vp, i32, i64, i32, vp, C.c_size_t, vp, vp, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -257,6 +259,7 @@ HOST_SYMBOLS = {
     "ampli_host_nb_score_batch": (C.c_int, [vp, vp, vp, vp, i64, vp]),
     "ampli_host_nb_tail": (C.c_double, [C.c_double, C.c_double, C.c_double, C.POINTER(i32)]),
     "ampli_host_pair_score_batch": (C.c_int, [vp, vp, vp, vp, i64, vp]),
+    "ampli_host_fdr_rows": (C.c_int, [vp, i32, i64, i32, vp, vp, vp]),
     "ampli_host_hyper_tail": (C.c_double, [i64, i64, i64, i64, i32, C.POINTER(i32)]),
 }
 

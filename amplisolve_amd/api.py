@@ -60,6 +60,7 @@ EXCEEDANCE_STRIP = 8
 EXCEEDANCE_ROWS = 8
 NB_NA = -1.0  # a cell of nb_score that is not evaluated (AMPLI_NB_NA)
 PAIR_NA = -999.0  # a cell of pair_score that is not evaluated (AMPLI_PAIR_NA)
+FDR_NA = -999.0  # a cell of fdr_adjust that is not tested (AMPLI_FDR_NA)
 
 
 def _ptr(t):
@@ -688,6 +689,37 @@ class Context:
         self._check(self.lib.ampli_pair_score_records(self.h, C.byref(recs_a), C.byref(recs_b), P, _ptr(pairs), n_pairs, _ptr(ref_code),
                                                       depth_cutoff, _ptr(s)))
         return s
+
+    def fdr_workspace_bytes(self, rows: int, P: int) -> int:
+        """Bytes of the workspace fdr_adjust needs for a plane of rows x P positions (ampli_fdr_workspace_bytes)."""
+        return int(self.lib.ampli_fdr_workspace_bytes(rows, P))
+
+    def fdr_adjust(self, s, two_sided: bool = False, a=None, m=None, rank=False, work=None):
+        """The Benjamini-Hochberg adjusted score of every cell of a score plane, each row on its own (ampli_fdr_adjust).
+        s: float32 [rows, P, 4, 2] of nb_score (two_sided False) or pair_score (two_sided True).  Returns (a, m) or, with rank (True,
+        or an int32 [rows, P, 4] tensor to fill), (a, m, rank): a float32 [rows, P, 4] -- the signed adjusted score, FDR_NA (-999) in a
+        cell that is not tested --, m int32 [rows] the tested cells of each row, rank the cell's rank R among them.  work: a uint8
+        tensor of at least fdr_workspace_bytes(rows, P) bytes; allocated here when not given."""
+        import torch
+
+        assert s.dtype == torch.float32 and s.is_cuda and s.is_contiguous() and s.dim() == 4 and tuple(s.shape[2:]) == (4, 2)
+        rows, P = int(s.shape[0]), int(s.shape[1])
+        if a is None:
+            a = torch.empty((rows, P, 4), dtype=torch.float32, device=self.device)
+        if m is None:
+            m = torch.empty((rows,), dtype=torch.int32, device=self.device)
+        if rank is True:
+            rank = torch.empty((rows, P, 4), dtype=torch.int32, device=self.device)
+        elif rank is False:
+            rank = None
+        if work is None:
+            work = torch.empty((self.fdr_workspace_bytes(rows, P),), dtype=torch.uint8, device=self.device)
+        assert a.dtype == torch.float32 and a.is_cuda and a.is_contiguous() and tuple(a.shape) == (rows, P, 4)
+        assert m.dtype == torch.int32 and m.is_cuda and m.is_contiguous() and tuple(m.shape) == (rows,)
+        assert rank is None or (rank.dtype == torch.int32 and rank.is_cuda and rank.is_contiguous() and tuple(rank.shape) == (rows, P, 4))
+        assert work.dtype == torch.uint8 and work.is_cuda and work.is_contiguous()
+        self._check(self.lib.ampli_fdr_adjust(self.h, _ptr(s), rows, P, int(bool(two_sided)), _ptr(work), work.numel(), _ptr(a), _ptr(m), _ptr(rank)))
+        return (a, m) if rank is None else (a, m, rank)
 
     def loo_call(self, rec: Records, P: int, acc: Acc, ref_code, C_value: float = 0.002, cov: int = 100, call_cov: int = 100,
                  mode: int = POISSON_PREFILTER, capacity: int = 0, dense_thr: bool = False, call_mask=None, calls_buf=None,

@@ -1444,4 +1444,63 @@ AMPLI_FN float ampli_pair_score(int64_t k_a, int64_t d_a, int64_t k_b, int64_t d
     return q;
 }
 
+// ---------------------------------------------------------------------------
+// False-discovery control (the definition is tests/fdr_model.py): the Benjamini-Hochberg adjusted score of every cell of a
+// score plane [rows][P][4][2], each row on its own.  A cell's p-value is the larger of its two strands' -- both strands must show the
+// allele -- so its key is the SMALLER strand score a; in the two-sided mode (the paired plane) both strands must lie on one side and
+// the p-value doubles, because the side was chosen by the data.
+//   one-sided:  TESTED iff 0 <= s_f <= 100 and 0 <= s_b <= 100; a = min(s_f, s_b), sign +.
+//   two-sided:  TESTED iff -100 <= s_f <= 100 and -100 <= s_b <= 100; both > 0: a = min, sign +; both < 0: a = min(|s_f|, |s_b|),
+//               sign -; otherwise a = 0.
+// Everything else -- a NaN, an infinity, any NA sentinel, anything beyond +-100 -- is UNTESTED.  A zero of either sign is a = 0.
+// The key is the BIT PATTERN of a (positive floats order as their bit patterns do: no denormal mode enters), 0 for a = 0 and for an
+// untested cell alike.  With m the tested cells of the row (a = 0 included) and R = #{tested j : a_j >= a} (the largest rank of a tie):
+//   B = a - 10 log10(m / R) - (two_sided ? 10 log10 2 : 0),      A = max(0, max{B_j : 0 < a_j <= a})
+// -- BH's step-up minimum over the larger p-values, in score space: q = 10^(-A / 10).  Stored: sign * (float)A, +0 where a = 0 or
+// A = 0 (-0 never), AMPLI_FDR_NA where untested.  Rounding to float is monotone, so the running maximum may be taken over
+// (float)B: max and rounding commute, and max(0, .) with them.
+// ---------------------------------------------------------------------------
+#define AMPLI_FDR_NA (-999.0f) // also in include/amplisolve_hip.h, token for token and unguarded: a copy that drifts is a macro redefinition
+#define AMPLI_FDR_UNTESTED 0
+#define AMPLI_FDR_ZERO 1
+#define AMPLI_FDR_PLUS 2
+#define AMPLI_FDR_MINUS 3
+
+AMPLI_FN uint32_t ampli_fdr_float_bits(float a)
+{
+    union { float f; uint32_t u; } v;
+    v.f = a;
+    return v.u;
+}
+
+// the key of one cell (0 for a = 0 and for an untested cell); *cls = AMPLI_FDR_UNTESTED / _ZERO / _PLUS / _MINUS
+AMPLI_FN uint32_t ampli_fdr_key(float s_f, float s_b, int two_sided, int *cls)
+{
+    const float lo = two_sided ? -100.0f : 0.0f;
+    if (!(s_f >= lo && s_f <= 100.0f && s_b >= lo && s_b <= 100.0f)) { *cls = AMPLI_FDR_UNTESTED; return 0u; } // a NaN fails every comparison
+    float a = 0.0f;
+    int c = AMPLI_FDR_ZERO;
+    if (s_f > 0.0f && s_b > 0.0f) { a = s_f < s_b ? s_f : s_b; c = AMPLI_FDR_PLUS; }
+    else if (s_f < 0.0f && s_b < 0.0f) { a = s_f > s_b ? -s_f : -s_b; c = AMPLI_FDR_MINUS; } // only the two-sided mode tests a negative score
+    *cls = c;
+    return c == AMPLI_FDR_ZERO ? 0u : ampli_fdr_float_bits(a);
+}
+
+// B of a key a > 0 with rank R among the m tested cells of its row, 1 <= R <= m < 2^31
+AMPLI_FN double ampli_fdr_value(uint32_t key, int32_t m, int32_t R, int two_sided)
+{
+    union { uint32_t u; float f; } v;
+    v.u = key;
+    const double b = (double)v.f - 10.0 * log10((double)m / (double)R);
+    return two_sided ? b - 10.0 * log10(2.0) : b;
+}
+
+// what is stored for a cell of class cls whose running maximum of (float)B is bmax: sign * max(0, bmax), never -0
+AMPLI_FN float ampli_fdr_store(int cls, float bmax)
+{
+    if (cls == AMPLI_FDR_UNTESTED) return AMPLI_FDR_NA;
+    if (cls == AMPLI_FDR_ZERO || !(bmax > 0.0f)) return 0.0f;
+    return cls == AMPLI_FDR_MINUS ? -bmax : bmax;
+}
+
 #endif

@@ -1,4 +1,4 @@
-// amplisolve_amd/csrc/host/command.cpp -- what the project's own eleven commands share (command.hpp)
+// amplisolve_amd/csrc/host/command.cpp -- what the project's own twelve commands share (command.hpp)
 #include "command.hpp"
 
 namespace ampli {

@@ -315,5 +315,15 @@ PairLimit limit_pair_literal(const int32_t rec[8], int rd, int nt, float thr_fw,
 std::string kmer_down(const Panel &p, const std::string &chrom, int pos);       // VC:3307-3458
 std::string kmer_up(const Panel &p, const std::string &chrom, int pos);         // VC:3461-3613
 int homopolymer_test(const std::string &down, const std::string &up, char sub); // VC:3615-3718
+// ---- run_fd.cpp ----
+// AmpliSolveFalseDiscovery (fd_main.cpp, run_fd.cpp): every tumour cell scored with the exact Poisson tail against the panel's
+// own error table, the Benjamini-Hochberg adjusted score of every cell per file, and the cells whose adjusted score reaches
+// -10 log10(fdr).  C_value in [0, 1], coverage_cutoff an integer >= 1, calling_cutoff an integer >= 0, fdr in (0, 1), q_min in (0, 100]
+// (the raw per-strand gate the listing is compared with); refbases_file: a chrom / pos / base table instead of the FASTA; exit status 0 / 1
+struct FdArgs {
+    std::string panel_design, reference_genome, germline_dir, tumour_dir, C_value = "0.002", coverage_cutoff = "100", calling_cutoff = "100", fdr = "0.05",
+                q_min = "13", output_dir, refbases_file;
+};
+int run_false_discovery(const FdArgs &a);
 
 } // namespace ampli

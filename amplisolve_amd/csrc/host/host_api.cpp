@@ -320,6 +320,50 @@ extern "C" int ampli_host_pair_score_batch(const int32_t *k_a, const int32_t *d_
     return 0;
 }
 
+extern "C" int ampli_host_fdr_rows(const float *s, int32_t rows, int64_t P, int32_t two_sided, float *a, int32_t *m, int32_t *rank)
+{
+    if (!s || !a || !m || rows < 1 || P <= 0 || (two_sided != 0 && two_sided != 1)) return AMPLI_E_INVALID;
+    if (P >= ((int64_t)1 << 29)) return AMPLI_E_RANGE;
+    const int64_t n = 4 * P;
+    std::vector<uint32_t> sorted((size_t)n);
+    std::vector<float> amax((size_t)n);
+    for (int32_t r = 0; r < rows; ++r) {
+        const float *sr = s + (size_t)r * (size_t)n * 2;
+        int32_t tested = 0;
+        for (int64_t i = 0; i < n; ++i) {
+            int cls;
+            sorted[(size_t)i] = ampli_fdr_key(sr[2 * i], sr[2 * i + 1], two_sided, &cls);
+            tested += cls != AMPLI_FDR_UNTESTED;
+        }
+        m[r] = tested;
+        std::sort(sorted.begin(), sorted.end());
+        // (float)B at the first slot of every tie group of positive keys (its rank is n - slot), and the running maximum of that
+        float run = -INFINITY;
+        for (int64_t i = 0; i < n; ++i) {
+            const uint32_t k = sorted[(size_t)i];
+            if (k != 0u && (i == 0 || k != sorted[(size_t)i - 1])) {
+                const float b = (float)ampli_fdr_value(k, tested, (int32_t)(n - i), two_sided);
+                if (b > run) run = b;
+            }
+            amax[(size_t)i] = run;
+        }
+        for (int64_t i = 0; i < n; ++i) {
+            int cls;
+            const uint32_t k = ampli_fdr_key(sr[2 * i], sr[2 * i + 1], two_sided, &cls);
+            float bmax = 0.0f;
+            int32_t R = 0;
+            if (k != 0u) {
+                const int64_t slot = std::lower_bound(sorted.begin(), sorted.end(), k) - sorted.begin();
+                bmax = amax[(size_t)slot];
+                R = (int32_t)(n - slot);
+            }
+            a[(size_t)r * (size_t)n + (size_t)i] = ampli_fdr_store(cls, bmax);
+            if (rank) rank[(size_t)r * (size_t)n + (size_t)i] = R;
+        }
+    }
+    return 0;
+}
+
 extern "C" double ampli_host_hyper_tail(int64_t N, int64_t K, int64_t n, int64_t k, int32_t up, int32_t *terms)
 {
     if (terms) *terms = 0;

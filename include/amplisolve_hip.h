@@ -136,6 +136,10 @@ extern "C" {
  *   (C19) paired comparison (tests/test_gpu_paired_contracts.py): d_s of ampli_pair_score_records is FULLY OVERWRITTEN, all
  *        [n_pairs][P][4][2] cells, AMPLI_PAIR_NA included, whatever it held.  Nothing else is written.  d_pairs is read at [0, 2 n_pairs),
  *        d_ref_code at [0, P), a record only at a position below P of a row that a pair names and that lies in its chunk.
+ *   (C20) false-discovery control (tests/test_gpu_fdr_contracts.py): d_a [rows][P][4] and d_m [rows] of ampli_fdr_adjust are FULLY
+ *        OVERWRITTEN, AMPLI_FDR_NA included, whatever they held; d_rank [rows][P][4] is FULLY OVERWRITTEN when it is not NULL.  d_work
+ *        is written only inside its first work_bytes bytes (ampli_fdr_workspace_bytes(rows, P) of them are used).  d_s is read at
+ *        [0, 8 rows P) and never written.  Nothing else is written.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -931,6 +935,47 @@ int ampli_nb_score_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P
 int ampli_pair_score_records(ampli_ctx *ctx, const ampli_records *recs_a, const ampli_records *recs_b, int64_t P,
                              const int32_t *d_pairs /* [n_pairs][2]: row in a, row in b */, int32_t n_pairs,
                              const uint8_t *d_ref_code, int32_t depth_cutoff, float *d_s /* [n_pairs][P][4][2] */);
+
+/*
+ * False-discovery control (the definition is tests/fdr_model.py): the Benjamini-Hochberg adjusted score of every cell of a
+ * score plane d_s float [rows][P][4][2] (row, position, base, strand) -- the plane ampli_nb_score_records and ampli_pair_score_records
+ * write.  A row is one file or one pair, and each row is adjusted on its own.
+ *
+ * Cell key, with s_f and s_b the two strand scores of cell (r, p, y):
+ *   two_sided == 0 (the negative-binomial plane; AMPLI_NB_NA and -888 are negative): the cell is TESTED iff 0 <= s_f <= 100 and
+ *     0 <= s_b <= 100; magnitude a = min(s_f, s_b), sign +.
+ *   two_sided == 1 (the paired plane): TESTED iff -100 <= s_f <= 100 and -100 <= s_b <= 100; both > 0: a = min, sign +; both < 0:
+ *     a = min(|s_f|, |s_b|), sign -; otherwise a = 0.
+ *   Everything else is UNTESTED: a NaN, an infinity, any sentinel, anything beyond +-100.  A zero of either sign is a = 0 (-0.0f is not
+ *   the largest key).  Inputs of magnitude below 2^-126 (denormals) are outside the contract: no scorer writes one.
+ * p_cell = max(p_fw, p_bw) -- both strands must show the allele, as every gate here asks -- is a valid, conservative p-value; the
+ * two-sided form doubles it, because the side was chosen by the data.
+ *
+ * Adjustment, in double.  m_r = the tested cells of row r, those with a = 0 included.  For a tested cell with a > 0:
+ *   R = #{tested j of the row : a_j >= a}        (the largest rank among ties: equal keys get equal values)
+ *   B = a - 10 log10(m_r / R) - (two_sided ? 10 log10 2 : 0)
+ *   A = max(0, max{B_j : 0 < a_j <= a})           (BH's step-up minimum over the larger p, in score space: q = 10^(-A / 10))
+ *   d_a float [rows][P][4], 16-byte aligned: sign * (float)A for a tested cell with a > 0; +0 where a = 0 or A = 0 (-0 is never
+ *     stored); AMPLI_FDR_NA (-999.0f) where untested.
+ *   d_m int32 [rows]: m_r.  A row with m_r = 0 is all NA.
+ *   d_rank int32 [rows][P][4], 16-byte aligned, or NULL: R, and 0 where untested or a = 0.
+ *   d_work: ampli_fdr_workspace_bytes(rows, P) bytes, 16-byte aligned (two key arrays of 4 P words, the digit histograms and the scans'
+ *     block totals, per row); 0 from the query means rows < 1, P <= 0 or 4 P >= 2^31.
+ * |A - model| <= 1e-5 (one float ulp at 100 is 7.6e-6; the double arithmetic under it adds less than 1e-12); m, R, the tested mask, the
+ * sign, +0 and NA are exact.  The same plane gives the same bytes, alone or as one row of a batch.
+ * Refusals, every output untouched.  AMPLI_E_INVALID: a null or misaligned pointer (d_rank may be NULL), rows < 1, P <= 0, two_sided
+ * not 0 or 1, a workspace smaller than the query's.  AMPLI_E_RANGE: 4 P >= 2^31.
+ * The form (csrc/ampli_fdr.hip): the keys' bit patterns and m; an LSD radix sort of each row's 4 P keys, 8 bits a pass, over tiles of
+ * AMPLI_FDR_TILE_KEYS keys with a stable scatter; B at the first slot of each tie group and its running maximum by a two-level scan
+ * (blocks of AMPLI_FDR_SCAN_BLOCK, whose totals one workgroup per row walks AMPLI_FDR_SCAN_BLOCK at a time); a binary search per cell.
+ * No workgroup waits for another.  Asynchronous on the context's stream: m_r is read from device memory, nothing synchronises.
+ */
+#define AMPLI_FDR_NA (-999.0f) /* also in csrc/ampli_math.h, token for token and unguarded: a copy that drifts is a macro redefinition */
+#define AMPLI_FDR_TILE_KEYS 4096 /* keys of one sort tile: 1024 positions */
+#define AMPLI_FDR_SCAN_BLOCK 512 /* elements of one scan block; one second-level step covers 512 * 512 keys = 65536 positions */
+size_t ampli_fdr_workspace_bytes(int32_t rows, int64_t P);
+int ampli_fdr_adjust(ampli_ctx *ctx, const float *d_s /* [rows][P][4][2] */, int32_t rows, int64_t P, int32_t two_sided, void *d_work,
+                     size_t work_bytes, float *d_a /* [rows][P][4] */, int32_t *d_m /* [rows] */, int32_t *d_rank /* [rows][P][4] or NULL */);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

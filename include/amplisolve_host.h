@@ -288,6 +288,13 @@ double ampli_host_nb_tail(double k, double m, double omega, int32_t *terms);
 int ampli_host_pair_score_batch(const int32_t *k_a, const int32_t *d_a, const int32_t *k_b, const int32_t *d_b, int64_t n, float *s);
 double ampli_host_hyper_tail(int64_t N, int64_t K, int64_t n, int64_t k, int32_t up, int32_t *terms);
 
+/* False-discovery control (the definition is tests/fdr_model.py): what ampli_fdr_adjust computes, from the same text
+ * (csrc/ampli_math.h: ampli_fdr_key, ampli_fdr_value, ampli_fdr_store) with std::sort in place of the device sort.
+ * _fdr_rows: s float [rows][P][4][2]; a float [rows][P][4] (sign * A, +0, AMPLI_FDR_NA = -999 where untested), m int32 [rows] (the tested
+ *   cells of each row), rank int32 [rows][P][4] or NULL (R, 0 where untested or a = 0).  Each row on its own.  Returns 0,
+ *   AMPLI_E_INVALID (-1) for a null pointer, rows < 1, P <= 0 or two_sided not 0 or 1, AMPLI_E_RANGE (-6) for 4 P >= 2^31. */
+int ampli_host_fdr_rows(const float *s, int32_t rows, int64_t P, int32_t two_sided, float *a, int32_t *m, int32_t *rank);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
