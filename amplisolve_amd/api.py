@@ -349,7 +349,8 @@ class Context:
                                                                int(bool(accumulate)) | (2 if summary else 0), n_slices, _ptr(sums), _ptr(gm)))
 
     def poisson_call_records(self, rec: Records, P: int, thr, ref_code, cov: int = 100, mode: int = POISSON_PREFILTER,
-                             call_mask=None, capacity: int = 0, calls_buf=None, n_calls=None):
+                             call_mask=None, capacity: int = 0, calls_buf=None, n_calls=None, q=None, af=None):
+        """q / af: the caller's buffers for the dense scores (float64 [T, R, 4, 2], all-scores mode only) and VAFs (float32 [T, R, 4, 3])"""
         import torch
 
         T, R = rec.n_samples, P + rec.E
@@ -363,8 +364,8 @@ class Context:
         if (capacity > 0 or n_calls is not None) and n_calls is None:
             n_calls = torch.zeros((CALL_COUNTER_WORDS,), dtype=torch.int64, device=d)
         self._check(self.lib.ampli_poisson_call_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), cov, mode, _ptr(call_mask),
-                                                        _ptr(calls_buf), capacity, _ptr(n_calls), None, None))
-        return dict(call_mask=call_mask, q=None, af=None, calls_buf=calls_buf, n_calls=n_calls, capacity=capacity)
+                                                        _ptr(calls_buf), capacity, _ptr(n_calls), _ptr(q), _ptr(af)))
+        return dict(call_mask=call_mask, q=q, af=af, calls_buf=calls_buf, n_calls=n_calls, capacity=capacity)
 
     def detection_limits(self, rec: Records, P: int, thr, ref_code, cov: int = 100, levels=(), counts=None):
         """Detection limits of the calling gate for one resident chunk (ampli_limit_records): per record and base the smallest
@@ -947,6 +948,16 @@ class Context:
         q = torch.empty(k.numel(), dtype=torch.float64, device=self.device)
         self._check(self.lib.ampli_score_dense_batch(self.h, _ptr(k), _ptr(rd), _ptr(err), k.numel(), _ptr(q)))
         return q
+
+    def drain_score_batch(self, k, rd, err):
+        """(Q, p) by the scorer of the prefilter mode's drain (ampli_drain_p) for counts k above the mean rd * err > 0"""
+        import torch
+
+        n = k.numel()
+        q = torch.empty(n, dtype=torch.float64, device=self.device)
+        p = torch.empty(n, dtype=torch.float64, device=self.device)
+        self._check(self.lib.ampli_drain_score_batch(self.h, _ptr(k), _ptr(rd), _ptr(err), n, _ptr(q), _ptr(p)))
+        return q, p
 
     def roundtrip_batch(self, x):
         import torch

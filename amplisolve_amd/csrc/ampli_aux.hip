@@ -14,6 +14,18 @@ __global__ void score_dense_batch_kernel(const int *k, const int *rd, const floa
     if (i < n) q[i] = ampli_poisson_score_dense(k[i], rd[i], err[i], lgtab, AMPLI_LGTAB);
 }
 
+// the drain's scorer on a list, one lane per item: what drain_body evaluates for one strand of a queued item with 0 < m < k
+// (ampli_host_drain_score_batch's semantics: no test of that condition here either)
+__global__ void drain_score_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, double *pv, const double *lgtab)
+{
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double m = (double)rd[i] * err[i]; // VC:3864: double * float
+    const double p = ampli_drain_p(k[i], m, lgtab, AMPLI_LGTAB);
+    if (pv) pv[i] = p;
+    if (q) q[i] = ampli_q_from_p(p);
+}
+
 __global__ void score_batch_kernel(const int *k, const int *rd, const float *err, const long long n, double *q, double *pv)
 {
     const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
@@ -65,6 +77,17 @@ extern "C" int ampli_score_dense_batch(ampli_ctx *ctx, const int32_t *d_k, const
     hipLaunchKernelGGL(score_dense_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, main_stream(ctx), d_k, d_rd, d_err,
                        (long long)n, d_q, (const double *)ctx->d_lgtab);
     return check_launch(ctx, "score_dense_batch_kernel");
+}
+
+extern "C" int ampli_drain_score_batch(ampli_ctx *ctx, const int32_t *d_k, const int32_t *d_rd, const float *d_err, int64_t n, double *d_q,
+                                       double *d_p)
+{
+    if (!ctx || !d_k || !d_rd || !d_err || n <= 0) return AMPLI_E_INVALID;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    { int rcl = ensure_lgtab(ctx); if (rcl) return rcl; }
+    hipLaunchKernelGGL(drain_score_batch_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, main_stream(ctx), d_k, d_rd, d_err,
+                       (long long)n, d_q, d_p, (const double *)ctx->d_lgtab);
+    return check_launch(ctx, "drain_score_batch_kernel");
 }
 
 extern "C" int ampli_roundtrip_batch(ampli_ctx *ctx, const float *d_in, int64_t n, float *d_out)

@@ -6,6 +6,7 @@
 #include <string>
 
 #include "../../include/amplisolve_hip.h"
+#include "ampli_math.h" // AMPLI_LGTAB
 
 // ---------------------------------------------------------------------------
 // context
@@ -71,8 +72,8 @@ struct ampli_ctx {
 };
 // 65537 entries (512 KB, L2-resident): every count a uint16 record can hold, + 1 for the drain's kf_lgamma(k + 1).  (4096 until round 6:
 // a wave of the drain in which ONE lane carries a count beyond the table -- a heterozygous site at 10 000 x -- runs the Lanczos form, 8
-// divisions and 2 logarithms, for all of its lanes.)
-constexpr int AMPLI_LGTAB = 65537;
+// divisions and 2 logarithms, for all of its lanes.)  AMPLI_LGTAB itself is defined in ampli_math.h, where the host's probes find it too.
+static_assert(AMPLI_LGTAB == 65537, "the lgamma table holds every uint16 count + 1");
 
 #define HIP_TRY(ctx, expr)                                                                        \
     do {                                                                                          \

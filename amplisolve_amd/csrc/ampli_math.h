@@ -226,10 +226,22 @@ AMPLI_FN double ampli_poisson_score(int32_t k, int32_t rd, float err)
 //   * log(sum) / log(f) are not taken: the prefactor exp(s log z - z - lgamma) is multiplied / divided instead.
 // Differences from the literal scorer: rounding (~1e-13 relative on p, measured in tests/test_math_host.py); the contract
 // is 1e-6, and a Q within 1e-6 of a gate is re-decided by the host in the reference's own arithmetic either way.
+// That the table gives the function's bits is asserted on the host: tests/csrc/scorer_domain_main.cpp (under the address and
+// undefined-behaviour sanitizers) and tests/test_math_host.py run the table and the no-table form of every scorer below over the
+// int32 domain and compare bits.  The index arithmetic is free of overflow: the index is compared as an unsigned number, so a
+// negative one takes the function, and k + 1 is never formed as an int -- ampli_lgamma_int_next takes k and adds inside
+// ((double)k + 1. is exact for every int32 k; at INT32_MAX the int sum wrapped to INT32_MIN and passed the signed guard it had).
 // ---------------------------------------------------------------------------
+#define AMPLI_LGTAB 65537 // entries of the table (why this many: ampli_internal.h)
 AMPLI_FN double ampli_lgamma_int(int n, const double *lgtab, int ntab)
 {
-    return (lgtab && n < ntab) ? lgtab[n] : ampli_kf_lgamma((double)n);
+    return (lgtab && (unsigned)n < (unsigned)ntab) ? lgtab[n] : ampli_kf_lgamma((double)n);
+}
+
+// kf_lgamma(k + 1) for an int32 k
+AMPLI_FN double ampli_lgamma_int_next(int k, const double *lgtab, int ntab)
+{
+    return (lgtab && ntab > 0 && (unsigned)k < (unsigned)(ntab - 1)) ? lgtab[k + 1] : ampli_kf_lgamma((double)k + 1.);
 }
 
 // P(s, z) by the series, z <= s (the branch kf_gammaq takes for z <= 1 or z < s), prefactor given
@@ -300,7 +312,7 @@ AMPLI_FN double ampli_poisson_p_dense(int32_t k, int32_t rd, float err, const do
     const double s = (double)k, z = (double)rd * err; // VC:3864: double * float
     if (z <= 1. || z < s) { // VC:3728
         if (!(z > 0)) return 1 - ampli_kf_gammaq(s, z); // z <= 0 or NaN: whatever the literal arithmetic gives
-        const double P = ampli_gammap_series_int(s, z, exp(s * log(z) - z - ampli_lgamma_int(k + 1, lgtab, ntab)));
+        const double P = ampli_gammap_series_int(s, z, exp(s * log(z) - z - ampli_lgamma_int_next(k, lgtab, ntab)));
         return 1 - (1. - P); // VC:3865 on top of VC:3728
     }
     if (k <= AMPLI_HORNER_K && z < 838860.8) return 1 - ampli_gammaq_horner_int(k, z, ampli_lgamma_int(k, lgtab, ntab));
@@ -314,7 +326,7 @@ AMPLI_FN double ampli_poisson_p_dense(int32_t k, int32_t rd, float err, const do
 AMPLI_FN double ampli_drain_p(int32_t k, double m, const double *lgtab, int ntab)
 {
     const double s = (double)k;
-    const double P = ampli_gammap_series_int(s, m, exp(s * log(m) - m - ampli_lgamma_int(k + 1, lgtab, ntab)));
+    const double P = ampli_gammap_series_int(s, m, exp(s * log(m) - m - ampli_lgamma_int_next(k, lgtab, ntab)));
     return 1 - (1. - P); // VC:3865 on top of VC:3728
 }
 

@@ -52,6 +52,31 @@ extern "C" void ampli_host_dense_score_batch(const int32_t *k, const int32_t *rd
 {
     for (int64_t i = 0; i < n; ++i) q[i] = ampli_poisson_score_dense(k[i], rd[i], err[i], nullptr, 0);
 }
+// kf_lgamma at the integers 0 .. AMPLI_LGTAB - 1 as the kernels hold it (lgamma_table_kernel), by the host's own function, filled once
+static const double *host_lgtab()
+{
+    static const std::vector<double> tab = [] {
+        std::vector<double> t(AMPLI_LGTAB);
+        for (int i = 0; i < AMPLI_LGTAB; ++i) t[i] = ampli_kf_lgamma((double)i);
+        return t;
+    }();
+    return tab.data();
+}
+extern "C" void ampli_host_drain_score_table_batch(const int32_t *k, const int32_t *rd, const float *err, int64_t n, double *q, double *p)
+{
+    const double *tab = host_lgtab();
+    for (int64_t i = 0; i < n; ++i) {
+        const double m = (double)rd[i] * err[i];
+        const double pv = ampli_drain_p(k[i], m, tab, AMPLI_LGTAB);
+        if (p) p[i] = pv;
+        if (q) q[i] = ampli_q_from_p(pv);
+    }
+}
+extern "C" void ampli_host_dense_score_table_batch(const int32_t *k, const int32_t *rd, const float *err, int64_t n, double *q)
+{
+    const double *tab = host_lgtab();
+    for (int64_t i = 0; i < n; ++i) q[i] = ampli_poisson_score_dense(k[i], rd[i], err[i], tab, AMPLI_LGTAB);
+}
 extern "C" void ampli_host_af_limit_batch(const int32_t *d, int64_t n, int32_t *out)
 {
     for (int64_t i = 0; i < n; ++i) out[i] = ampli_af_limit(d[i]);

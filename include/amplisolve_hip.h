@@ -465,6 +465,14 @@ typedef struct ampli_call {
  *     emission order.  d_n_calls without d_calls just counts.
  *   d_q [T][R][4][2] double, optional dense scores (Q_fw,Q_bw per nucleotide; -1 = not evaluated;
  *     requires mode FULL); d_af [T][R][4][3] float optional dense {AF, AF_fw, AF_bw}.
+ * Count domain (ampli_poisson_call, _blocks and _records alike).  Admitted in the int32 layout: eight non-negative counts per
+ *   record with FW + BW <= INT32_MAX (what the ASEQ parser admits), and ANY int32 in the RD column (ampli_records.rd / rd_ext).
+ *   Inside it every kernel returns the reference's result: counts and depths of 2^24 and more are never skipped in fp32 (not
+ *   exact floats) but scored; a forward depth RD - BW of 0 gives Q = 100, a negative one (as a negative threshold cell) NaN and
+ *   no call; the lgamma table is indexed by 0 <= count <= 65536 only, every other count -- INT32_MAX included -- takes the
+ *   function (tests/test_gpu_call_domain.py, tests/test_gpu_scorer_domain.py).  Outside it nothing is read or written out of
+ *   bounds, and no more is promised: a negative count is scored by whatever the literal arithmetic gives (no count indexes
+ *   anything but that table), and strand sums beyond INT32_MAX wrap as int32 sums do.
  */
 int ampli_poisson_call(ampli_ctx *ctx, const int32_t *d_trecs, int64_t P, int64_t E,
                        const uint32_t *d_ext_pos, int32_t T, const float *d_thr,
@@ -1028,6 +1036,12 @@ int ampli_score_batch(ampli_ctx *ctx, const int32_t *d_k, const int32_t *d_rd, c
  * lgamma from a table of the Lanczos form's own values, division-free series and continued fraction (csrc/ampli_math.h,
  * ampli_poisson_score_dense); q[i] equals ampli_score_batch's to rounding (~1e-13 relative on p) */
 int ampli_score_dense_batch(ampli_ctx *ctx, const int32_t *d_k, const int32_t *d_rd, const float *d_err, int64_t n, double *d_q);
+/* the scorer of the prefilter mode's drain for the same tests: one strand of a queued item, a count k against a mean
+ * m = rd * err with 0 < m < k (the series branch, division-free, lgamma(k + 1) from the same table; csrc/ampli_math.h,
+ * ampli_drain_p): p[i] and q[i] = Q of it, as ampli_host_drain_score_batch.  Outside 0 < m < k the result is whatever that
+ * arithmetic gives (the drain never asks).  Either output may be NULL. */
+int ampli_drain_score_batch(ampli_ctx *ctx, const int32_t *d_k, const int32_t *d_rd, const float *d_err, int64_t n, double *d_q,
+                            double *d_p);
 /* text round trip on the device for known-answer tests: out[i] = stof(sprintf("%f", in[i])) */
 int ampli_roundtrip_batch(ampli_ctx *ctx, const float *d_in, int64_t n, float *d_out);
 

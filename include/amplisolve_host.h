@@ -42,6 +42,10 @@ int ampli_host_prefilter_skip_f32(int32_t k, int32_t rd, float err); /* the stre
 void ampli_host_dense_score_batch(const int32_t *k, const int32_t *rd, const float *err, int64_t n, double *q);
 /* the drain kernel's scorer (division-free series, csrc/ampli_math.h) for items with k > rd*err > 0: Q and p */
 void ampli_host_drain_score_batch(const int32_t *k, const int32_t *rd, const float *err, int64_t n, double *q, double *p);
+/* the same two with kf_lgamma at the integers read from a table of AMPLI_LGTAB entries, as the kernels read it: the table is
+ * filled once, by the host's own ampli_kf_lgamma; the results carry the same bits as the two above for every int32 input */
+void ampli_host_dense_score_table_batch(const int32_t *k, const int32_t *rd, const float *err, int64_t n, double *q);
+void ampli_host_drain_score_table_batch(const int32_t *k, const int32_t *rd, const float *err, int64_t n, double *q, double *p);
 
 /* ---- panel + cohort: BED (or error table) + a directory of .PILEUP.ASEQ packed into the record SoA ---- */
 typedef struct ampli_host_cohort ampli_host_cohort;

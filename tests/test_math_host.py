@@ -7,6 +7,7 @@ import numpy as np
 
 from amplisolve_amd import host_lib
 from oracle import pyoracle as orc
+from tests import scorer_grids
 
 
 def test_af_gate_integer_bound_equals_fp_gate():
@@ -146,26 +147,18 @@ def test_division_free_series_of_the_drain_kernel_is_the_reference_series():
     Q >= 20 decisions identical outside 1e-9 of a gate (a pair within 1e-6 of the call gate is re-decided by the host either
     way) -- including z so close to s that the reference's 99-term cap truncates the series, and depths up to the int32 range."""
     H = host_lib()
-    rng = np.random.default_rng(8)
-    ks, rds, es = [], [], []
-    for err in (0.0001, 0.0005, 0.002, 0.002189, 0.0035, 0.01, 0.02, 0.05, 0.25):
-        for scale in (50, 300, 1000, 2500, 25000, 400000, 3_000_000, 16_000_000, 500_000_000):
-            rd = rng.integers(max(1, scale // 2), scale * 2, 600)
-            m = rd * float(np.float32(err))
-            # k from just above m (slow convergence, cap region) to far above it (Q = 100)
-            for f in (1.0, 1.01, 1.1, 1.5, 3.0, 10.0):
-                k = np.maximum(np.floor(m * f).astype(np.int64) + rng.integers(1, 4, rd.size), 1)
-                ok = k < (1 << 31) - 1
-                ks.append(k[ok]); rds.append(rd[ok]); es.append(np.full(ok.sum(), err))
-    k = np.concatenate(ks).astype(np.int32)
-    rd = np.concatenate(rds).astype(np.int32)
-    e = np.concatenate(es).astype(np.float32)
-    keep = k.astype(np.float64) > rd.astype(np.float64) * e.astype(np.float64)
-    k, rd, e = k[keep], rd[keep], e[keep]
+    k, rd, e = scorer_grids.drain_grid()  # the device's test draws the same points (tests/test_gpu_scorer_domain.py)
+    assert (k == scorer_grids.INT32_MAX).any()
     q = np.empty(k.size, np.float64)
     p = np.empty(k.size, np.float64)
     H.ampli_host_drain_score_batch(k.ctypes.data_as(C.c_void_p), rd.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), k.size,
                                    q.ctypes.data_as(C.c_void_p), p.ctypes.data_as(C.c_void_p))
+    # kf_lgamma(k + 1) from the table, as the kernels read it, gives the very bits of calling the function
+    qt, pt = np.empty_like(q), np.empty_like(p)
+    H.ampli_host_drain_score_table_batch(k.ctypes.data_as(C.c_void_p), rd.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), k.size,
+                                         qt.ctypes.data_as(C.c_void_p), pt.ctypes.data_as(C.c_void_p))
+    assert (k < scorer_grids.LGTAB - 1).any() and (k >= scorer_grids.LGTAB - 1).any()  # both sides of the table's end
+    assert np.array_equal(pt.view(np.int64), p.view(np.int64)) and np.array_equal(qt.view(np.int64), q.view(np.int64))
     qo, po = orc.score_batch(k, rd, e)
     assert k.size > 200_000
     # p = 1 - (1 - P) is a multiple of 2^-53: a last-bit difference in P can move it by one such step
@@ -185,28 +178,16 @@ def test_dense_scorer_of_the_all_scores_mode_is_the_reference_scorer():
     on counts around the mean at every depth (both branches of kf_gammaq, the identity step j = s of the continued fraction,
     the 99-step caps of both loops, k and m far beyond 100) and on the special codes: p within 1e-11 relative + one step of
     1 - (1 - P) (the contract is 1e-6), the specials identical, the Q >= 5 / >= 20 / = 100 decisions identical outside 1e-9 of a gate."""
-    import os
-
     H = host_lib()
-    g = np.load(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "vc_scorer_reference.npz"))
-    rng = np.random.default_rng(21)
-    ks, rds, es = [g["k"].astype(np.int64)], [g["rd"].astype(np.int64)], [g["err"].astype(np.float64)]
-    for err in (0.0, -1.0, 0.0001, 0.0005, 0.002, 0.002189, 0.0035, 0.01, 0.02, 0.05, 0.25, 0.9):
-        for scale in (1, 5, 50, 300, 1000, 2500, 25000, 400000, 3_000_000, 16_000_000, 500_000_000):
-            rd = rng.integers(max(1, scale // 2), scale * 2 + 1, 400)
-            m = rd * float(np.float32(err if err > 0 else 0.0010008))
-            for f in (0.0, 0.3, 0.8, 0.97, 1.0, 1.03, 1.3, 3.0, 10.0):
-                k = np.maximum(np.floor(m * f).astype(np.int64) + rng.integers(-2, 3, rd.size), 0)
-                ok = k < (1 << 31) - 1
-                ks.append(k[ok]); rds.append(rd[ok]); es.append(np.full(int(ok.sum()), err))
-    # small counts x small means: what a 2000x panel holds
-    kk, mm = np.meshgrid(np.arange(0, 40), np.arange(1, 120), indexing="ij")
-    ks.append(kk.ravel()); rds.append(mm.ravel() * 50); es.append(np.full(kk.size, 0.002))
-    k = np.concatenate(ks).astype(np.int32)
-    rd = np.concatenate(rds).astype(np.int32)
-    e = np.concatenate(es).astype(np.float32)
+    k, rd, e = scorer_grids.dense_grid()  # the device's test draws the same points (tests/test_gpu_scorer_domain.py)
+    assert (k == scorer_grids.INT32_MAX).any()
     q = np.empty(k.size, np.float64)
     H.ampli_host_dense_score_batch(k.ctypes.data_as(C.c_void_p), rd.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), k.size, q.ctypes.data_as(C.c_void_p))
+    # kf_lgamma(k) and kf_lgamma(k + 1) from the table, as the kernels read them, give the very bits of calling the function
+    qt = np.empty_like(q)
+    H.ampli_host_dense_score_table_batch(k.ctypes.data_as(C.c_void_p), rd.ctypes.data_as(C.c_void_p), e.ctypes.data_as(C.c_void_p), k.size, qt.ctypes.data_as(C.c_void_p))
+    assert (k < scorer_grids.LGTAB - 1).any() and (k >= scorer_grids.LGTAB).any()  # both sides of the table's end
+    assert np.array_equal(qt.view(np.int64), q.view(np.int64))
     qo, po = orc.score_batch(k, rd, e)
     assert k.size > 400_000
     special = (qo == -888) | (qo == 100) | (qo == 0) | np.isnan(qo)
