@@ -47,6 +47,11 @@ class Records(C.Structure):
                 ("ext_pos", vp), ("layout", i32), ("n_samples", i32), ("rd", vp), ("rd_ext", vp)]
 
 
+class DiluteMix(C.Structure):
+    """mirror of ampli_dilute_mix: one mixture of the in-silico dilution, 32 bytes"""
+    _fields_ = [("row_a", i32), ("row_b", i32), ("keep_a", u64), ("keep_b", u64), ("key", u64)]
+
+
 # every symbol include/amplisolve_hip.h declares: (restype, argtypes)
 HIP_SYMBOLS = {
     "ampli_abi_version": (C.c_int, []),
@@ -160,6 +165,7 @@ HIP_SYMBOLS = {
     "ampli_pair_score_records": (C.c_int, [vp, C.POINTER(Records), C.POINTER(Records), i64, vp, i32, vp, i32, vp]),
     "ampli_fdr_workspace_bytes": (C.c_size_t, [i32, i64]),
     "ampli_fdr_adjust": (C.c_int, [vp, vp, i32, i64, i32, vp, C.c_size_t, vp, vp, vp]),
+    "ampli_dilute_records": (C.c_int, [vp, C.POINTER(Records), C.POINTER(Records), i64, vp, i32, vp, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -264,6 +270,10 @@ HOST_SYMBOLS = {
     "ampli_host_pair_score_batch": (C.c_int, [vp, vp, vp, vp, i64, vp]),
     "ampli_host_fdr_rows": (C.c_int, [vp, i32, i64, i32, vp, vp, vp]),
     "ampli_host_hyper_tail": (C.c_double, [i64, i64, i64, i64, i32, C.POINTER(i32)]),
+    "ampli_host_philox4x32_10": (None, [vp, vp, vp]),
+    "ampli_host_thin": (i64, [i64, u64, u64, C.c_uint32, i32, i32]),
+    "ampli_host_dilute_keep": (u64, [C.c_double]),
+    "ampli_host_dilute_records": (C.c_int, [vp, i32, i64, vp, i32, i64, i64, vp, i32, vp, vp]),
 }
 
 _hip = None

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, GenotypeParams, LooCall, Records, hip_lib
+from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, Records, hip_lib
 
 NT = "ACGT"
 POISSON_FULL = 0
@@ -61,6 +61,8 @@ EXCEEDANCE_ROWS = 8
 NB_NA = -1.0  # a cell of nb_score that is not evaluated (AMPLI_NB_NA)
 PAIR_NA = -999.0  # a cell of pair_score that is not evaluated (AMPLI_PAIR_NA)
 FDR_NA = -999.0  # a cell of fdr_adjust that is not tested (AMPLI_FDR_NA)
+DILUTE_BAD_COUNT, DILUTE_BAD_MIXTURE = 1, 2  # the flag word of a mixture of dilute (AMPLI_DILUTE_BAD_*)
+DILUTE_KEEP_ALL = 1 << 32  # the threshold that keeps every read
 
 
 def _ptr(t):
@@ -690,6 +692,38 @@ class Context:
         self._check(self.lib.ampli_pair_score_records(self.h, C.byref(recs_a), C.byref(recs_b), P, _ptr(pairs), n_pairs, _ptr(ref_code),
                                                       depth_cutoff, _ptr(s)))
         return s
+
+    def dilute(self, recs_a: Records, recs_b: Records | None, P: int, mixtures, out=None, flags=None):
+        """In-silico dilution (ampli_dilute_records): every mixture thins row_a of recs_a and, unless row_b is -1, row_b of
+        recs_b read by read and adds the two.  mixtures: a sequence of (row_a, row_b, keep_a, keep_b, key) -- keep in [0, 2^32] is the
+        threshold of ampli_host_dilute_keep, key any 64-bit word -- or a device tensor of descriptors (uint8 [n_mix, 32] or int64
+        [n_mix, 4]).  Returns (out, flags): out int32 [n_mix, P, 8], dense records of the I32 layout (dilution_records wraps them), flags
+        int32 [n_mix] (DILUTE_BAD_COUNT, DILUTE_BAD_MIXTURE)."""
+        import torch
+
+        if isinstance(mixtures, torch.Tensor):
+            d_mix = mixtures
+            assert d_mix.is_cuda and d_mix.is_contiguous() and d_mix.dim() == 2 and d_mix.shape[1] * d_mix.element_size() == C.sizeof(DiluteMix)
+        else:
+            if not len(mixtures):
+                raise AmpliError("dilute: the list of mixtures is empty")
+            rows = [DiluteMix(int(ra), int(rb), int(ka), int(kb), int(key) & 0xFFFFFFFFFFFFFFFF) for ra, rb, ka, kb, key in mixtures]
+            host = torch.frombuffer(bytearray(bytes((DiluteMix * len(rows))(*rows))), dtype=torch.uint8)
+            d_mix = host.view(len(rows), C.sizeof(DiluteMix)).to(self.device)
+        n_mix = int(d_mix.shape[0])
+        if out is None:
+            out = torch.empty((n_mix, P, 8), dtype=torch.int32, device=self.device)
+        if flags is None:
+            flags = torch.empty((n_mix,), dtype=torch.int32, device=self.device)
+        assert out.dtype == torch.int32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n_mix, P, 8)
+        assert flags.dtype == torch.int32 and flags.is_cuda and flags.is_contiguous() and tuple(flags.shape) == (n_mix,)
+        self._check(self.lib.ampli_dilute_records(self.h, C.byref(recs_a), C.byref(recs_b) if recs_b is not None else None, P, _ptr(d_mix), n_mix,
+                                                  _ptr(out), _ptr(flags)))
+        return out, flags
+
+    def dilution_records(self, out) -> Records:
+        """the mixtures dilute wrote as Records (I32, dense, E = 0, a row per mixture): what detection_limits, nb_score and the others take"""
+        return self.records(out, "i32", int(out.shape[0]))
 
     def fdr_workspace_bytes(self, rows: int, P: int) -> int:
         """Bytes of the workspace fdr_adjust needs for a plane of rows x P positions (ampli_fdr_workspace_bytes)."""

@@ -7,7 +7,8 @@
   bin/AmpliSolveSampleConcordance, bin/AmpliSolveContamination,
   bin/AmpliSolveAmpliconCoverage, bin/AmpliSolveSubstitutionSpectrum,
   bin/AmpliSolveNormalExceedance, bin/AmpliSolveOverdispersedCalling,
-  bin/AmpliSolvePairedComparison, bin/AmpliSolveFalseDiscovery                            the project's own command lines
+  bin/AmpliSolvePairedComparison, bin/AmpliSolveFalseDiscovery,
+  bin/AmpliSolveInSilicoDilution                                                          the project's own command lines
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the CPU-only container too.
 """
@@ -33,10 +34,10 @@ HOST_LIB = os.path.join(LIB, "libamplisolve_host.so")
 # detection limits and power, ampli_dispersion.hip the panel's dispersion, ampli_concordance.hip
 # genotype bit planes and all-pairs sample concordance, ampli_contamination.hip cross-sample contamination,
 # ampli_amplicon.hip amplicon coverage and copy ratio, ampli_spectrum.hip the substitution spectrum, ampli_exceedance.hip the panel-of-normals exceedance,
-# ampli_overdispersion.hip the overdispersion fit and the negative-binomial score, ampli_paired.hip the paired comparison of two files, ampli_fdr.hip false-discovery control (device sort and scan), ampli_aux.hip scorer checks and synthetic panels.  ampli_runtime.hip: context, streams, memory and
+# ampli_overdispersion.hip the overdispersion fit and the negative-binomial score, ampli_paired.hip the paired comparison of two files, ampli_fdr.hip false-discovery control (device sort and scan), ampli_dilution.hip in-silico dilution (read-level mixing), ampli_aux.hip scorer checks and synthetic panels.  ampli_runtime.hip: context, streams, memory and
 # settings; ampli_pileup.hip: the upstream counting kernel; ampli_comm.hip: RCCL binding
 HIP_SOURCES = ["ampli_kernels.hip", "ampli_exchange.hip", "ampli_loo.hip", "ampli_limits.hip", "ampli_dispersion.hip", "ampli_concordance.hip", "ampli_contamination.hip",
-               "ampli_amplicon.hip", "ampli_spectrum.hip", "ampli_exceedance.hip", "ampli_overdispersion.hip", "ampli_paired.hip", "ampli_fdr.hip", "ampli_aux.hip",
+               "ampli_amplicon.hip", "ampli_spectrum.hip", "ampli_exceedance.hip", "ampli_overdispersion.hip", "ampli_paired.hip", "ampli_fdr.hip", "ampli_dilution.hip", "ampli_aux.hip",
                "ampli_runtime.hip", "ampli_pileup.hip", "ampli_comm.hip"]
 HIP_HEADERS = ["ampli_device.h", "ampli_internal.h", "ampli_math.h", "ampli_synth.h"]
 OBJ = os.path.join(PKG, "build")
@@ -96,7 +97,8 @@ def build_host(force: bool = False) -> str:
                       ("AmpliSolveSampleConcordance", "sc_main.cpp"), ("AmpliSolveContamination", "ct_main.cpp"),
                       ("AmpliSolveAmpliconCoverage", "ac_main.cpp"), ("AmpliSolveSubstitutionSpectrum", "ss_main.cpp"),
                       ("AmpliSolveNormalExceedance", "ex_main.cpp"), ("AmpliSolveOverdispersedCalling", "od_main.cpp"),
-                      ("AmpliSolvePairedComparison", "pc_main.cpp"), ("AmpliSolveFalseDiscovery", "fd_main.cpp")):
+                      ("AmpliSolvePairedComparison", "pc_main.cpp"), ("AmpliSolveFalseDiscovery", "fd_main.cpp"),
+                      ("AmpliSolveInSilicoDilution", "di_main.cpp")):
         msrc = os.path.join(hdir, main)
         out = os.path.join(BIN, exe)
         if os.path.exists(msrc) and (force or _newer(out, deps + [msrc, HOST_LIB])):

@@ -1515,4 +1515,94 @@ AMPLI_FN float ampli_fdr_store(int cls, float bmax)
     return cls == AMPLI_FDR_MINUS ? -bmax : bmax;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// In-silico dilution (the definition is tests/dilution_model.py): read-level mixing of two count files.  32-bit integer
+// work only, so the device, the host library and the numpy model agree integer for integer.
+//   Generator.  Philox4x32-10 (Salmon et al., 2011).  Multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; key increments W0 = 0x9E3779B9,
+//     W1 = 0xBB67AE85.  One round on counter (c0, c1, c2, c3) with key (k0, k1): (hi0, lo0) = M0 * c0 as a 64-bit product,
+//     (hi1, lo1) = M1 * c2; the new counter is (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0).  Ten rounds; the key is bumped by (W0, W1)
+//     after each round (the bump after the last round is dead).
+//   Thinning.  Thin(n, keep; key, p, f, side) = #{ i < n : word_i < keep }, compared as 64-bit unsigned, keep in [0, 2^32].  word_i is
+//     output word (i & 3) of Philox with counter (i >> 2, p, f | side << 3, 0) and key (low word, high word of the 64-bit key); p is the
+//     position index, f in 0..7 the record field, side 0 for file a and 1 for file b.  A read is word i of its field, kept with
+//     probability keep / 2^32, independently.  Exactly: keep = 2^32 keeps all, keep = 0 keeps none, Thin is non-decreasing in n and in
+//     keep -- so a series with one key is nested.
+//   Mixture.  {int32 row_a; int32 row_b; uint64 keep_a; uint64 keep_b; uint64 key}: out[f] = Thin(a[f], keep_a; key, p, f, 0) +
+//     Thin(b[f], keep_b; key, p, f, 1) over the PRIMARY records; row_b == -1 is pure down-sampling.  The output record is ABSENT
+//     (field 0 = AMPLI_ABSENT, the other seven 0) when a's record is absent, when b is named and its record is absent, or when a present
+//     input record holds a count outside [0, 2^24 - 2] (AMPLI_DILUTE_BAD_COUNT).  A mixture is all ABSENT with AMPLI_DILUTE_BAD_MIXTURE
+//     when a row is outside its chunk, a keep is above 2^32, row_b >= 0 without a chunk b, or row_b < -1.
+//   Fractions to thresholds.  keep = (uint64) floor(ldexp(x, 32) + 0.5), x a double in [0, 1]: IEEE operations, the same everywhere.
+// ------------------------------------------------------------------------------------------------------------------------------------
+#ifndef AMPLI_DILUTE_MIX_DEFINED // also in include/amplisolve_hip.h and include/amplisolve_host.h
+#define AMPLI_DILUTE_MIX_DEFINED
+typedef struct ampli_dilute_mix {
+    int32_t row_a, row_b;
+    uint64_t keep_a, keep_b, key;
+} ampli_dilute_mix;
+#define AMPLI_DILUTE_BAD_COUNT 1
+#define AMPLI_DILUTE_BAD_MIXTURE 2
+#define AMPLI_DILUTE_MAX_COUNT 16777214 /* 2^24 - 2 */
+#endif
+#define AMPLI_DILUTE_KEEP_ALL 4294967296ull // 2^32
+#ifdef __cplusplus // whichever of the three copies came first, this is the layout the kernel, the host library and the bindings share
+#include <stddef.h>
+static_assert(sizeof(ampli_dilute_mix) == 32 && offsetof(ampli_dilute_mix, row_a) == 0 && offsetof(ampli_dilute_mix, row_b) == 4 &&
+                  offsetof(ampli_dilute_mix, keep_a) == 8 && offsetof(ampli_dilute_mix, keep_b) == 16 && offsetof(ampli_dilute_mix, key) == 24,
+              "ampli_dilute_mix is {int32 row_a; int32 row_b; uint64 keep_a; uint64 keep_b; uint64 key}, 32 bytes");
+static_assert(AMPLI_DILUTE_BAD_COUNT == 1 && AMPLI_DILUTE_BAD_MIXTURE == 2 && AMPLI_DILUTE_MAX_COUNT == (1 << 24) - 2, "the flag bits and the count range");
+#endif
+
+AMPLI_FN void ampli_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
+{
+    uint32_t c0 = ctr[0], c1 = ctr[1], c2 = ctr[2], c3 = ctr[3], k0 = key[0], k1 = key[1];
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c0, p1 = (uint64_t)0xCD9E8D57u * c2;
+        const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c1 ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c3 ^ k1;
+        c1 = (uint32_t)p1; c3 = (uint32_t)p0; c0 = n0; c2 = n2;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+    out[0] = c0; out[1] = c1; out[2] = c2; out[3] = c3;
+}
+
+// the kept reads of ONE Philox block: block j of list (p, fs = f | side << 3), of whose four words the first `live` (1..4) are reads
+AMPLI_FN int ampli_thin_block(uint32_t j, int live, uint64_t keep, uint64_t key, uint32_t p, uint32_t fs)
+{
+    const uint32_t ctr[4] = {j, p, fs, 0u}, k[2] = {(uint32_t)key, (uint32_t)(key >> 32)};
+    uint32_t w[4];
+    ampli_philox4x32_10(ctr, k, w);
+    int c = (uint64_t)w[0] < keep ? 1 : 0;
+    c += (live > 1 && (uint64_t)w[1] < keep) ? 1 : 0;
+    c += (live > 2 && (uint64_t)w[2] < keep) ? 1 : 0;
+    c += (live > 3 && (uint64_t)w[3] < keep) ? 1 : 0;
+    return c;
+}
+
+// Thin itself, block after block (the host library and the checks; the kernel deals the blocks out to its lanes)
+AMPLI_FN int64_t ampli_thin(int64_t n, uint64_t keep, uint64_t key, uint32_t p, int field, int side)
+{
+    if (n <= 0 || keep == 0) return 0;
+    if (keep >= AMPLI_DILUTE_KEEP_ALL) return n;
+    int64_t c = 0;
+    for (int64_t j = 0; 4 * j < n; ++j) c += ampli_thin_block((uint32_t)j, n - 4 * j >= 4 ? 4 : (int)(n - 4 * j), keep, key, p, (uint32_t)(field | side << 3));
+    return c;
+}
+
+AMPLI_FN uint64_t ampli_dilute_keep(double x) { return (uint64_t)floor(ldexp(x, 32) + 0.5); }
+
+// a mixture's own faults, checked before any record is loaded; has_b: a chunk b was given
+AMPLI_FN int ampli_dilute_mix_ok(int32_t row_a, int32_t row_b, uint64_t keep_a, uint64_t keep_b, int32_t n_a, int32_t n_b, int has_b)
+{
+    if (row_a < 0 || row_a >= n_a || keep_a > AMPLI_DILUTE_KEEP_ALL || keep_b > AMPLI_DILUTE_KEEP_ALL || row_b < -1) return 0;
+    return row_b == -1 || (has_b && row_b < n_b);
+}
+
+// a present record's counts all lie in [0, 2^24 - 2]
+AMPLI_FN int ampli_dilute_counts_ok(const int32_t r[8])
+{
+    int ok = 1;
+    for (int f = 0; f < 8; ++f) ok &= (uint32_t)r[f] <= (uint32_t)AMPLI_DILUTE_MAX_COUNT;
+    return ok;
+}
+
 #endif

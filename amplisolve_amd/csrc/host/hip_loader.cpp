@@ -68,6 +68,7 @@ static void load()
     BIND(nb_score_records, "ampli_nb_score_records")
     BIND(pair_score_records, "ampli_pair_score_records")
     BIND(fdr_workspace_bytes, "ampli_fdr_workspace_bytes") BIND(fdr_adjust, "ampli_fdr_adjust")
+    BIND(dilute_records, "ampli_dilute_records")
     BIND(event_create, "ampli_event_create") BIND(event_destroy, "ampli_event_destroy") BIND(event_record, "ampli_event_record") BIND(event_sync, "ampli_event_sync")
     BIND(pileup_count, "ampli_pileup_count")
     BIND(comm_create, "ampli_comm_create") BIND(comm_destroy, "ampli_comm_destroy") BIND(comm_reduce_scatter_f64, "ampli_comm_reduce_scatter_f64")

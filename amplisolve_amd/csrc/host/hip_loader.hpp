@@ -83,6 +83,7 @@ struct HipApi {
     int (*pair_score_records)(ampli_ctx *, const ampli_records *, const ampli_records *, int64_t, const int32_t *, int32_t, const uint8_t *, int32_t, float *);
     size_t (*fdr_workspace_bytes)(int32_t, int64_t);
     int (*fdr_adjust)(ampli_ctx *, const float *, int32_t, int64_t, int32_t, void *, size_t, float *, int32_t *, int32_t *);
+    int (*dilute_records)(ampli_ctx *, const ampli_records *, const ampli_records *, int64_t, const ampli_dilute_mix *, int32_t, int32_t *, int32_t *);
     int (*event_create)(void **);
     int (*event_destroy)(void *);
     int (*event_record)(ampli_ctx *, void *);

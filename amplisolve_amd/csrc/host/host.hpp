@@ -302,6 +302,15 @@ struct PcArgs {
     std::string panel_design, reference_genome, sample_dir, pairs, depth_cutoff = "100", q_min = "13", min_vaf = "0.005", output_dir, refbases_file;
 };
 int run_paired_comparison(const PcArgs &a);
+// ---- run_di.cpp ----
+// AmpliSolveInSilicoDilution (di_main.cpp, run_di.cpp): a dilution series over the files of sample_dir -- every line of `mixtures`
+// (source<TAB>diluent or -<TAB>fraction[<TAB>scale]) mixed `replicates` times read by read, gated with the table's thresholds, the share of
+// the source's called cells still called beside the predicted power.  replicates in 1 .. 2^20 - 1, seed an unsigned 64-bit integer,
+// coverage_cutoff >= 1, confidence in [0.5, 0.99], write_counts 0 or 1; exit status 0 / 1
+struct DiArgs {
+    std::string error_file, sample_dir, mixtures, replicates = "8", seed = "1", coverage_cutoff = "100", confidence = "0.95", write_counts = "0", output_dir;
+};
+int run_insilico_dilution(const DiArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

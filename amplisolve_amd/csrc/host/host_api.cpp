@@ -376,6 +376,54 @@ extern "C" double ampli_host_hyper_tail(int64_t N, int64_t K, int64_t n, int64_t
     return s.res;
 }
 
+extern "C" void ampli_host_philox4x32_10(const uint32_t *ctr, const uint32_t *key, uint32_t *out) { ampli_philox4x32_10(ctr, key, out); }
+
+extern "C" int64_t ampli_host_thin(int64_t n, uint64_t keep, uint64_t key, uint32_t p, int32_t field, int32_t side)
+{
+    if (n < 0 || keep > AMPLI_DILUTE_KEEP_ALL || field < 0 || field > 7 || side < 0 || side > 1) return -1;
+    return ampli_thin(n, keep, key, p, field, side);
+}
+
+extern "C" uint64_t ampli_host_dilute_keep(double x) { return x >= 0.0 && x <= 1.0 ? ampli_dilute_keep(x) : UINT64_MAX; }
+
+extern "C" int ampli_host_dilute_records(const int32_t *recs_a, int32_t n_a, int64_t stride_a, const int32_t *recs_b, int32_t n_b, int64_t stride_b,
+                                         int64_t P, const ampli_dilute_mix *mix, int32_t n_mix, int32_t *out, int32_t *flags)
+{
+    if (!recs_a || !mix || !out || !flags || P <= 0 || n_mix < 1 || n_a < 1 || n_b < 0 || (!recs_b && n_b != 0)) return AMPLI_E_INVALID;
+    if (stride_a == 0) stride_a = P;
+    if (stride_b == 0) stride_b = P;
+    if (stride_a < P || stride_b < P) return AMPLI_E_INVALID;
+    if (P >= 0x7FFFFFFFll) return AMPLI_E_RANGE;
+    for (int32_t m = 0; m < n_mix; ++m) {
+        const ampli_dilute_mix &mx = mix[m];
+        int32_t *o = out + (size_t)m * (size_t)P * 8;
+        const bool mix_ok = ampli_dilute_mix_ok(mx.row_a, mx.row_b, mx.keep_a, mx.keep_b, n_a, n_b, recs_b != nullptr) != 0;
+        int flag = mix_ok ? 0 : AMPLI_DILUTE_BAD_MIXTURE;
+        for (int64_t p = 0; p < P; ++p, o += 8) {
+            bool present = mix_ok;
+            const int32_t *a = nullptr, *b = nullptr;
+            if (mix_ok) {
+                bool bad = false;
+                a = recs_a + ((size_t)mx.row_a * (size_t)stride_a + (size_t)p) * 8;
+                if (a[0] == AMPLI_ABSENT) present = false;
+                else bad = !ampli_dilute_counts_ok(a);
+                if (mx.row_b >= 0) {
+                    b = recs_b + ((size_t)mx.row_b * (size_t)stride_b + (size_t)p) * 8;
+                    if (b[0] == AMPLI_ABSENT) present = false;
+                    else bad = bad || !ampli_dilute_counts_ok(b);
+                }
+                if (bad) { flag |= AMPLI_DILUTE_BAD_COUNT; present = false; }
+            }
+            for (int f = 0; f < 8; ++f) {
+                if (!present) o[f] = f == 0 ? AMPLI_ABSENT : 0;
+                else o[f] = (int32_t)(ampli_thin(a[f], mx.keep_a, mx.key, (uint32_t)p, f, 0) + (b ? ampli_thin(b[f], mx.keep_b, mx.key, (uint32_t)p, f, 1) : 0));
+            }
+        }
+        flags[m] = flag;
+    }
+    return 0;
+}
+
 extern "C" int ampli_host_genotype_classify_batch(const int32_t *recs, int64_t count, const ampli_genotype_params *prm, uint8_t *bits)
 {
     if (!recs || !prm || !bits || count < 0 || !ampli_genotype_params_ok(prm)) return AMPLI_E_INVALID;

@@ -140,6 +140,9 @@ extern "C" {
  *        OVERWRITTEN, AMPLI_FDR_NA included, whatever they held; d_rank [rows][P][4] is FULLY OVERWRITTEN when it is not NULL.  d_work
  *        is written only inside its first work_bytes bytes (ampli_fdr_workspace_bytes(rows, P) of them are used).  d_s is read at
  *        [0, 8 rows P) and never written.  Nothing else is written.
+ *   (C21) in-silico dilution (tests/test_gpu_dilution_contracts.py): d_out of ampli_dilute_records is FULLY OVERWRITTEN, all
+ *        [n_mix][P][8] words, ABSENT records included, and d_flags is FULLY OVERWRITTEN, all [n_mix] words, whatever they held.  Nothing
+ *        else is written.  d_mix is read at [0, n_mix), a record only at a position below P, of a row that a valid mixture names.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -984,6 +987,58 @@ int ampli_pair_score_records(ampli_ctx *ctx, const ampli_records *recs_a, const 
 size_t ampli_fdr_workspace_bytes(int32_t rows, int64_t P);
 int ampli_fdr_adjust(ampli_ctx *ctx, const float *d_s /* [rows][P][4][2] */, int32_t rows, int64_t P, int32_t two_sided, void *d_work,
                      size_t work_bytes, float *d_a /* [rows][P][4] */, int32_t *d_m /* [rows] */, int32_t *d_rank /* [rows][P][4] or NULL */);
+
+/*
+ * In-silico dilution (the definition is tests/dilution_model.py): read-level mixing of two count files.  32-bit integer
+ * work only, so the device, the host library and the numpy model agree integer for integer.
+ *   Generator.  Philox4x32-10 (Salmon et al., 2011).  Multipliers M0 = 0xD2511F53, M1 = 0xCD9E8D57; key increments W0 = 0x9E3779B9,
+ *     W1 = 0xBB67AE85.  One round on counter (c0, c1, c2, c3) with key (k0, k1): (hi0, lo0) = M0 * c0 as a 64-bit product,
+ *     (hi1, lo1) = M1 * c2; the new counter is (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0).  Ten rounds; the key is bumped by (W0, W1)
+ *     after each round (the bump after the last round is dead).
+ *   Thinning.  Thin(n, keep; key, p, f, side) = #{ i < n : word_i < keep }, compared as 64-bit unsigned, keep in [0, 2^32].  word_i is
+ *     output word (i & 3) of Philox with counter (i >> 2, p, f | side << 3, 0) and key (low word, high word of the 64-bit key); p is the
+ *     position index, f in 0..7 the record field, side 0 for file a and 1 for file b.  A read is word i of its field, kept with
+ *     probability keep / 2^32, independently.  Exactly: keep = 2^32 keeps all, keep = 0 keeps none, Thin is non-decreasing in n and in
+ *     keep -- so a series with one key is nested.
+ *   Mixture.  {int32 row_a; int32 row_b; uint64 keep_a; uint64 keep_b; uint64 key}: out[f] = Thin(a[f], keep_a; key, p, f, 0) +
+ *     Thin(b[f], keep_b; key, p, f, 1) over the PRIMARY records; row_b == -1 is pure down-sampling.  The output record is ABSENT
+ *     (field 0 = AMPLI_ABSENT, the other seven 0) when a's record is absent, when b is named and its record is absent, or when a present
+ *     input record holds a count outside [0, 2^24 - 2] (AMPLI_DILUTE_BAD_COUNT).  A mixture is all ABSENT with AMPLI_DILUTE_BAD_MIXTURE
+ *     when a row is outside its chunk, a keep is above 2^32, row_b >= 0 without a chunk b, or row_b < -1.
+ *   Fractions to thresholds.  keep = (uint64) floor(ldexp(x, 32) + 0.5), x a double in [0, 1]: IEEE operations, the same everywhere.
+ *
+ * ampli_dilute_records: d_mix, n_mix descriptors of 32 bytes in DEVICE memory, 8-byte aligned (like d_pairs of the paired comparison).
+ * Only the PRIMARY record of (row, position) enters, slot r < P; extras and an RD plane have no effect.  recs_a and recs_b may be the
+ * same chunk, different chunks, or chunks of different layouts; recs_b may be NULL when every mixture has row_b == -1.  A row may occur
+ * in many mixtures.  [0, 2^24 - 2] is the range the fast kernels take: it bounds a list at 2^22 Philox blocks and keeps every output
+ * below 2^25.  The mixture's faults are checked on the device before any record is loaded (they cannot be checked on the host without
+ * a copy); both keeps are checked whether b is named or not.  A bad count in EITHER present input record raises the flag.
+ *   d_out int32 [n_mix][P][8], 16-byte aligned: the AMPLI_RECORDS_I32 layout, dense, E = 0 -- every entry point takes it as an
+ *     ampli_records as it stands (n_samples = n_mix), and so does ampli_records_pack16.
+ *   d_flags int32 [n_mix]: AMPLI_DILUTE_BAD_COUNT | AMPLI_DILUTE_BAD_MIXTURE, 0 for a clean mixture.  The call clears it on the stream
+ *     and the kernel ORs into it with at most one integer atomic per workgroup; OR is order-free.
+ * No kernel reads another mixture's data: a mixture's bytes do not depend on the batch it is launched in, and the same inputs give the
+ * same bytes.
+ * Refusals, every output untouched.  AMPLI_E_INVALID: a null or misaligned pointer other than recs_b, P <= 0, n_mix < 1, broken
+ * records (n < 1, an unknown layout, a row stride below P + E, misaligned records).  AMPLI_E_RANGE: P >= 2^31.
+ * The form (csrc/ampli_dilution.hip): the grid is (position tiles, mixtures), at most 65 535 mixtures a launch; a wave owns one record
+ * at a time, its 64 lanes deal out the record's Philox blocks, the per-field counts are added across the wave and one 32-byte record is
+ * stored.  The 16 (side, field) lists of a record are walked one after the other (DESIGN 22 measures the alternative).  Asynchronous
+ * on the context's stream.
+ */
+#ifndef AMPLI_DILUTE_MIX_DEFINED /* also in csrc/ampli_math.h and include/amplisolve_host.h */
+#define AMPLI_DILUTE_MIX_DEFINED
+typedef struct ampli_dilute_mix {
+    int32_t row_a, row_b;
+    uint64_t keep_a, keep_b, key;
+} ampli_dilute_mix;
+#define AMPLI_DILUTE_BAD_COUNT 1
+#define AMPLI_DILUTE_BAD_MIXTURE 2
+#define AMPLI_DILUTE_MAX_COUNT 16777214 /* 2^24 - 2 */
+#endif
+int ampli_dilute_records(ampli_ctx *ctx, const ampli_records *recs_a, const ampli_records *recs_b /* may be NULL */, int64_t P,
+                         const ampli_dilute_mix *d_mix /* [n_mix] */, int32_t n_mix, int32_t *d_out /* [n_mix][P][8] */,
+                         int32_t *d_flags /* [n_mix] */);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

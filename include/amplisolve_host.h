@@ -299,6 +299,32 @@ double ampli_host_hyper_tail(int64_t N, int64_t K, int64_t n, int64_t k, int32_t
  *   AMPLI_E_INVALID (-1) for a null pointer, rows < 1, P <= 0 or two_sided not 0 or 1, AMPLI_E_RANGE (-6) for 4 P >= 2^31. */
 int ampli_host_fdr_rows(const float *s, int32_t rows, int64_t P, int32_t two_sided, float *a, int32_t *m, int32_t *rank);
 
+/* In-silico dilution (the definition is tests/dilution_model.py): csrc/ampli_math.h's functions, the text dilute_kernel runs,
+ * so that every integer is pinned without a GPU.  The definition in full stands in include/amplisolve_hip.h (ampli_dilute_records).
+ * _philox4x32_10: Philox4x32-10 of counter ctr[4] and key key[2] into out[4].
+ * _thin: Thin(n, keep; key, p, field, side) = #{ i < n : word_i < keep }, word_i = output word (i & 3) of Philox with counter
+ *   (i >> 2, p, field | side << 3, 0) and key (low word, high word); -1 for n < 0, keep above 2^32, field outside 0..7 or side outside 0..1.
+ * _dilute_keep: (uint64) floor(ldexp(x, 32) + 0.5); x outside [0, 1] (a NaN included) gives UINT64_MAX, which every entry refuses.
+ * _dilute_records: ampli_dilute_records over int32 records on the host.  recs_a int32 [n_a][stride_a][8] and recs_b (NULL with n_b = 0
+ *   when there is no chunk b) [n_b][stride_b][8], strides in records (0 = P), of which the first P records of a row enter; mix [n_mix];
+ *   out int32 [n_mix][P][8] and flags int32 [n_mix], both fully overwritten.  Returns 0, or AMPLI_E_INVALID (-1) with nothing written
+ *   for a null pointer other than recs_b, P <= 0, n_mix < 1, n_a < 1, n_b < 0, a stride below P, AMPLI_E_RANGE (-6) for P >= 2^31. */
+#ifndef AMPLI_DILUTE_MIX_DEFINED /* also in csrc/ampli_math.h and include/amplisolve_hip.h */
+#define AMPLI_DILUTE_MIX_DEFINED
+typedef struct ampli_dilute_mix {
+    int32_t row_a, row_b;
+    uint64_t keep_a, keep_b, key;
+} ampli_dilute_mix;
+#define AMPLI_DILUTE_BAD_COUNT 1
+#define AMPLI_DILUTE_BAD_MIXTURE 2
+#define AMPLI_DILUTE_MAX_COUNT 16777214 /* 2^24 - 2 */
+#endif
+void ampli_host_philox4x32_10(const uint32_t *ctr, const uint32_t *key, uint32_t *out);
+int64_t ampli_host_thin(int64_t n, uint64_t keep, uint64_t key, uint32_t p, int32_t field, int32_t side);
+uint64_t ampli_host_dilute_keep(double x);
+int ampli_host_dilute_records(const int32_t *recs_a, int32_t n_a, int64_t stride_a, const int32_t *recs_b, int32_t n_b, int64_t stride_b, int64_t P,
+                              const ampli_dilute_mix *mix, int32_t n_mix, int32_t *out, int32_t *flags);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */
