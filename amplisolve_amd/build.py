@@ -2,13 +2,9 @@
 
   lib/libamplisolve_hip.so   HIP kernels + C ABI (include/amplisolve_hip.h), hipcc --offload-arch=gfx950
   lib/libamplisolve_host.so  C++ host: BED / ASEQ / error-table parsers, SoA packer, writers (include/amplisolve_host.h)
-  bin/AmpliSolveErrorEstimation, bin/AmpliSolveVariantCalling   the two drop-in command lines
-  bin/AmpliSolveLeaveOneOut, bin/AmpliSolveDetectionLimit, bin/AmpliSolveDetectionPower, bin/AmpliSolvePanelDispersion,
-  bin/AmpliSolveSampleConcordance, bin/AmpliSolveContamination,
-  bin/AmpliSolveAmpliconCoverage, bin/AmpliSolveSubstitutionSpectrum,
-  bin/AmpliSolveNormalExceedance, bin/AmpliSolveOverdispersedCalling,
-  bin/AmpliSolvePairedComparison, bin/AmpliSolveFalseDiscovery,
-  bin/AmpliSolveInSilicoDilution                                                          the project's own command lines
+  bin/<executable>           one per csrc/host/*_main.cpp (EXECUTABLES below): the drop-in command lines and the project's own
+
+Both libraries take the constants and plain structs they share from include/amplisolve_types.h.
 
 hipcc cross-compiles gfx950 without a GPU, so this runs in the CPU-only container too.
 """
@@ -29,17 +25,26 @@ BIN = os.path.join(PKG, "bin")
 HIP_LIB = os.path.join(LIB, "libamplisolve_hip.so")
 HOST_LIB = os.path.join(LIB, "libamplisolve_host.so")
 
-# The kernels + their C ABI, one translation unit per stage (the map: csrc/ampli_kernels.hip): ampli_kernels.hip the timed step (records,
-# error reduce, finalize, Poisson), ampli_exchange.hip the multi-GPU merges and slices, ampli_loo.hip leave-one-out, ampli_limits.hip
-# detection limits and power, ampli_dispersion.hip the panel's dispersion, ampli_concordance.hip
-# genotype bit planes and all-pairs sample concordance, ampli_contamination.hip cross-sample contamination,
-# ampli_amplicon.hip amplicon coverage and copy ratio, ampli_spectrum.hip the substitution spectrum, ampli_exceedance.hip the panel-of-normals exceedance,
-# ampli_overdispersion.hip the overdispersion fit and the negative-binomial score, ampli_paired.hip the paired comparison of two files, ampli_fdr.hip false-discovery control (device sort and scan), ampli_dilution.hip in-silico dilution (read-level mixing), ampli_aux.hip scorer checks and synthetic panels.  ampli_runtime.hip: context, streams, memory and
-# settings; ampli_pileup.hip: the upstream counting kernel; ampli_comm.hip: RCCL binding
+# The kernels + their C ABI, one translation unit per stage; what each one holds is the map at the head of csrc/ampli_kernels.hip
+# (the timed step itself) and the first lines of each file.
 HIP_SOURCES = ["ampli_kernels.hip", "ampli_exchange.hip", "ampli_loo.hip", "ampli_limits.hip", "ampli_dispersion.hip", "ampli_concordance.hip", "ampli_contamination.hip",
                "ampli_amplicon.hip", "ampli_spectrum.hip", "ampli_exceedance.hip", "ampli_overdispersion.hip", "ampli_paired.hip", "ampli_fdr.hip", "ampli_dilution.hip", "ampli_aux.hip",
                "ampli_runtime.hip", "ampli_pileup.hip", "ampli_comm.hip"]
 HIP_HEADERS = ["ampli_device.h", "ampli_internal.h", "ampli_math.h", "ampli_synth.h"]
+# the public headers; amplisolve_types.h is included by the other two and by csrc/ampli_math.h, so both libraries depend on it
+INCLUDE = os.path.join(ROOT, "include")
+TYPES_H = os.path.join(INCLUDE, "amplisolve_types.h")
+HIP_H = os.path.join(INCLUDE, "amplisolve_hip.h")
+HOST_H = os.path.join(INCLUDE, "amplisolve_host.h")
+# (executable, its main under csrc/host): the two drop-in command lines and computeCounts, then the project's own commands
+EXECUTABLES = (("AmpliSolveErrorEstimation", "ee_main.cpp"), ("AmpliSolveVariantCalling", "vc_main.cpp"), ("computeCounts", "cc_main.cpp"),
+               ("AmpliSolveLeaveOneOut", "loo_main.cpp"), ("AmpliSolveDetectionLimit", "dl_main.cpp"),
+               ("AmpliSolveDetectionPower", "dp_main.cpp"), ("AmpliSolvePanelDispersion", "pd_main.cpp"),
+               ("AmpliSolveSampleConcordance", "sc_main.cpp"), ("AmpliSolveContamination", "ct_main.cpp"),
+               ("AmpliSolveAmpliconCoverage", "ac_main.cpp"), ("AmpliSolveSubstitutionSpectrum", "ss_main.cpp"),
+               ("AmpliSolveNormalExceedance", "ex_main.cpp"), ("AmpliSolveOverdispersedCalling", "od_main.cpp"),
+               ("AmpliSolvePairedComparison", "pc_main.cpp"), ("AmpliSolveFalseDiscovery", "fd_main.cpp"),
+               ("AmpliSolveInSilicoDilution", "di_main.cpp"))
 OBJ = os.path.join(PKG, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off"]
 CXX_FLAGS = ["-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-pthread"]
@@ -69,7 +74,7 @@ def hipcc_path() -> str:
 def build_hip(force: bool = False) -> str:
     os.makedirs(LIB, exist_ok=True)
     srcs = [os.path.join(CSRC, f) for f in HIP_SOURCES]
-    deps = srcs + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [os.path.join(ROOT, "include", "amplisolve_hip.h")]
+    deps = srcs + [os.path.join(CSRC, h) for h in HIP_HEADERS] + [HIP_H, TYPES_H]
     if force or _newer(HIP_LIB, deps):
         # every translation unit to an object of its own, all at once (at most 16 compilers), then one link
         os.makedirs(OBJ, exist_ok=True)
@@ -87,18 +92,10 @@ def build_host(force: bool = False) -> str:
     hdir = os.path.join(CSRC, "host")
     srcs = [os.path.join(hdir, f) for f in sorted(os.listdir(hdir)) if f.endswith(".cpp") and not f.endswith("_main.cpp")]
     deps = srcs + [os.path.join(hdir, f) for f in os.listdir(hdir) if f.endswith(".hpp")] + [
-        os.path.join(CSRC, "ampli_math.h"), os.path.join(CSRC, "ampli_synth.h"),
-        os.path.join(ROOT, "include", "amplisolve_host.h"), os.path.join(ROOT, "include", "amplisolve_hip.h")]
+        os.path.join(CSRC, "ampli_math.h"), os.path.join(CSRC, "ampli_synth.h"), HOST_H, HIP_H, TYPES_H]
     if force or _newer(HOST_LIB, deps):
         _run(["g++", *CXX_FLAGS, "-shared", "-o", HOST_LIB, *srcs, "-ldl", "-lz"])
-    for exe, main in (("AmpliSolveErrorEstimation", "ee_main.cpp"), ("AmpliSolveVariantCalling", "vc_main.cpp"), ("computeCounts", "cc_main.cpp"),
-                      ("AmpliSolveLeaveOneOut", "loo_main.cpp"), ("AmpliSolveDetectionLimit", "dl_main.cpp"),
-                      ("AmpliSolveDetectionPower", "dp_main.cpp"), ("AmpliSolvePanelDispersion", "pd_main.cpp"),
-                      ("AmpliSolveSampleConcordance", "sc_main.cpp"), ("AmpliSolveContamination", "ct_main.cpp"),
-                      ("AmpliSolveAmpliconCoverage", "ac_main.cpp"), ("AmpliSolveSubstitutionSpectrum", "ss_main.cpp"),
-                      ("AmpliSolveNormalExceedance", "ex_main.cpp"), ("AmpliSolveOverdispersedCalling", "od_main.cpp"),
-                      ("AmpliSolvePairedComparison", "pc_main.cpp"), ("AmpliSolveFalseDiscovery", "fd_main.cpp"),
-                      ("AmpliSolveInSilicoDilution", "di_main.cpp")):
+    for exe, main in EXECUTABLES:
         msrc = os.path.join(hdir, main)
         out = os.path.join(BIN, exe)
         if os.path.exists(msrc) and (force or _newer(out, deps + [msrc, HOST_LIB])):

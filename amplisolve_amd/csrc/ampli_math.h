@@ -10,6 +10,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "../../include/amplisolve_types.h"
+
 #if defined(__HIPCC__)
 #define AMPLI_FN __host__ __device__ __forceinline__
 #else
@@ -384,7 +386,7 @@ AMPLI_FN int ampli_prefilter_skip_f32(int32_t k, int32_t rd, float err_eff)
 // AMPLI_LIMIT_MAX_EVALS -- is AMPLI_LIMK_RECHECK: the host settles it with the literal scan (ampli_host_limit_reads).
 // One ampli_limit_step is ONE scorer evaluation, so that a kernel can run the steps of several strands in a single loop.
 // ---------------------------------------------------------------------------
-#define AMPLI_LIMIT_BAND 1e-6           // = AMPLI_CALL_GATE_EPS of include/amplisolve_hip.h
+#define AMPLI_LIMIT_BAND AMPLI_CALL_GATE_EPS // one band for the search and for the call list
 #define AMPLI_LIMIT_MAX_EVALS 128       // the longest walk seen on 200 000 random strands is 26 evaluations from floor(m) + 1
 #define AMPLI_LIMK_PENDING (-3)        // the search goes on
 #define AMPLI_LIMK_RECHECK (-2)        // not decided here
@@ -695,11 +697,6 @@ AMPLI_FN void ampli_power_lod(int32_t FW, int32_t k_fw, int32_t BW, int32_t k_bw
 // Returns the status: AMPLI_DISPERSION_FEW (n < 2 or K < 2: z = phi = 0), else AMPLI_DISPERSION_OK, with AMPLI_DISPERSION_HIGH
 // where z >= z_cutoff.  The finalize kernel and ampli_host_dispersion_cell_batch both run this text.
 // ---------------------------------------------------------------------------
-#ifndef AMPLI_DISPERSION_HIGH // also in include/amplisolve_hip.h, which this header does not need
-#define AMPLI_DISPERSION_OK 0
-#define AMPLI_DISPERSION_FEW 1
-#define AMPLI_DISPERSION_HIGH 0x40
-#endif
 AMPLI_FN uint8_t ampli_dispersion_cell(int32_t n, double K, double D, double x2, double rinv, double z_cutoff, double *z, float *phi)
 {
     *z = 0.0;
@@ -724,22 +721,6 @@ AMPLI_FN uint8_t ampli_dispersion_cell(int32_t n, double K, double D, double x2,
 // Returns the bits AMPLI_GENO_V | _A | _C | _G | _T (the base is HET or HOM) | _H (the position is a het); 0 unless VALID.  Bit k is
 // plane k of the device's uint64 planes[sample][6][W].  genotype_planes_kernel and ampli_host_genotype_classify_batch run this text.
 // ---------------------------------------------------------------------------
-#ifndef AMPLI_GENOTYPE_PARAMS_DEFINED // also in include/amplisolve_hip.h, which this header does not need
-#define AMPLI_GENOTYPE_PARAMS_DEFINED
-typedef struct ampli_genotype_params {
-    int32_t min_depth, absent_max_pm, het_min_pm, het_max_pm, hom_min_pm;
-} ampli_genotype_params;
-#define AMPLI_GENO_V 1
-#define AMPLI_GENO_A 2
-#define AMPLI_GENO_C 4
-#define AMPLI_GENO_G 8
-#define AMPLI_GENO_T 16
-#define AMPLI_GENO_H 32
-#define AMPLI_GENO_PLANES 6
-#define AMPLI_RELATION_UNDETERMINED 0
-#define AMPLI_RELATION_SAME 1
-#define AMPLI_RELATION_DIFFERENT 2
-#endif
 // min_depth >= 1 and 0 <= absent_max_pm < het_min_pm <= het_max_pm < hom_min_pm <= 1000
 AMPLI_FN int ampli_genotype_params_ok(const ampli_genotype_params *q)
 {
@@ -788,21 +769,6 @@ AMPLI_FN int ampli_concordance_relation(int32_t het_either, int32_t het_match, i
 // fraction and se are NaN where den == 0.  The status: UNDETERMINED while s0 + s3 < min_sites, else CONTAMINATED where
 // fraction >= min_fraction (never for a NaN), else CLEAN.
 // ---------------------------------------------------------------------------
-#ifndef AMPLI_CONTAM_SUMS // also in include/amplisolve_hip.h, which this header does not need
-#define AMPLI_CONTAM_SITES_HOM 0
-#define AMPLI_CONTAM_ALT_HOM 1
-#define AMPLI_CONTAM_DEPTH_HOM 2
-#define AMPLI_CONTAM_SITES_HET 3
-#define AMPLI_CONTAM_ALT_HET 4
-#define AMPLI_CONTAM_DEPTH_HET 5
-#define AMPLI_CONTAM_SITES_BG 6
-#define AMPLI_CONTAM_ALT_BG 7
-#define AMPLI_CONTAM_DEPTH_BG 8
-#define AMPLI_CONTAM_SUMS 9
-#define AMPLI_CONTAM_STATUS_UNDETERMINED 0
-#define AMPLI_CONTAM_STATUS_CLEAN 1
-#define AMPLI_CONTAM_STATUS_CONTAMINATED 2
-#endif
 AMPLI_FN int ampli_contamination_estimate(const int64_t s[AMPLI_CONTAM_SUMS], int64_t min_sites, double min_fraction, double *fraction, double *se,
                                           double *background)
 {
@@ -834,21 +800,6 @@ AMPLI_FN int ampli_contamination_estimate(const int64_t s[AMPLI_CONTAM_SUMS], in
 //   gene    GAIN if n >= min_amplicons, median ratio >= gain_ratio and median z >= z_cutoff; LOSS if n >= min_amplicons, median ratio
 //           <= loss_ratio and median z <= -z_cutoff; else NEUTRAL (a NaN median compares false: NEUTRAL)
 // ---------------------------------------------------------------------------
-#ifndef AMPLI_AMP_SUMS // also in include/amplisolve_hip.h, which this header does not need
-#define AMPLI_AMP_PRESENT 0
-#define AMPLI_AMP_DEPTH_FW 1
-#define AMPLI_AMP_DEPTH_BW 2
-#define AMPLI_AMP_CALLABLE 3
-#define AMPLI_AMP_SUMS 4
-#define AMPLI_AMPLICON_OK 0
-#define AMPLI_AMPLICON_FEW 1
-#define AMPLI_AMPLICON_DARK 2
-#define AMPLI_AMPLICON_MAX 4096
-#define AMPLI_AMPLICON_STRIP 8
-#define AMPLI_GENE_NEUTRAL 0
-#define AMPLI_GENE_GAIN 1
-#define AMPLI_GENE_LOSS 2
-#endif
 AMPLI_FN double ampli_amplicon_share(int64_t d, int64_t total) { return (double)d / (double)total; }
 
 AMPLI_FN double ampli_amplicon_median_pick(double lo, double hi, int64_t m)
@@ -935,39 +886,6 @@ AMPLI_FN int ampli_amplicon_gene_status(int64_t n, double median_ratio, double m
 //   96 channels  the classes below 64 folded onto a pyrimidine reference base (r in {A, G}: r' = 3 - r, l' = 3 - t, t' = 3 - l,
 //           y' = 3 - y), both strands summed: channel 16 sub + 4 l' + t', sub = (r' == T ? 3 : 0) + k' -- C>A C>G C>T T>A T>C T>G
 // ---------------------------------------------------------------------------
-#ifndef AMPLI_SPEC_SUMS // also in include/amplisolve_hip.h, which this header does not need
-#define AMPLI_SPEC_SITES 0
-#define AMPLI_SPEC_FW_A 1
-#define AMPLI_SPEC_FW_C 2
-#define AMPLI_SPEC_FW_G 3
-#define AMPLI_SPEC_FW_T 4
-#define AMPLI_SPEC_BW_A 5
-#define AMPLI_SPEC_BW_C 6
-#define AMPLI_SPEC_BW_G 7
-#define AMPLI_SPEC_BW_T 8
-#define AMPLI_SPEC_SUMS 9
-#define AMPLI_SPECTRUM_MAX_CLASSES 128
-#define AMPLI_SPECTRUM_STRIP 4
-#define AMPLI_SPECTRUM_SKIP 255
-#define AMPLI_SPECTRUM_CLASSES 68
-#define AMPLI_SPECTRUM_TYPES 13
-#define AMPLI_SPECTRUM_ALL 12
-#define AMPLI_SPECTRUM_CHANNELS 96
-#define AMPLI_SPECTRUM_OK 0
-#define AMPLI_SPECTRUM_LOW_SITES 1
-#define AMPLI_SPECTRUM_NO_REFERENCE 2
-#define AMPLI_SPECTRUM_ELEVATED 3
-#define AMPLI_SPECTRUM_ASYMMETRIC 4
-#define AMPLI_SPECTRUM_REF_OK 0
-#define AMPLI_SPECTRUM_REF_FEW 1
-#endif
-#ifndef AMPLI_SPECTRUM_PARAMS_DEFINED // also in include/amplisolve_host.h
-#define AMPLI_SPECTRUM_PARAMS_DEFINED
-typedef struct ampli_spectrum_params {
-    int64_t min_sites, min_normals;
-    double excess_ratio, z_cutoff, asym_delta;
-} ampli_spectrum_params;
-#endif
 
 // the gate of one record, without a branch on the data: every clause is evaluated and the results are and-ed
 AMPLI_FN int ampli_spectrum_enters(const int32_t fw[4], const int32_t bw[4], int present, uint32_t ref, uint32_t cls, int32_t C, int32_t cutoff,
@@ -1122,18 +1040,6 @@ AMPLI_FN void ampli_spectrum_score(const int64_t *alt, const int64_t *dep, const
 // normal reaches on both strands at once" is a different, far weaker rule and is not this one.)  A field is below 2^31 and a depth
 // below 2^33, min_vaf_pm at most 1000: no product leaves unsigned 64 bits.
 // ---------------------------------------------------------------------------
-#ifndef AMPLI_EXCEEDANCE_NA // also in include/amplisolve_hip.h, which this header does not need
-#define AMPLI_EXCEEDANCE_NA 0xFFFF
-#define AMPLI_EXCEEDANCE_MAX_NORMALS 65534
-#define AMPLI_EXCEEDANCE_STRIP 8
-#define AMPLI_EXCEEDANCE_ROWS 8
-#endif
-#ifndef AMPLI_EXCEEDANCE_PARAMS_DEFINED // also in include/amplisolve_host.h
-#define AMPLI_EXCEEDANCE_PARAMS_DEFINED
-typedef struct ampli_exceedance_params {
-    int64_t min_alt_reads, min_vaf_pm, min_normals, max_normals;
-} ampli_exceedance_params;
-#endif
 // every count >= 0 and min_vaf_pm at most 1000
 AMPLI_FN int ampli_exceedance_params_ok(const ampli_exceedance_params *q)
 {
@@ -1184,7 +1090,6 @@ AMPLI_FN int ampli_exceedance_candidate(uint64_t x_fw, uint64_t x_bw, uint64_t d
 // arithmetic, and on the samples tested the same bound, between 0 and 1e-8.
 // One ampli_nb_step is a short run of terms, so that a kernel runs the tails of a lane in a single loop (as ampli_tail_step).
 // ---------------------------------------------------------------------------
-#define AMPLI_NB_NA (-1.0f) // also in include/amplisolve_hip.h, token for token and unguarded: a copy that drifts is a macro redefinition
 #define AMPLI_NB_POISSON_BELOW 1e-290
 #define AMPLI_NB_EPS 1e-9
 #define AMPLI_NB_EPS_DOWN 1e-18
@@ -1371,7 +1276,6 @@ AMPLI_FN float ampli_nb_score(int32_t k, int32_t d, float e, double w, int32_t *
 //     a tail that would need more is a NaN and its score AMPLI_PAIR_NA, not a wrong number.
 // One ampli_hyper_step is AMPLI_TAIL_RUN terms, so that a kernel runs all of a lane's cells in a single loop (as ampli_nb_step).
 // ---------------------------------------------------------------------------
-#define AMPLI_PAIR_NA (-999.0f) // also in include/amplisolve_hip.h, token for token and unguarded: a copy that drifts is a macro redefinition
 #define AMPLI_HYPER_EPS 1e-9
 #define AMPLI_HYPER_MAX_TERMS (1 << 20)  // of one sum: the loop's own bound
 #define AMPLI_HYPER_TERMS(var) (8.0 * sqrt(var) + 64.0)
@@ -1472,7 +1376,6 @@ AMPLI_FN float ampli_pair_score(int64_t k_a, int64_t d_a, int64_t k_b, int64_t d
 // A = 0 (-0 never), AMPLI_FDR_NA where untested.  Rounding to float is monotone, so the running maximum may be taken over
 // (float)B: max and rounding commute, and max(0, .) with them.
 // ---------------------------------------------------------------------------
-#define AMPLI_FDR_NA (-999.0f) // also in include/amplisolve_hip.h, token for token and unguarded: a copy that drifts is a macro redefinition
 #define AMPLI_FDR_UNTESTED 0
 #define AMPLI_FDR_ZERO 1
 #define AMPLI_FDR_PLUS 2
@@ -1534,24 +1437,7 @@ AMPLI_FN float ampli_fdr_store(int cls, float bmax)
 //     when a row is outside its chunk, a keep is above 2^32, row_b >= 0 without a chunk b, or row_b < -1.
 //   Fractions to thresholds.  keep = (uint64) floor(ldexp(x, 32) + 0.5), x a double in [0, 1]: IEEE operations, the same everywhere.
 // ------------------------------------------------------------------------------------------------------------------------------------
-#ifndef AMPLI_DILUTE_MIX_DEFINED // also in include/amplisolve_hip.h and include/amplisolve_host.h
-#define AMPLI_DILUTE_MIX_DEFINED
-typedef struct ampli_dilute_mix {
-    int32_t row_a, row_b;
-    uint64_t keep_a, keep_b, key;
-} ampli_dilute_mix;
-#define AMPLI_DILUTE_BAD_COUNT 1
-#define AMPLI_DILUTE_BAD_MIXTURE 2
-#define AMPLI_DILUTE_MAX_COUNT 16777214 /* 2^24 - 2 */
-#endif
 #define AMPLI_DILUTE_KEEP_ALL 4294967296ull // 2^32
-#ifdef __cplusplus // whichever of the three copies came first, this is the layout the kernel, the host library and the bindings share
-#include <stddef.h>
-static_assert(sizeof(ampli_dilute_mix) == 32 && offsetof(ampli_dilute_mix, row_a) == 0 && offsetof(ampli_dilute_mix, row_b) == 4 &&
-                  offsetof(ampli_dilute_mix, keep_a) == 8 && offsetof(ampli_dilute_mix, keep_b) == 16 && offsetof(ampli_dilute_mix, key) == 24,
-              "ampli_dilute_mix is {int32 row_a; int32 row_b; uint64 keep_a; uint64 keep_b; uint64 key}, 32 bytes");
-static_assert(AMPLI_DILUTE_BAD_COUNT == 1 && AMPLI_DILUTE_BAD_MIXTURE == 2 && AMPLI_DILUTE_MAX_COUNT == (1 << 24) - 2, "the flag bits and the count range");
-#endif
 
 AMPLI_FN void ampli_philox4x32_10(const uint32_t ctr[4], const uint32_t key[2], uint32_t out[4])
 {

@@ -1,6 +1,6 @@
-// amplisolve_amd/csrc/host/command.hpp -- what the project's own thirteen commands (run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp,
-// run_ct.cpp, run_ac.cpp, run_ss.cpp, run_ex.cpp, run_od.cpp, run_pc.cpp, run_fd.cpp, run_di.cpp) share: how a value is parsed and refused, the frame of a command, its inputs, the two
-// ways a cohort goes over the device (streamed, resident) and how the files are written.  command.cpp; internal to those files.
+// amplisolve_amd/csrc/host/command.hpp -- what the project's own commands (every run_*.cpp but run_ee.cpp / run_vc.cpp) share: how a
+// value is parsed and refused, the frame of a command, its inputs, the two ways a cohort goes over the device (streamed, resident)
+// and how the files are written.  command.cpp; internal to those files.
 #pragma once
 #include <climits>
 #include <initializer_list>

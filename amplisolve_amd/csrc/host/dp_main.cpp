@@ -2,28 +2,14 @@
 // in the reference's key=value style.
 //   AmpliSolveDetectionPower errorFile=<table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<int> levels=<f>[,<f>...] confidence=<f>
 // Exactly 6 tokens in this order.  Not a drop-in: the exit status is 0 on success and 1 on any failure.
-#include <clocale>
-#include <cstdlib>
-
-#include "host.hpp"
 #include "main_args.hpp"
 
-using ampli::token;
+using A = ampli::DpArgs;
 
-int main(int argc, char **argv)
-{
-    setlocale(LC_ALL, "");
-    if (argc != 7) {
-        std::cout << "Usage:\n\tAmpliSolveDetectionPower errorFile=<error table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<int> "
-                     "levels=<float>[,<float>...] confidence=<0.5 .. 0.99>\n\tAll arguments are required, in this order." << std::endl;
-        return 1;
-    }
-    ampli::DpArgs a;
-    a.error_file = token(argv[1], "errorFile");
-    a.tumour_dir = token(argv[2], "tumour_dir");
-    a.output_dir = token(argv[3], "output_dir");
-    a.coverage_cutoff = token(argv[4], "coverage_cutoff");
-    a.levels = token(argv[5], "levels");
-    a.confidence = token(argv[6], "confidence");
-    return ampli::finish(ampli::run_detection_power(a));
-}
+static const char USAGE[] = "Usage:\n\tAmpliSolveDetectionPower errorFile=<error table> tumour_dir=<dir> output_dir=<dir> coverage_cutoff=<int> "
+                            "levels=<float>[,<float>...] confidence=<0.5 .. 0.99>\n\tAll arguments are required, in this order.";
+
+static const ampli::KeyArg<A> KEYS[] = {{"errorFile", &A::error_file}, {"tumour_dir", &A::tumour_dir}, {"output_dir", &A::output_dir},
+                                        {"coverage_cutoff", &A::coverage_cutoff}, {"levels", &A::levels}, {"confidence", &A::confidence}};
+
+int main(int argc, char **argv) { return ampli::command_main(argc, argv, USAGE, KEYS, ampli::run_detection_power); }

@@ -216,8 +216,8 @@ void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // without the static destructors and atexit handlers of the HIP runtime (queue / signal / pool teardown that only serves a
 // process that lives on; the driver reclaims everything at exit either way).  AMPLISOLVE_EXIT=orderly returns instead.
 void finish_process(int status);
-// ---- run_ee.cpp, run_vc.cpp, and the project's own commands: run_loo.cpp, run_dl.cpp, run_dp.cpp, run_pd.cpp, run_sc.cpp, run_ct.cpp,
-// run_ac.cpp, run_ss.cpp, run_ex.cpp (what those nine share: command.hpp) ----
+// ---- run_ee.cpp, run_vc.cpp, and the project's own commands: every other run_*.cpp (what those share: command.hpp; their
+// main(): command_main of main_args.hpp over the Args struct's fields) ----
 int run_error_estimation(const EeArgs &a);
 int run_variant_calling(const VcArgs &a);
 // AmpliSolveLeaveOneOut (loo_main.cpp): C_value is one value or a comma-separated list; exit status 0 / 1

@@ -42,6 +42,8 @@
 #include <stddef.h>
 #include <stdint.h>
 
+#include "amplisolve_types.h" /* the AMPLI_* constants and parameter structs named below that the host library shares */
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -442,8 +444,7 @@ typedef struct ampli_call {
  * the device.  Such (record, alternative) pairs are put on the call list EITHER WAY with AMPLI_CALL_BORDERLINE set; the mask
  * bit follows the device's own value, and the host re-evaluates the pair with the reference's operation sequence before it
  * writes anything (csrc/host/annotate.cpp: score_reference_sequence).  None occurs on Toy_data or the synthetic panels. */
-#define AMPLI_CALL_BORDERLINE 1
-#define AMPLI_CALL_GATE_EPS 1e-6
+#define AMPLI_CALL_BORDERLINE 1 /* the distance: AMPLI_CALL_GATE_EPS of amplisolve_types.h */
 
 #define AMPLI_CALL_SHARDS 32
 #define AMPLI_CALL_COUNTER_STRIDE 16 /* uint64 words between shard counters: one 128-byte line each */
@@ -607,9 +608,6 @@ int ampli_power_stats(ampli_ctx *ctx, uint64_t out[3], int32_t reset);
  * to: cells OK | cells FEW | cells HIGH | positions with a HIGH cell.
  * No floating-point atomics: the same inputs in the same chunks give the same bytes.  Asynchronous on the context's stream.
  */
-#define AMPLI_DISPERSION_OK 0
-#define AMPLI_DISPERSION_FEW 1
-#define AMPLI_DISPERSION_HIGH 0x40
 int ampli_dispersion_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_acc_table *d_acc0, int32_t coverage_cutoff,
                              double *d_x2, double *d_rinv, int32_t accumulate, double *d_sample_x2, double *d_sample_expect,
                              int64_t *d_sample_terms);
@@ -638,22 +636,6 @@ int ampli_dispersion_finalize(ampli_ctx *ctx, int64_t P, const ampli_acc_table *
  * Integers only: the same inputs give the same bytes.  Both are asynchronous on the context's stream.  The relation of a pair is
  * decided on the host (ampli_host_concordance_relation, include/amplisolve_host.h).
  */
-#ifndef AMPLI_GENOTYPE_PARAMS_DEFINED /* also in csrc/ampli_math.h */
-#define AMPLI_GENOTYPE_PARAMS_DEFINED
-typedef struct ampli_genotype_params {
-    int32_t min_depth, absent_max_pm, het_min_pm, het_max_pm, hom_min_pm;
-} ampli_genotype_params;
-#define AMPLI_GENO_V 1
-#define AMPLI_GENO_A 2
-#define AMPLI_GENO_C 4
-#define AMPLI_GENO_G 8
-#define AMPLI_GENO_T 16
-#define AMPLI_GENO_H 32
-#define AMPLI_GENO_PLANES 6
-#define AMPLI_RELATION_UNDETERMINED 0
-#define AMPLI_RELATION_SAME 1
-#define AMPLI_RELATION_DIFFERENT 2
-#endif
 int64_t ampli_concordance_words(int64_t P);
 int ampli_genotype_planes_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_genotype_params *prm, uint64_t *d_planes);
 int ampli_concordance_pairs(ampli_ctx *ctx, int64_t P, const uint64_t *d_planes_a, int32_t n_a, const uint64_t *d_planes_b, int32_t n_b,
@@ -680,21 +662,6 @@ int ampli_concordance_pairs(ampli_ctx *ctx, int64_t P, const uint64_t *d_planes_
  * same inputs give the same bytes.  Asynchronous on the context's stream.  The estimate and the status of a pair are decided on the
  * host (ampli_host_contamination_estimate, include/amplisolve_host.h).
  */
-#ifndef AMPLI_CONTAM_SUMS /* also in csrc/ampli_math.h */
-#define AMPLI_CONTAM_SITES_HOM 0
-#define AMPLI_CONTAM_ALT_HOM 1
-#define AMPLI_CONTAM_DEPTH_HOM 2
-#define AMPLI_CONTAM_SITES_HET 3
-#define AMPLI_CONTAM_ALT_HET 4
-#define AMPLI_CONTAM_DEPTH_HET 5
-#define AMPLI_CONTAM_SITES_BG 6
-#define AMPLI_CONTAM_ALT_BG 7
-#define AMPLI_CONTAM_DEPTH_BG 8
-#define AMPLI_CONTAM_SUMS 9
-#define AMPLI_CONTAM_STATUS_UNDETERMINED 0
-#define AMPLI_CONTAM_STATUS_CLEAN 1
-#define AMPLI_CONTAM_STATUS_CONTAMINATED 2
-#endif
 int ampli_contamination_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint64_t *d_planes_a, const uint64_t *d_planes_b,
                                 int32_t n_b, int64_t *d_sums);
 
@@ -738,21 +705,6 @@ int ampli_contamination_records(ampli_ctx *ctx, const ampli_records *recs, int64
  *   d_total int64 [S], d_centre double [S], d_k int32 [S], d_ratio, d_z double [S][A]: FULLY OVERWRITTEN (C15).
  * AMPLI_E_INVALID as above; AMPLI_E_RANGE: A > AMPLI_AMPLICON_MAX.  Both are asynchronous on the context's stream.
  */
-#ifndef AMPLI_AMP_SUMS /* also in csrc/ampli_math.h */
-#define AMPLI_AMP_PRESENT 0
-#define AMPLI_AMP_DEPTH_FW 1
-#define AMPLI_AMP_DEPTH_BW 2
-#define AMPLI_AMP_CALLABLE 3
-#define AMPLI_AMP_SUMS 4
-#define AMPLI_AMPLICON_OK 0
-#define AMPLI_AMPLICON_FEW 1
-#define AMPLI_AMPLICON_DARK 2
-#define AMPLI_AMPLICON_MAX 4096 /* N of amplicon_reference, A of amplicon_ratio: 32 KB of LDS */
-#define AMPLI_AMPLICON_STRIP 8  /* rows per wave of amplicon_depth_kernel */
-#define AMPLI_GENE_NEUTRAL 0
-#define AMPLI_GENE_GAIN 1
-#define AMPLI_GENE_LOSS 2
-#endif
 int ampli_amplicon_depth_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, int32_t A, const uint32_t *d_amp_off,
                                  const uint32_t *d_amp_pos, int64_t W, int32_t coverage_cutoff, int64_t *d_sums);
 int ampli_amplicon_reference(ampli_ctx *ctx, const int64_t *d_sums, int32_t N, int32_t A, const uint8_t *d_use, int32_t min_normals,
@@ -789,32 +741,6 @@ int ampli_amplicon_ratio(ampli_ctx *ctx, const int64_t *d_sums, int32_t S, int32
  * (as ampli_last_reduce_kernel; AMPLI_E_INVALID before the first).  Integers only: the same inputs give the same bytes, whatever
  * the order the segments arrive in.  Asynchronous on the context's stream.
  */
-#ifndef AMPLI_SPEC_SUMS /* also in csrc/ampli_math.h */
-#define AMPLI_SPEC_SITES 0
-#define AMPLI_SPEC_FW_A 1
-#define AMPLI_SPEC_FW_C 2
-#define AMPLI_SPEC_FW_G 3
-#define AMPLI_SPEC_FW_T 4
-#define AMPLI_SPEC_BW_A 5
-#define AMPLI_SPEC_BW_C 6
-#define AMPLI_SPEC_BW_G 7
-#define AMPLI_SPEC_BW_T 8
-#define AMPLI_SPEC_SUMS 9
-#define AMPLI_SPECTRUM_MAX_CLASSES 128
-#define AMPLI_SPECTRUM_STRIP 4    /* rows per workgroup of spectrum_kernel */
-#define AMPLI_SPECTRUM_SKIP 255
-#define AMPLI_SPECTRUM_CLASSES 68 /* the command line's classes: 64 trinucleotide contexts and 4 edge classes */
-#define AMPLI_SPECTRUM_TYPES 13   /* twelve strand-resolved substitution types and ALL */
-#define AMPLI_SPECTRUM_ALL 12
-#define AMPLI_SPECTRUM_CHANNELS 96
-#define AMPLI_SPECTRUM_OK 0
-#define AMPLI_SPECTRUM_LOW_SITES 1
-#define AMPLI_SPECTRUM_NO_REFERENCE 2
-#define AMPLI_SPECTRUM_ELEVATED 3
-#define AMPLI_SPECTRUM_ASYMMETRIC 4
-#define AMPLI_SPECTRUM_REF_OK 0
-#define AMPLI_SPECTRUM_REF_FEW 1
-#endif
 int ampli_spectrum_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint8_t *d_ref_code, const uint8_t *d_class, int32_t C,
                            int32_t coverage_cutoff, int32_t max_alt_pm, int64_t *d_sums);
 int ampli_last_spectrum_segments(const ampli_ctx *ctx);
@@ -853,12 +779,6 @@ int ampli_last_spectrum_segments(const ampli_ctx *ctx);
  * the accumulate form is a plain read-modify-write, there are no atomics and the bytes are the same in any launch order.
  * Integers only.  Asynchronous on the context's stream.
  */
-#ifndef AMPLI_EXCEEDANCE_NA /* also in csrc/ampli_math.h */
-#define AMPLI_EXCEEDANCE_NA 0xFFFF
-#define AMPLI_EXCEEDANCE_MAX_NORMALS 65534
-#define AMPLI_EXCEEDANCE_STRIP 8 /* normal rows decoded into LDS at a time */
-#define AMPLI_EXCEEDANCE_ROWS 8  /* tumour rows per workgroup of exceedance_kernel */
-#endif
 int ampli_exceedance_records(ampli_ctx *ctx, const ampli_records *recs_t, const ampli_records *recs_n, int64_t P, const uint8_t *d_ref_code,
                              int32_t normal_cutoff, int32_t calling_cutoff, int64_t first_t, int64_t first_n, int32_t skip_same_index,
                              int32_t accumulate, uint16_t *d_elig, uint16_t *d_ge);
@@ -906,7 +826,6 @@ int ampli_exceedance_records(ampli_ctx *ctx, const ampli_records *recs_t, const 
  * order); the score kernel gives a wave one tumour row of a tile, a lane a position, and walks the lane's six cells in one loop.
  * Asynchronous on the context's stream.
  */
-#define AMPLI_NB_NA (-1.0f) /* also in csrc/ampli_math.h, token for token and unguarded: a copy that drifts is a macro redefinition */
 int ampli_overdispersion_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const ampli_acc_table *d_acc0, int32_t coverage_cutoff,
                                  double *d_s2, int32_t accumulate);
 int ampli_overdispersion_finalize(ampli_ctx *ctx, int64_t P, const ampli_acc_table *d_acc0, const double *d_x2, const double *d_s2,
@@ -942,7 +861,6 @@ int ampli_nb_score_records(ampli_ctx *ctx, const ampli_records *trecs, int64_t P
  * The form: a wave owns one pair of a 64-position tile, a lane a position, and walks the lane's six cells in one loop.  Asynchronous on
  * the context's stream.
  */
-#define AMPLI_PAIR_NA (-999.0f) /* also in csrc/ampli_math.h, token for token and unguarded: a copy that drifts is a macro redefinition */
 int ampli_pair_score_records(ampli_ctx *ctx, const ampli_records *recs_a, const ampli_records *recs_b, int64_t P,
                              const int32_t *d_pairs /* [n_pairs][2]: row in a, row in b */, int32_t n_pairs,
                              const uint8_t *d_ref_code, int32_t depth_cutoff, float *d_s /* [n_pairs][P][4][2] */);
@@ -981,7 +899,6 @@ int ampli_pair_score_records(ampli_ctx *ctx, const ampli_records *recs_a, const 
  * (blocks of AMPLI_FDR_SCAN_BLOCK, whose totals one workgroup per row walks AMPLI_FDR_SCAN_BLOCK at a time); a binary search per cell.
  * No workgroup waits for another.  Asynchronous on the context's stream: m_r is read from device memory, nothing synchronises.
  */
-#define AMPLI_FDR_NA (-999.0f) /* also in csrc/ampli_math.h, token for token and unguarded: a copy that drifts is a macro redefinition */
 #define AMPLI_FDR_TILE_KEYS 4096 /* keys of one sort tile: 1024 positions */
 #define AMPLI_FDR_SCAN_BLOCK 512 /* elements of one scan block; one second-level step covers 512 * 512 keys = 65536 positions */
 size_t ampli_fdr_workspace_bytes(int32_t rows, int64_t P);
@@ -1026,16 +943,6 @@ int ampli_fdr_adjust(ampli_ctx *ctx, const float *d_s /* [rows][P][4][2] */, int
  * stored.  The 16 (side, field) lists of a record are walked one after the other (DESIGN 22 measures the alternative).  Asynchronous
  * on the context's stream.
  */
-#ifndef AMPLI_DILUTE_MIX_DEFINED /* also in csrc/ampli_math.h and include/amplisolve_host.h */
-#define AMPLI_DILUTE_MIX_DEFINED
-typedef struct ampli_dilute_mix {
-    int32_t row_a, row_b;
-    uint64_t keep_a, keep_b, key;
-} ampli_dilute_mix;
-#define AMPLI_DILUTE_BAD_COUNT 1
-#define AMPLI_DILUTE_BAD_MIXTURE 2
-#define AMPLI_DILUTE_MAX_COUNT 16777214 /* 2^24 - 2 */
-#endif
 int ampli_dilute_records(ampli_ctx *ctx, const ampli_records *recs_a, const ampli_records *recs_b /* may be NULL */, int64_t P,
                          const ampli_dilute_mix *d_mix /* [n_mix] */, int32_t n_mix, int32_t *d_out /* [n_mix][P][8] */,
                          int32_t *d_flags /* [n_mix] */);

@@ -16,6 +16,7 @@
 #define AMPLISOLVE_HOST_H
 #include <stddef.h>
 #include <stdint.h>
+#include "amplisolve_types.h"
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -192,22 +193,21 @@ void ampli_host_dispersion_cell_batch(const int32_t *n, const double *K, const d
                                       double z_cutoff, double *z, float *phi, uint8_t *status);
 
 /* Sample identity: the genotype of `count` records (int32 [count][8], absent: field 0 == INT32_MIN) as the six plane bits
- * AMPLI_GENO_V | _A | _C | _G | _T | _H of include/amplisolve_hip.h -- csrc/ampli_math.h's ampli_genotype_classify, what
+ * AMPLI_GENO_V | _A | _C | _G | _T | _H of include/amplisolve_types.h -- csrc/ampli_math.h's ampli_genotype_classify, what
  * genotype_planes_kernel runs.  Returns 0, or AMPLI_E_INVALID (-1) with nothing written when prm breaks its inequalities. */
-struct ampli_genotype_params; /* include/amplisolve_hip.h */
 int ampli_host_genotype_classify_batch(const int32_t *recs, int64_t count, const struct ampli_genotype_params *prm, uint8_t *bits);
 /* the relation of a pair of samples from two of its counts: AMPLI_RELATION_UNDETERMINED when het_either < min_sites, else _SAME when
  * (double)het_match >= same_fraction * (double)het_either, else _DIFFERENT */
 int ampli_host_concordance_relation(int32_t het_either, int32_t het_match, int32_t min_sites, double same_fraction);
 /* Cross-sample contamination: fraction, its standard error and the background rate e of one ordered pair from its nine
- * sums (order AMPLI_CONTAM_* of include/amplisolve_hip.h) -- csrc/ampli_math.h's ampli_contamination_estimate, in double, unfused.
+ * sums (order AMPLI_CONTAM_* of include/amplisolve_types.h) -- csrc/ampli_math.h's ampli_contamination_estimate, in double, unfused.
  * fraction and se are NaN where the pair has no depth on an informative site; any of the three pointers may be NULL.  Returns
  * AMPLI_CONTAM_STATUS_UNDETERMINED when sites_hom + sites_het < min_sites, else _CONTAMINATED when fraction >= min_fraction, else
  * _CLEAN; AMPLI_E_INVALID (-1) when sums is NULL. */
 int ampli_host_contamination_estimate(const int64_t *sums, int64_t min_sites, double min_fraction, double *fraction, double *se, double *background);
 /* Amplicon copy ratio: csrc/ampli_math.h's functions, in double, unfused.  _median: the median of the m values of v that
  * are not NaN (signed values; v is not changed), NaN if there is none or v is NULL.  _z: mad > 0 ? ((ratio - 1.0) * med) / (1.4826 * mad)
- * : NaN.  _share: (double)d / (double)total.  _gene_status: AMPLI_GENE_GAIN / _LOSS / _NEUTRAL (include/amplisolve_hip.h). */
+ * : NaN.  _share: (double)d / (double)total.  _gene_status: AMPLI_GENE_GAIN / _LOSS / _NEUTRAL (include/amplisolve_types.h). */
 double ampli_host_amplicon_median(const double *v, int64_t m);
 /* the BED rows (with the amplicon id of column 4 and the gene of column 6, "." where missing) and the position index of a panel as text,
  * for tests: "R chrom start end name gene" per row, "W" + the walk, "D" + the dup flags, "P" + chrom:coord per position.  Returns the
@@ -228,15 +228,8 @@ int ampli_host_amplicon_gene_status(int64_t n, double median_ratio, double media
  *   is ALL), sites int64 [S][13] and the 96 channels ctx_alt, ctx_dep int64 [S][96] (both may be NULL).
  * _score: the reference from the first N samples (the normals) and the score of all S: ref double [13][4] = med, mad, med_a, mad_a;
  *   n_eff int32 [13]; status uint8 [13] (AMPLI_SPECTRUM_REF_*); rate2, ratio, z, asym, za double [S][13]; flag uint8 [S][13]
- *   (AMPLI_SPECTRUM_OK, _LOW_SITES, _NO_REFERENCE, _ELEVATED, _ASYMMETRIC of include/amplisolve_hip.h).  Returns 0, or AMPLI_E_INVALID
+ *   (AMPLI_SPECTRUM_OK, _LOW_SITES, _NO_REFERENCE, _ELEVATED, _ASYMMETRIC of include/amplisolve_types.h).  Returns 0, or AMPLI_E_INVALID
  *   for a null pointer, S <= 0 or N outside [0, S]. */
-#ifndef AMPLI_SPECTRUM_PARAMS_DEFINED /* also in csrc/ampli_math.h */
-#define AMPLI_SPECTRUM_PARAMS_DEFINED
-typedef struct ampli_spectrum_params {
-    int64_t min_sites, min_normals;
-    double excess_ratio, z_cutoff, asym_delta;
-} ampli_spectrum_params;
-#endif
 int ampli_host_spectrum_enters_batch(const int32_t *recs, int64_t count, const uint8_t *ref_code, const uint8_t *cls, int32_t C, int32_t coverage_cutoff,
                                      int32_t max_alt_pm, uint8_t *enters);
 int ampli_host_spectrum_class(int32_t r, int32_t l, int32_t t);
@@ -252,12 +245,6 @@ int ampli_host_spectrum_score(const int64_t *alt, const int64_t *dep, const int6
  * x[0] >= min_alt_reads and x[1] >= min_alt_reads, 1000 (x[0] + x[1]) >= min_vaf_pm (depth[0] + depth[1]), elig >= min_normals, and
  * ge[0] <= max_normals and ge[1] <= max_normals: the per-strand rule.  Returns 0, or AMPLI_E_INVALID (-1) with nothing written for a
  * null pointer, count < 0, a negative parameter or min_vaf_pm above 1000. */
-#ifndef AMPLI_EXCEEDANCE_PARAMS_DEFINED /* also in csrc/ampli_math.h */
-#define AMPLI_EXCEEDANCE_PARAMS_DEFINED
-typedef struct ampli_exceedance_params {
-    int64_t min_alt_reads, min_vaf_pm, min_normals, max_normals;
-} ampli_exceedance_params;
-#endif
 int ampli_host_exceedance_candidate_batch(const uint64_t *x, const uint64_t *depth, const uint16_t *elig, const uint16_t *ge, int64_t count,
                                           const ampli_exceedance_params *prm, uint8_t *candidate);
 
@@ -309,16 +296,6 @@ int ampli_host_fdr_rows(const float *s, int32_t rows, int64_t P, int32_t two_sid
  *   when there is no chunk b) [n_b][stride_b][8], strides in records (0 = P), of which the first P records of a row enter; mix [n_mix];
  *   out int32 [n_mix][P][8] and flags int32 [n_mix], both fully overwritten.  Returns 0, or AMPLI_E_INVALID (-1) with nothing written
  *   for a null pointer other than recs_b, P <= 0, n_mix < 1, n_a < 1, n_b < 0, a stride below P, AMPLI_E_RANGE (-6) for P >= 2^31. */
-#ifndef AMPLI_DILUTE_MIX_DEFINED /* also in csrc/ampli_math.h and include/amplisolve_hip.h */
-#define AMPLI_DILUTE_MIX_DEFINED
-typedef struct ampli_dilute_mix {
-    int32_t row_a, row_b;
-    uint64_t keep_a, keep_b, key;
-} ampli_dilute_mix;
-#define AMPLI_DILUTE_BAD_COUNT 1
-#define AMPLI_DILUTE_BAD_MIXTURE 2
-#define AMPLI_DILUTE_MAX_COUNT 16777214 /* 2^24 - 2 */
-#endif
 void ampli_host_philox4x32_10(const uint32_t *ctr, const uint32_t *key, uint32_t *out);
 int64_t ampli_host_thin(int64_t n, uint64_t keep, uint64_t key, uint32_t p, int32_t field, int32_t side);
 uint64_t ampli_host_dilute_keep(double x);

@@ -32,10 +32,13 @@ def host_fdr(s, two_sided, rank=True):
 def test_the_header_states_the_constants_the_tests_use():
     hip = open(os.path.join(ROOT, "include", "amplisolve_hip.h")).read()
     math = open(os.path.join(ROOT, "amplisolve_amd", "csrc", "ampli_math.h")).read()
+    types = open(os.path.join(ROOT, "include", "amplisolve_types.h")).read()
     assert int(re.search(r"#define AMPLI_FDR_TILE_KEYS (\d+)", hip).group(1)) == fp.TILE_KEYS
     assert int(re.search(r"#define AMPLI_FDR_SCAN_BLOCK (\d+)", hip).group(1)) == fp.SCAN_BLOCK
-    na = [re.search(r"#define AMPLI_FDR_NA (\S+)", t).group(1) for t in (hip, math)]
-    assert na[0] == na[1] == "(-999.0f)"
+    # one definition, in the header that the other two include
+    assert [m.group(1) for m in re.finditer(r"#\s*define\s+AMPLI_FDR_NA\s+(\S+)", types)] == ["(-999.0f)"]
+    for t in (hip, math):
+        assert not re.search(r"#\s*define\s+AMPLI_FDR_NA\b", t) and "amplisolve_types.h" in t
     assert "(C20)" in hip and "ampli_fdr_adjust" in hip and "ampli_fdr_workspace_bytes" in hip
 
 
