@@ -101,7 +101,8 @@ extern "C" int ampli_roundtrip_batch(ampli_ctx *ctx, const float *d_in, int64_t 
 extern "C" int ampli_synth_fill(ampli_ctx *ctx, int32_t *d_recs, int64_t P, int32_t n_samples, int32_t first_sample,
                                 uint64_t seed, int32_t depth, int32_t tumour)
 {
-    if (!ctx || !d_recs || P <= 0 || n_samples <= 0 || n_samples > 65535 || depth <= 0) return AMPLI_E_INVALID; // n_samples = gridDim.y
+    if (!ctx || !d_recs || P <= 0 || n_samples <= 0 || depth <= 0) return AMPLI_E_INVALID;
+    if (n_samples > 65535) return fail(ctx, AMPLI_E_RANGE, "synth_fill: more than 65535 samples in one call (grid limit); fill the panel in parts"); // n_samples = gridDim.y
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipLaunchKernelGGL(synth_fill_kernel, dim3((unsigned)((P + 255) / 256), (unsigned)n_samples), dim3(256), 0, main_stream(ctx),
                        (int4 *)d_recs, (long long)P, (int)n_samples, (int)first_sample, (unsigned long long)seed, (int)depth, (int)tumour);

@@ -193,7 +193,7 @@ extern "C" int ampli_concordance_pairs(ampli_ctx *ctx, int64_t P, const uint64_t
         return fail(ctx, AMPLI_E_INVALID, "concordance_pairs: bad argument (P > 0, n_a > 0, n_b > 0, 8-byte aligned planes, 4-byte aligned d_counts)");
     if (P >= 0x7FFFFFFFll) return fail(ctx, AMPLI_E_RANGE, "concordance_pairs: P must be below 2^31 (the counts are int32)");
     const long long ta = ((long long)n_a + CP_TA - 1) / CP_TA, tb = ((long long)n_b + CP_TB - 1) / CP_TB;
-    if (ta > 65535) return fail(ctx, AMPLI_E_RANGE, "concordance_pairs: n_a must be below 2097120");
+    if (ta > 65535) return fail(ctx, AMPLI_E_RANGE, "concordance_pairs: n_a must be at most 2097120");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t st = main_stream(ctx);
     const int symmetric = d_planes_a == d_planes_b && n_a == n_b;

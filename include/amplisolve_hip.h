@@ -1009,7 +1009,8 @@ int ampli_roundtrip_batch(ampli_ctx *ctx, const float *d_in, int64_t n, float *d
 
 /* deterministic synthetic panel generated in HBM: fills recs[n_samples][P][8]
  * for samples [first_sample, first_sample+n_samples) of panel `seed`; tumour != 0 spikes SNVs.
- * Bit-identical to ampli_synth_record() on the host (amplisolve_amd/csrc/ampli_synth.h). */
+ * Bit-identical to ampli_synth_record() on the host (amplisolve_amd/csrc/ampli_synth.h).
+ * n_samples > 65535 is AMPLI_E_RANGE (one grid row per sample): fill a larger panel in parts. */
 int ampli_synth_fill(ampli_ctx *ctx, int32_t *d_recs, int64_t P, int32_t n_samples,
                      int32_t first_sample, uint64_t seed, int32_t depth, int32_t tumour);
 int ampli_synth_ref(ampli_ctx *ctx, uint8_t *d_ref_code, int64_t P, uint64_t seed);
