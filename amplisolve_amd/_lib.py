@@ -52,6 +52,11 @@ class DiluteMix(C.Structure):
     _fields_ = [("row_a", i32), ("row_b", i32), ("keep_a", u64), ("keep_b", u64), ("key", u64)]
 
 
+class MonitorParams(C.Structure):
+    """mirror of ampli_monitor_params: the gates of an evaluated entry of the monitoring sums"""
+    _fields_ = [("coverage_cutoff", i32), ("max_vaf_pm", i32)]
+
+
 # every symbol include/amplisolve_hip.h declares: (restype, argtypes)
 HIP_SYMBOLS = {
     "ampli_abi_version": (C.c_int, []),
@@ -166,6 +171,10 @@ HIP_SYMBOLS = {
     "ampli_fdr_workspace_bytes": (C.c_size_t, [i32, i64]),
     "ampli_fdr_adjust": (C.c_int, [vp, vp, i32, i64, i32, vp, C.c_size_t, vp, vp, vp]),
     "ampli_dilute_records": (C.c_int, [vp, C.POINTER(Records), C.POINTER(Records), i64, vp, i32, vp, vp]),
+    "ampli_monitor_sums_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, vp, vp, i32, i64, C.POINTER(MonitorParams), vp, vp]),
+    "ampli_monitor_control_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, vp, vp, i32, i64, vp, i32, vp, vp, i64, i32, i32, u64,
+                                                C.POINTER(MonitorParams), vp, vp]),
+    "ampli_monitor_score": (C.c_int, [vp, vp, vp, i64, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -274,6 +283,17 @@ HOST_SYMBOLS = {
     "ampli_host_thin": (i64, [i64, u64, u64, C.c_uint32, i32, i32]),
     "ampli_host_dilute_keep": (u64, [C.c_double]),
     "ampli_host_dilute_records": (C.c_int, [vp, i32, i64, vp, i32, i64, i64, vp, i32, vp, vp]),
+    "ampli_host_monitor_sums": (C.c_int, [vp, i32, i64, i64, vp, vp, vp, vp, i32, i64, C.POINTER(MonitorParams), vp, vp]),
+    "ampli_host_monitor_controls": (C.c_int, [vp, i32, i64, i64, vp, vp, vp, vp, i32, i64, vp, i32, vp, vp, i64, i32, i32, u64,
+                                              C.POINTER(MonitorParams), vp, vp]),
+    "ampli_host_monitor_score": (C.c_int, [vp, vp, i64, vp]),
+    "ampli_host_monitor_control_draw": (C.c_uint32, [C.c_uint32, C.c_uint32, C.c_uint32, u64, C.c_uint32]),
+    "ampli_host_monitor_verdict": (C.c_int, [i64, i64, f32, f32, i64, i64, C.c_double]),
+    "ampli_host_monitor_excess": (C.c_double, [i64, C.c_double, i64]),
+    "ampli_host_monitor_count_ge": (i64, [f32, f32, vp, i64]),
+    "ampli_host_monitor_empirical_p": (C.c_double, [i64, i64]),
+    "ampli_host_monitor_lod_reads": (i64, [C.c_double, C.c_double, C.POINTER(i32)]),
+    "ampli_host_monitor_lod": (C.c_double, [C.c_double, C.c_double, i64, i64, C.c_double]),
 }
 
 _hip = None

@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, Records, hip_lib
+from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, MonitorParams, Records, hip_lib
 
 NT = "ACGT"
 POISSON_FULL = 0
@@ -63,6 +63,11 @@ PAIR_NA = -999.0  # a cell of pair_score that is not evaluated (AMPLI_PAIR_NA)
 FDR_NA = -999.0  # a cell of fdr_adjust that is not tested (AMPLI_FDR_NA)
 DILUTE_BAD_COUNT, DILUTE_BAD_MIXTURE = 1, 2  # the flag word of a mixture of dilute (AMPLI_DILUTE_BAD_*)
 DILUTE_KEEP_ALL = 1 << 32  # the threshold that keeps every read
+# the six sums of Context.monitor_sums (AMPLI_MON_*), the score of a cell without an evaluated entry, the verdicts and the strip of rows
+MON_N_EVAL, MON_N_SEEN, MON_K_FW, MON_K_BW, MON_D_FW, MON_D_BW, MON_SUMS = 0, 1, 2, 3, 4, 5, 6
+MON_NA = -1.0
+MON_NOT_EVALUABLE, MON_NOT_DETECTED, MON_DETECTED = 0, 1, 2
+MON_STRIP = 8
 
 
 def _ptr(t):
@@ -720,6 +725,91 @@ class Context:
         self._check(self.lib.ampli_dilute_records(self.h, C.byref(recs_a), C.byref(recs_b) if recs_b is not None else None, P, _ptr(d_mix), n_mix,
                                                   _ptr(out), _ptr(flags)))
         return out, flags
+
+    def _monitor_lists(self, P: int, thr, ref_code, list_off, list_cell):
+        """the arguments the two monitoring gathers share: (thr, ref_code, list_off, list_cell, L, W) on the device.  Host lists are
+        checked (monotone offsets, cells that fit 32 bits -- an entry at or beyond P is none, by the definition) and uploaded; device lists
+        are taken as they are (the kernels cut them)."""
+        import numpy as np
+        import torch
+
+        if not isinstance(list_off, torch.Tensor):
+            off, cell = np.asarray(list_off, np.int64), np.asarray(list_cell, np.int64)
+            assert off.ndim == 1 and len(off) >= 2 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= len(cell) < 1 << 28
+            assert ((cell >= 0) & (cell < 1 << 32)).all()
+            list_off = torch.from_numpy(off.astype(np.uint32).view(np.int32)).to(self.device)
+            list_cell = torch.from_numpy((cell if len(cell) else np.zeros(1, np.int64)).astype(np.uint32).view(np.int32)).to(self.device)
+            W = len(cell)
+        else:
+            W = list_cell.numel()
+            if W == 0:  # a pointer is required even where nothing is read through it
+                list_cell = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        for t in (list_off, list_cell):
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+        assert thr.dtype == torch.float32 and thr.is_cuda and thr.is_contiguous() and thr.numel() == 8 * P
+        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        return thr, ref_code, list_off, list_cell, list_off.numel() - 1, W
+
+    def monitor_sums(self, rec: Records, P: int, thr, ref_code, list_off, list_cell, cov: int = 100, max_vaf_pm: int = 1000, sums=None, lam=None):
+        """The pooled sums of every (sample of one resident chunk, variant list) (ampli_monitor_sums_records): sums int64
+        [n, L, 6] (MON_*) and lam float64 [n, L, 2], the expected counts of the strands under the error table.  thr: the table's
+        float32 [2, 4, P]; ref_code uint8 [P]; list_off [L + 1] and list_cell [W]: the lists as a CSR of cells 4 p + y -- device int32
+        tensors (read as uint32) or host arrays.  sums, lam: the chunk's rows of larger matrices (contiguous views), overwritten."""
+        import torch
+
+        thr, ref_code, list_off, list_cell, L, W = self._monitor_lists(P, thr, ref_code, list_off, list_cell)
+        n = rec.n_samples
+        if sums is None:
+            sums = torch.empty((n, L, MON_SUMS), dtype=torch.int64, device=self.device)
+        if lam is None:
+            lam = torch.empty((n, L, 2), dtype=torch.float64, device=self.device)
+        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and tuple(sums.shape) == (n, L, MON_SUMS)
+        assert lam.dtype == torch.float64 and lam.is_cuda and lam.is_contiguous() and tuple(lam.shape) == (n, L, 2)
+        prm = MonitorParams(int(cov), int(max_vaf_pm))
+        self._check(self.lib.ampli_monitor_sums_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), _ptr(list_off), _ptr(list_cell), L, W,
+                                                        C.byref(prm), _ptr(sums), _ptr(lam)))
+        return sums, lam
+
+    def monitor_controls(self, rec: Records, P: int, thr, ref_code, list_off, list_cell, pairs, cand_off, cand_pos, R: int, first_rep: int = 0,
+                         seed: int = 0, cov: int = 100, max_vaf_pm: int = 1000, sums=None, lam=None):
+        """The sums of R matched random control lists for every (row, list) of pairs (ampli_monitor_control_records): every
+        entry of the list is moved to a position drawn among the candidates of its reference base (cand_off int32 [5], cand_pos int32
+        [n_cand] on the device: positions grouped by reference base), replicates first_rep .. first_rep + R - 1 of seed.  pairs: int32
+        [n_pairs, 2] on the device; a row or list outside its range gives zeros.  Returns sums int64 [n_pairs, R, 6] and lam float64
+        [n_pairs, R, 2]; a replicate's cells do not depend on the batch it is computed in."""
+        import torch
+
+        thr, ref_code, list_off, list_cell, L, W = self._monitor_lists(P, thr, ref_code, list_off, list_cell)
+        assert pairs.dtype == torch.int32 and pairs.is_cuda and pairs.is_contiguous() and pairs.dim() == 2 and pairs.shape[1] == 2
+        assert cand_off.dtype == torch.int32 and cand_off.is_cuda and cand_off.is_contiguous() and tuple(cand_off.shape) == (5,)
+        assert cand_pos.dtype == torch.int32 and cand_pos.is_cuda and cand_pos.is_contiguous() and cand_pos.dim() == 1
+        n_pairs, n_cand = int(pairs.shape[0]), int(cand_pos.numel())
+        if n_cand == 0:
+            cand_pos = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        if sums is None:
+            sums = torch.empty((n_pairs, R, MON_SUMS), dtype=torch.int64, device=self.device)
+        if lam is None:
+            lam = torch.empty((n_pairs, R, 2), dtype=torch.float64, device=self.device)
+        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and tuple(sums.shape) == (n_pairs, R, MON_SUMS)
+        assert lam.dtype == torch.float64 and lam.is_cuda and lam.is_contiguous() and tuple(lam.shape) == (n_pairs, R, 2)
+        prm = MonitorParams(int(cov), int(max_vaf_pm))
+        self._check(self.lib.ampli_monitor_control_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), _ptr(list_off), _ptr(list_cell), L, W,
+                                                           _ptr(pairs), n_pairs, _ptr(cand_off), _ptr(cand_pos), n_cand, R, first_rep,
+                                                           int(seed) & 0xFFFFFFFFFFFFFFFF, C.byref(prm), _ptr(sums), _ptr(lam)))
+        return sums, lam
+
+    def monitor_score(self, sums, lam, q=None):
+        """The pooled Poisson score of both strands of every cell of monitor_sums or monitor_controls (ampli_monitor_score):
+        float32 [..., 2], MON_NA (-1) where no entry was evaluated."""
+        import torch
+
+        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and sums.shape[-1] == MON_SUMS
+        assert lam.dtype == torch.float64 and lam.is_cuda and lam.is_contiguous() and tuple(lam.shape) == tuple(sums.shape[:-1]) + (2,)
+        if q is None:
+            q = torch.empty(tuple(lam.shape), dtype=torch.float32, device=self.device)
+        assert q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == tuple(lam.shape)
+        self._check(self.lib.ampli_monitor_score(self.h, _ptr(sums), _ptr(lam), sums.numel() // MON_SUMS, _ptr(q)))
+        return q
 
     def dilution_records(self, out) -> Records:
         """the mixtures dilute wrote as Records (I32, dense, E = 0, a row per mixture): what detection_limits, nb_score and the others take"""

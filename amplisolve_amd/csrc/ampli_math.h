@@ -1491,4 +1491,116 @@ AMPLI_FN int ampli_dilute_counts_ok(const int32_t r[8])
     return ok;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Tumour-informed monitoring (the definition is tests/monitor_model.py): pooled evidence over the cells of a variant list.
+//   Lists.  A CSR: list_off uint32 [L + 1], list_cell uint32 [W], an entry c = 4 p + y (position index p, base y).  Lists may be empty,
+//     overlap and name a cell several times (it counts as often).  An entry with p >= P is none.  Offsets are cut to [0, W].
+//   Evaluated entry of sample row s, from the PRIMARY record of (s, p): the record is present; D_fw >= coverage_cutoff and D_bw >=
+//     coverage_cutoff (a strand's four counts); ref_code[p] in 0..3 and y != it; e_fw = thr[0][y][p] and e_bw = thr[1][y][p] both finite
+//     and >= 0 (so not the -1 of VC:3844); 1000 (k_fw + k_bw) <= max_vaf_pm (D_fw + D_bw) in int64, k the strand's count of base y.
+//     e == 0 is replaced by 0.0010008f (VC:3852-3856).
+//   Sums per (sample, list): N_EVAL, N_SEEN (evaluated entries with k_fw + k_bw >= 1), K_FW, K_BW, D_FW, D_BW in int64, and the doubles
+//     Lambda_st = sum (double)d_st * (double)e_st.  Lane j of 64 takes entries j, j + 64, ... in ascending order and adds each product to
+//     an accumulator that starts at +0.0 (an entry that is not evaluated adds nothing); the 64 accumulators are combined by
+//     x += x[lane ^ off] for off = 32, 16, 8, 4, 2, 1.  IEEE additions in that order, unfused: no tolerance.
+//   Pooled score per strand: Q = ampli_nb_q_from_p(P[X >= K]), X Poisson of mean Lambda -- ampli_nb_init(K, Lambda, 0) and the step loop:
+//     K == 0 gives 0, Lambda == 0 with K > 0 gives 100; N_EVAL == 0 gives AMPLI_MON_NA.
+//   Matched random controls: entry i of list l at (p, y) with g = ref_code[p] becomes (p', y), p' = cand[(uint64(word) * m) >> 32] among
+//     the m candidates of g (cand_off uint32 [5], cand_pos); word = output word 0 of Philox4x32-10 with counter (i, r, l,
+//     AMPLI_MON_CONTROL_TAG) and key (low word, high word of the seed), r the replicate's global index.  No control entry where p >= P,
+//     g > 3, m == 0 or p' >= P.  The multiply-high draw favours some candidates by less than m / 2^32.
+// ------------------------------------------------------------------------------------------------------------------------------------
+AMPLI_FN int ampli_mon_thr_ok(float e) { return e >= 0.0f && e <= 3.402823466e38f; } // a NaN, an infinity and a negative value fail
+
+// what does not depend on the sample: the reference base, the listed base and the two thresholds
+AMPLI_FN int ampli_mon_entry_ok(uint32_t ref, uint32_t y, float e_fw, float e_bw)
+{
+    return ref <= 3u && y != ref && ampli_mon_thr_ok(e_fw) && ampli_mon_thr_ok(e_bw);
+}
+
+// what does: the record of an entry that passed ampli_mon_entry_ok
+AMPLI_FN int ampli_mon_record_ok(int present, int64_t k_fw, int64_t k_bw, int64_t D_fw, int64_t D_bw, int32_t cov, int32_t max_vaf_pm)
+{
+    return present && D_fw >= (int64_t)cov && D_bw >= (int64_t)cov && 1000ll * (k_fw + k_bw) <= (int64_t)max_vaf_pm * (D_fw + D_bw);
+}
+
+AMPLI_FN double ampli_mon_lambda_term(int64_t d, float e)
+{
+    if (e == 0.0f) e = 0.0010008f;
+    return (double)d * (double)e;
+}
+
+// the index among the m candidates of its reference base that entry i of list l takes in replicate r
+AMPLI_FN uint32_t ampli_mon_control_draw(uint32_t i, uint32_t r, uint32_t l, uint64_t seed, uint32_t m)
+{
+    const uint32_t ctr[4] = {i, r, l, AMPLI_MON_CONTROL_TAG}, k[2] = {(uint32_t)seed, (uint32_t)(seed >> 32)};
+    uint32_t w[4];
+    ampli_philox4x32_10(ctr, k, w);
+    return (uint32_t)(((uint64_t)w[0] * (uint64_t)m) >> 32);
+}
+
+#ifdef __cplusplus
+static_assert(AMPLI_MON_NA == AMPLI_NB_NA, "a tail beyond the term bound leaves ampli_nb_q_from_p as AMPLI_NB_NA and is stored as AMPLI_MON_NA");
+#endif
+// what a pooled score needs before its sum: returns 1 with *s ready for ampli_nb_step while s->live, else 0 with *q the score
+AMPLI_FN int ampli_mon_score_begin(ampli_nb_sum *s, int64_t K, double lam, float *q)
+{
+    ampli_nb_init(s, (double)K, lam, 0.0);
+    if (!s->live) { *q = ampli_nb_q_from_p(s->res); return 0; }
+    return 1;
+}
+
+// the whole of one strand's pooled score (host, tests)
+AMPLI_FN float ampli_mon_score(int64_t n_eval, int64_t K, double lam)
+{
+    if (n_eval <= 0) return AMPLI_MON_NA;
+    ampli_nb_sum s;
+    float q;
+    if (ampli_mon_score_begin(&s, K, lam, &q)) {
+        while (s.live) ampli_nb_step(&s);
+        q = ampli_nb_q_from_p(s.res);
+    }
+    return q;
+}
+
+AMPLI_FN int ampli_mon_verdict(int64_t n_eval, int64_t n_seen, float q_fw, float q_bw, int64_t min_variants, int64_t min_seen, double q_min)
+{
+    if (n_eval < min_variants) return AMPLI_MON_NOT_EVALUABLE;
+    return n_seen >= min_seen && (double)q_fw >= q_min && (double)q_bw >= q_min ? AMPLI_MON_DETECTED : AMPLI_MON_NOT_DETECTED;
+}
+
+// the pooled excess fraction of a strand: max(0, (K - Lambda) / D); 0 without depth
+AMPLI_FN double ampli_mon_excess(int64_t K, double lam, int64_t D)
+{
+    if (D <= 0) return 0.0;
+    const double x = ((double)K - lam) / (double)D;
+    return x > 0.0 ? x : 0.0;
+}
+
+AMPLI_FN double ampli_mon_empirical_p(int64_t n_ge, int64_t R) { return (1.0 + (double)n_ge) / ((double)R + 1.0); }
+
+// the smallest K >= floor(Lambda) + 1 whose pooled score reaches q_min, walking upwards one count at a time for at most
+// AMPLI_MON_LOD_MAX_EVALS evaluations; 0 where none is found within them, q_min is above 100 (or a NaN), or Lambda is not in [0, 2^52)
+AMPLI_FN int64_t ampli_mon_lod_reads(double lam, double q_min, int32_t *evals)
+{
+    if (evals) *evals = 0;
+    if (!(q_min <= 100.0) || !(lam >= 0.0) || !(lam < 4503599627370496.0)) return 0;
+    int64_t K = (int64_t)floor(lam) + 1;
+    for (int i = 0; i < AMPLI_MON_LOD_MAX_EVALS; ++i, ++K) {
+        if (evals) *evals = i + 1;
+        if ((double)ampli_mon_score(1, K, lam) >= q_min) return K;
+    }
+    return 0;
+}
+
+// the pooled limit of detection of a (sample, list): the larger of the strands' (K_min - Lambda) / D; -1 where a strand has no K_min or no depth
+AMPLI_FN double ampli_mon_lod(double lam_fw, double lam_bw, int64_t D_fw, int64_t D_bw, double q_min)
+{
+    if (D_fw <= 0 || D_bw <= 0) return -1.0;
+    const int64_t kf = ampli_mon_lod_reads(lam_fw, q_min, (int32_t *)0), kb = ampli_mon_lod_reads(lam_bw, q_min, (int32_t *)0);
+    if (kf <= 0 || kb <= 0) return -1.0;
+    const double a = ((double)kf - lam_fw) / (double)D_fw, b = ((double)kb - lam_bw) / (double)D_bw;
+    return a > b ? a : b;
+}
+
 #endif

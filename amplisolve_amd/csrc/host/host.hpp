@@ -311,6 +311,17 @@ struct DiArgs {
     std::string error_file, sample_dir, mixtures, replicates = "8", seed = "1", coverage_cutoff = "100", confidence = "0.95", write_counts = "0", output_dir;
 };
 int run_insilico_dilution(const DiArgs &a);
+// AmpliSolveVariantMonitoring (mo_main.cpp, run_mo.cpp): tumour-informed monitoring.  `variants` lists
+// list<TAB>chrom<TAB>pos<TAB>ref<TAB>alt per line, `assign` sample<TAB>list per line ("-": no assignment); the panel, the thresholds and
+// the reference bases come from the error table alone.  Every file of sample_dir against every list (Monitoring_Matrix.txt), every
+// assigned pair with its limit of detection, `controls` matched random lists and the list's detections among the samples not assigned
+// to it (Monitoring_Own.txt), Monitoring_Summary.txt.  coverage_cutoff >= 0, q_min in (0, 100], min_variants >= 1, min_seen >= 0,
+// max_vaf in [0, 1] (the gate in per mille, rounded), controls >= 0, seed an unsigned 64-bit integer; exit status 0 / 1
+struct MoArgs {
+    std::string error_file, sample_dir, variants, assign = "-", coverage_cutoff = "100", q_min = "20", min_variants = "5", min_seen = "2", max_vaf = "1",
+                controls = "100", seed = "1", output_dir;
+};
+int run_variant_monitoring(const MoArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

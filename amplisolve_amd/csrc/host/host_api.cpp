@@ -550,3 +550,172 @@ extern "C" int ampli_host_sample_order(const char *dir, char *out, int64_t cap)
         return e.code ? e.code : -1;
     }
 }
+
+// ---- tumour-informed monitoring: csrc/ampli_math.h's functions in the order of the definition ----------------------------
+
+namespace {
+
+// one entry of a list as its lane sees it: a cell, or none
+struct MonEntry {
+    uint32_t p, y;
+    bool some;
+};
+
+// the sums of one (row, list): lane j takes entries j, j + 64, ... in ascending order; the 64 accumulators of each strand are combined by
+// x += x[lane ^ off] for off = 32, 16, 8, 4, 2, 1.  The integers are added as unsigned words, as the device adds them.
+void mon_sums(const int32_t *row, int64_t P, const float *thr, const uint8_t *ref_code, const MonEntry *ent, size_t len, const ampli_monitor_params *prm,
+              int64_t *o, double *ol)
+{
+    uint64_t acc[AMPLI_MON_SUMS] = {0, 0, 0, 0, 0, 0};
+    double lf[64], lb[64];
+    for (int j = 0; j < 64; ++j) lf[j] = lb[j] = 0.0;
+    for (size_t i = 0; i < len; ++i) {
+        const MonEntry &e = ent[i];
+        if (!e.some || (int64_t)e.p >= P) continue;
+        const uint32_t ref = ref_code[e.p];
+        if (ref > 3u) continue;
+        const float ef = thr[(size_t)e.y * (size_t)P + e.p], eb = thr[(size_t)(4 + e.y) * (size_t)P + e.p];
+        if (!ampli_mon_entry_ok(ref, e.y, ef, eb)) continue;
+        const int32_t *r = row + (size_t)e.p * 8;
+        const int64_t FW = (int64_t)r[0] + r[1] + r[2] + r[3], BW = (int64_t)r[4] + r[5] + r[6] + r[7];
+        const int64_t kf = r[e.y], kb = r[4 + e.y];
+        if (!ampli_mon_record_ok(r[0] != AMPLI_ABSENT, kf, kb, FW, BW, prm->coverage_cutoff, prm->max_vaf_pm)) continue;
+        acc[AMPLI_MON_N_EVAL] += 1;
+        acc[AMPLI_MON_N_SEEN] += kf + kb >= 1 ? 1 : 0;
+        acc[AMPLI_MON_K_FW] += (uint64_t)kf;
+        acc[AMPLI_MON_K_BW] += (uint64_t)kb;
+        acc[AMPLI_MON_D_FW] += (uint64_t)FW;
+        acc[AMPLI_MON_D_BW] += (uint64_t)BW;
+        lf[i & 63] = lf[i & 63] + ampli_mon_lambda_term(FW, ef);
+        lb[i & 63] = lb[i & 63] + ampli_mon_lambda_term(BW, eb);
+    }
+    for (int off = 32; off >= 1; off >>= 1) {
+        double nf[64], nb[64];
+        for (int j = 0; j < 64; ++j) { nf[j] = lf[j] + lf[j ^ off]; nb[j] = lb[j] + lb[j ^ off]; }
+        memcpy(lf, nf, sizeof lf);
+        memcpy(lb, nb, sizeof lb);
+    }
+    for (int k = 0; k < AMPLI_MON_SUMS; ++k) o[k] = (int64_t)acc[k];
+    ol[0] = lf[0];
+    ol[1] = lb[0];
+}
+
+int mon_args_bad(const int32_t *recs, int32_t n, int64_t &stride, int64_t P, const float *thr, const uint8_t *ref_code, const uint32_t *list_off,
+                 const uint32_t *list_cell, int32_t L, int64_t W, const ampli_monitor_params *prm, const int64_t *sums, const double *lambda)
+{
+    if (!recs || !thr || !ref_code || !list_off || !list_cell || !prm || !sums || !lambda || n < 1 || P <= 0 || L < 1 || W < 0 ||
+        prm->coverage_cutoff < 0 || prm->max_vaf_pm < 0 || prm->max_vaf_pm > 1000)
+        return AMPLI_E_INVALID;
+    if (stride == 0) stride = P;
+    if (stride < P) return AMPLI_E_INVALID;
+    if (P >= 0x7FFFFFFFll || W >= (1ll << 28)) return AMPLI_E_RANGE;
+    return 0;
+}
+
+// the bounds of list l, cut to [0, W]
+void mon_bounds(const uint32_t *list_off, int64_t l, int64_t W, uint32_t &off, uint32_t &end)
+{
+    const uint32_t w = (uint32_t)W, off_ = list_off[l], end_ = list_off[l + 1];
+    off = off_ < w ? off_ : w;
+    end = end_ < off ? off : (end_ < w ? end_ : w);
+}
+
+} // namespace
+
+extern "C" int ampli_host_monitor_sums(const int32_t *recs, int32_t n, int64_t stride, int64_t P, const float *thr, const uint8_t *ref_code,
+                                       const uint32_t *list_off, const uint32_t *list_cell, int32_t L, int64_t W, const ampli_monitor_params *prm,
+                                       int64_t *sums, double *lambda)
+{
+    { int rc = mon_args_bad(recs, n, stride, P, thr, ref_code, list_off, list_cell, L, W, prm, sums, lambda); if (rc) return rc; }
+    std::vector<MonEntry> ent;
+    for (int32_t l = 0; l < L; ++l) {
+        uint32_t off, end;
+        mon_bounds(list_off, l, W, off, end);
+        ent.clear();
+        for (uint32_t e = off; e < end; ++e) ent.push_back({list_cell[e] >> 2, list_cell[e] & 3u, true});
+        for (int32_t s = 0; s < n; ++s)
+            mon_sums(recs + (size_t)s * (size_t)stride * 8, P, thr, ref_code, ent.data(), ent.size(), prm, sums + ((size_t)s * L + l) * AMPLI_MON_SUMS,
+                     lambda + ((size_t)s * L + l) * 2);
+    }
+    return 0;
+}
+
+extern "C" int ampli_host_monitor_controls(const int32_t *recs, int32_t n, int64_t stride, int64_t P, const float *thr, const uint8_t *ref_code,
+                                           const uint32_t *list_off, const uint32_t *list_cell, int32_t L, int64_t W, const int32_t *pairs, int32_t n_pairs,
+                                           const uint32_t *cand_off, const uint32_t *cand_pos, int64_t n_cand, int32_t R, int32_t first_rep, uint64_t seed,
+                                           const ampli_monitor_params *prm, int64_t *sums, double *lambda)
+{
+    if (!pairs || !cand_off || !cand_pos || n_pairs < 1 || R < 1 || first_rep < 0 || n_cand < 0) return AMPLI_E_INVALID;
+    { int rc = mon_args_bad(recs, n, stride, P, thr, ref_code, list_off, list_cell, L, W, prm, sums, lambda); if (rc) return rc; }
+    if (n_cand >= (1ll << 32) || (int64_t)first_rep + R > 0x7FFFFFFFll) return AMPLI_E_RANGE;
+    std::vector<MonEntry> ent;
+    for (int32_t q = 0; q < n_pairs; ++q) {
+        const int32_t row = pairs[2 * (size_t)q], l = pairs[2 * (size_t)q + 1];
+        for (int32_t rep = 0; rep < R; ++rep) {
+            int64_t *o = sums + ((size_t)q * R + rep) * AMPLI_MON_SUMS;
+            double *ol = lambda + ((size_t)q * R + rep) * 2;
+            if (row < 0 || row >= n || l < 0 || l >= L) {
+                for (int k = 0; k < AMPLI_MON_SUMS; ++k) o[k] = 0;
+                ol[0] = ol[1] = 0.0;
+                continue;
+            }
+            uint32_t off, end;
+            mon_bounds(list_off, l, W, off, end);
+            ent.clear();
+            for (uint32_t e = off; e < end; ++e) {
+                const uint32_t c = list_cell[e], p = c >> 2;
+                MonEntry m = {0, c & 3u, false};
+                if ((int64_t)p < P && ref_code[p] <= 3u) {
+                    const uint32_t g = ref_code[p], nc = (uint32_t)n_cand;
+                    const uint32_t lo = cand_off[g] < nc ? cand_off[g] : nc;
+                    const uint32_t hi = cand_off[g + 1] < lo ? lo : (cand_off[g + 1] < nc ? cand_off[g + 1] : nc);
+                    if (hi > lo) {
+                        const uint32_t drawn = cand_pos[lo + ampli_mon_control_draw(e - off, (uint32_t)first_rep + (uint32_t)rep, (uint32_t)l, seed, hi - lo)];
+                        if ((int64_t)drawn < P && drawn < (1u << 30)) { m.p = drawn; m.some = true; }
+                    }
+                }
+                ent.push_back(m);
+            }
+            mon_sums(recs + (size_t)row * (size_t)stride * 8, P, thr, ref_code, ent.data(), ent.size(), prm, o, ol);
+        }
+    }
+    return 0;
+}
+
+extern "C" int ampli_host_monitor_score(const int64_t *sums, const double *lambda, int64_t n_cells, float *q)
+{
+    if (!sums || !lambda || !q || n_cells < 1) return AMPLI_E_INVALID;
+    for (int64_t i = 0; i < n_cells; ++i) {
+        const int64_t *c = sums + i * AMPLI_MON_SUMS;
+        q[2 * i] = ampli_mon_score(c[AMPLI_MON_N_EVAL], c[AMPLI_MON_K_FW], lambda[2 * i]);
+        q[2 * i + 1] = ampli_mon_score(c[AMPLI_MON_N_EVAL], c[AMPLI_MON_K_BW], lambda[2 * i + 1]);
+    }
+    return 0;
+}
+
+extern "C" uint32_t ampli_host_monitor_control_draw(uint32_t i, uint32_t r, uint32_t l, uint64_t seed, uint32_t m) { return ampli_mon_control_draw(i, r, l, seed, m); }
+
+extern "C" int ampli_host_monitor_verdict(int64_t n_eval, int64_t n_seen, float q_fw, float q_bw, int64_t min_variants, int64_t min_seen, double q_min)
+{
+    return ampli_mon_verdict(n_eval, n_seen, q_fw, q_bw, min_variants, min_seen, q_min);
+}
+
+extern "C" double ampli_host_monitor_excess(int64_t K, double lam, int64_t D) { return ampli_mon_excess(K, lam, D); }
+
+extern "C" double ampli_host_monitor_empirical_p(int64_t n_ge, int64_t R) { return ampli_mon_empirical_p(n_ge, R); }
+
+extern "C" int64_t ampli_host_monitor_count_ge(float obs_fw, float obs_bw, const float *ctl_q, int64_t R)
+{
+    if (!ctl_q || R < 0) return -1;
+    const float obs = obs_fw < obs_bw ? obs_fw : obs_bw;
+    int64_t n_ge = 0;
+    for (int64_t r = 0; r < R; ++r) n_ge += (ctl_q[2 * r] < ctl_q[2 * r + 1] ? ctl_q[2 * r] : ctl_q[2 * r + 1]) >= obs ? 1 : 0;
+    return n_ge;
+}
+
+extern "C" int64_t ampli_host_monitor_lod_reads(double lam, double q_min, int32_t *evals) { return ampli_mon_lod_reads(lam, q_min, evals); }
+
+extern "C" double ampli_host_monitor_lod(double lam_fw, double lam_bw, int64_t D_fw, int64_t D_bw, double q_min)
+{
+    return ampli_mon_lod(lam_fw, lam_bw, D_fw, D_bw, q_min);
+}

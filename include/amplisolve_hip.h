@@ -145,6 +145,17 @@ extern "C" {
  *   (C21) in-silico dilution (tests/test_gpu_dilution_contracts.py): d_out of ampli_dilute_records is FULLY OVERWRITTEN, all
  *        [n_mix][P][8] words, ABSENT records included, and d_flags is FULLY OVERWRITTEN, all [n_mix] words, whatever they held.  Nothing
  *        else is written.  d_mix is read at [0, n_mix), a record only at a position below P, of a row that a valid mixture names.
+ *   (C22) tumour-informed monitoring (tests/test_gpu_monitor_contracts.py): d_sums and d_lambda of ampli_monitor_sums_records are FULLY
+ *        OVERWRITTEN, all [recs->n_samples][L][6] sums and [recs->n_samples][L][2] doubles, with plain stores (one wave owns a cell:
+ *        nothing is cleared, nothing is added to), empty lists included (zeros).  Nothing else is written -- the other chunks' rows of a
+ *        larger matrix included.  d_list_off is read at [0, L], d_list_cell at [0, W) at most, d_ref_code at [0, P), d_thr at
+ *        [0, 8 P), a record only at a listed position below P of a row below n_samples.
+ *   (C23) monitoring controls: d_sums and d_lambda of ampli_monitor_control_records are FULLY OVERWRITTEN, all [n_pairs][R][6] sums and
+ *        [n_pairs][R][2] doubles, the zeros of a pair whose row or list is out of range included.  Nothing else is written.  d_pairs
+ *        is read at [0, 2 n_pairs), d_cand_off at [0, 5), d_cand_pos at [0, n_cand) at most, a record only at a drawn position below P
+ *        of a row that a pair names and that lies in the chunk.
+ *   (C24) monitoring scores: d_q of ampli_monitor_score is FULLY OVERWRITTEN, all [n_cells][2] scores, AMPLI_MON_NA included.  Nothing
+ *        else is written; d_sums is read at [0, 6 n_cells) and d_lambda at [0, 2 n_cells).
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -946,6 +957,61 @@ int ampli_fdr_adjust(ampli_ctx *ctx, const float *d_s /* [rows][P][4][2] */, int
 int ampli_dilute_records(ampli_ctx *ctx, const ampli_records *recs_a, const ampli_records *recs_b /* may be NULL */, int64_t P,
                          const ampli_dilute_mix *d_mix /* [n_mix] */, int32_t n_mix, int32_t *d_out /* [n_mix][P][8] */,
                          int32_t *d_flags /* [n_mix] */);
+
+/*
+ * Tumour-informed monitoring (the definition, in plain numpy, is tests/monitor_model.py): pooled evidence over the cells of
+ * variant lists -- is a patient's tumour, known as a list of somatic variants, in this plasma sample at all?
+ *   Lists.  A CSR IN DEVICE MEMORY: d_list_off uint32 [L + 1], d_list_cell uint32 [W], an entry c = 4 p + y (position index p below
+ *     2^30, base y).  Lists may be empty, overlap and name a cell several times; a cell named twice counts twice.  An entry with
+ *     p >= P is none.  Offsets are cut to [0, W]: the contents are not validated on the host and nothing outside is addressed.
+ *   Evaluated entry of sample row s, from the PRIMARY record of (s, p) only (slot p < P; extras and an RD plane have no effect): the
+ *     record is present; D_fw >= coverage_cutoff and D_bw >= coverage_cutoff, each the sum of the strand's four counts;
+ *     d_ref_code[p] in 0..3 and y != it; e_fw = d_thr[0][y][p] and e_bw = d_thr[1][y][p] both finite and >= 0 (so not the -1 of
+ *     VC:3844, "no estimate"); 1000 (k_fw + k_bw) <= max_vaf_pm (D_fw + D_bw) in int64, k the strand's count of base y (1000 switches
+ *     this gate off; it keeps a germline or mislisted site from carrying a list on its own).  e == 0 is replaced by 0.0010008f
+ *     (VC:3852-3856).
+ *   Sums per (sample, list), in the order AMPLI_MON_*: N_EVAL, N_SEEN (evaluated entries with k_fw + k_bw >= 1), K_FW, K_BW, D_FW,
+ *     D_BW, int64; and the doubles Lambda_fw, Lambda_bw, each the sum of (double)d_st * (double)e_st.  The order of the double additions
+ *     is part of the definition: lane j of 64 takes the list's entries j, j + 64, ... in ascending order and adds each product to an
+ *     accumulator that starts at +0.0 (an entry that is not evaluated adds nothing); the 64 accumulators are combined by the butterfly
+ *     x += x[lane ^ off] for off = 32, 16, 8, 4, 2, 1.  Unfused IEEE operations: the model, the host library and the device agree bit
+ *     for bit.  W >= 2^28 is AMPLI_E_RANGE, so no integer sum can leave int64 (a depth is below 2^34).
+ *   Pooled score per strand: Q = (float)(-10 log10(max(p, 1e-10))), 0 for p >= 1, p = P[X >= K] for X Poisson of mean Lambda
+ *     (ampli_nb_init at omega = 0 and its step loop, csrc/ampli_math.h).  K == 0 gives 0, Lambda == 0 with K > 0 gives 100,
+ *     N_EVAL == 0 gives AMPLI_MON_NA for both strands; so does a tail beyond the term bound (csrc/ampli_math.h says when).
+ *   Matched random controls, replicate r (global index) of list l: entry i (0-based within the list) at (p, y) with g = d_ref_code[p]
+ *     becomes (p', y), p' = d_cand_pos[d_cand_off[g] + ((uint64(word) * m) >> 32)] with m = d_cand_off[g + 1] - d_cand_off[g] the
+ *     candidates of g (d_cand_off uint32 [5], bounds cut to [0, n_cand]; d_cand_pos uint32 [n_cand], positions grouped by reference
+ *     base) and word = output word 0 of Philox4x32-10 with counter (i, r, l, AMPLI_MON_CONTROL_TAG) and key (low word, high word of
+ *     seed).  No control entry where p >= P, g > 3, m == 0 or p' >= P.  The multiply-high draw favours some candidates by less than
+ *     m / 2^32.  A control list depends on (seed, l, r) only, never on the sample; its sums are formed exactly as above, from the
+ *     thresholds and the reference base of p', max_vaf_pm included.
+ *
+ * ampli_monitor_sums_records: d_sums int64 [recs->n_samples][L][6] and d_lambda double [recs->n_samples][L][2], 8-byte aligned, FULLY
+ *   OVERWRITTEN with plain stores (C22); a streamed cohort passes each chunk its rows of one matrix.  A wave owns one list and
+ *   AMPLI_MON_STRIP consecutive rows; lists of up to 256 entries keep their cells and thresholds in registers (loaded once per wave),
+ *   longer ones are walked in rounds of 64 by the same wave.
+ * ampli_monitor_control_records: d_pairs int32 [n_pairs][2] (row of the chunk, list) in device memory; replicates first_rep ..
+ *   first_rep + R - 1; d_sums int64 [n_pairs][R][6] and d_lambda double [n_pairs][R][2], FULLY OVERWRITTEN (C23).  A row or list index
+ *   outside its range makes that pair's cells all zero (which scores as N_EVAL = 0); the index is checked before any list or record
+ *   is loaded.  A wave owns one (pair, replicate): a replicate's cells do not depend on the batch it is computed in.
+ * ampli_monitor_score: d_q float [n_cells][2] (fw, bw) from d_sums int64 [n_cells][6] and d_lambda double [n_cells][2], FULLY
+ *   OVERWRITTEN (C24).  A lane per cell; the lane's two tails run in one loop.
+ * Refusals, every output untouched.  AMPLI_E_INVALID: a null or misaligned pointer (prm is a host pointer), P <= 0, L < 1, W < 0,
+ *   R < 1, n_pairs < 1, n_cells < 1, first_rep < 0, n_cand < 0, coverage_cutoff < 0, max_vaf_pm outside 0..1000, broken records.
+ *   AMPLI_E_RANGE: P >= 2^31, W >= 2^28, n_samples > 2097120, n_cand >= 2^32, first_rep + R >= 2^31.
+ * No LDS, no barrier, no atomics: the same inputs give the same bytes.  All three are asynchronous on the context's stream.  The
+ * verdict, the excess fractions, the empirical p and the limit of detection are decided on the host (include/amplisolve_host.h).
+ */
+int ampli_monitor_sums_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const float *d_thr, const uint8_t *d_ref_code,
+                               const uint32_t *d_list_off, const uint32_t *d_list_cell, int32_t L, int64_t W, const ampli_monitor_params *prm,
+                               int64_t *d_sums /* [n][L][6] */, double *d_lambda /* [n][L][2] */);
+int ampli_monitor_control_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const float *d_thr, const uint8_t *d_ref_code,
+                                  const uint32_t *d_list_off, const uint32_t *d_list_cell, int32_t L, int64_t W, const int32_t *d_pairs /* [n_pairs][2] */,
+                                  int32_t n_pairs, const uint32_t *d_cand_off /* [5] */, const uint32_t *d_cand_pos /* [n_cand] */, int64_t n_cand,
+                                  int32_t R, int32_t first_rep, uint64_t seed, const ampli_monitor_params *prm, int64_t *d_sums /* [n_pairs][R][6] */,
+                                  double *d_lambda /* [n_pairs][R][2] */);
+int ampli_monitor_score(ampli_ctx *ctx, const int64_t *d_sums, const double *d_lambda, int64_t n_cells, float *d_q /* [n_cells][2] */);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

@@ -302,6 +302,39 @@ uint64_t ampli_host_dilute_keep(double x);
 int ampli_host_dilute_records(const int32_t *recs_a, int32_t n_a, int64_t stride_a, const int32_t *recs_b, int32_t n_b, int64_t stride_b, int64_t P,
                               const ampli_dilute_mix *mix, int32_t n_mix, int32_t *out, int32_t *flags);
 
+/* Tumour-informed monitoring (the definition is tests/monitor_model.py): csrc/ampli_math.h's functions in the order of the
+ * definition, so that every integer, every double and every score is pinned without a GPU.  The definition in full stands in
+ * include/amplisolve_hip.h (ampli_monitor_sums_records).
+ * _monitor_sums, _monitor_controls, _monitor_score: the three device entry points over int32 records on the host.  recs int32
+ *   [n][stride][8], stride in records (0 = P), of which the first P records of a row enter; the other arrays as on the device.  The
+ *   outputs are fully overwritten.  Returns 0, or AMPLI_E_INVALID (-1) / AMPLI_E_RANGE (-6) with nothing written where the device
+ *   entry point refuses.
+ * _monitor_control_draw: the index among m candidates that entry i of list l takes in replicate r: (uint64(word) * m) >> 32, word =
+ *   output word 0 of Philox4x32-10 with counter (i, r, l, AMPLI_MON_CONTROL_TAG) and key (low word, high word of seed).
+ * _monitor_verdict: AMPLI_MON_NOT_EVALUABLE if n_eval < min_variants; else AMPLI_MON_DETECTED iff n_seen >= min_seen and q_fw >= q_min
+ *   and q_bw >= q_min (the float scores widened to double); else AMPLI_MON_NOT_DETECTED.
+ * _monitor_excess: the pooled excess fraction of a strand, max(0, ((double)K - Lambda) / (double)D); 0 for D <= 0.
+ * _monitor_count_ge: n_ge = the controls r < R whose min(ctl_q[r][0], ctl_q[r][1]) >= min(obs_fw, obs_bw); -1 for a null pointer or R < 0.
+ * _monitor_empirical_p: (1 + n_ge) / (R + 1).
+ * _monitor_lod_reads: the smallest K >= floor(Lambda) + 1 whose pooled score reaches q_min, walking upwards one count at a time for at
+ *   most AMPLI_MON_LOD_MAX_EVALS evaluations; 0 where none is found within them, q_min is above 100 or Lambda is outside [0, 2^52);
+ *   *evals (optional) = evaluations made.
+ * _monitor_lod: the pooled limit of detection, the larger of the strands' (K_min - Lambda) / D; -1 where a strand has no K_min or D <= 0. */
+int ampli_host_monitor_sums(const int32_t *recs, int32_t n, int64_t stride, int64_t P, const float *thr, const uint8_t *ref_code, const uint32_t *list_off,
+                            const uint32_t *list_cell, int32_t L, int64_t W, const ampli_monitor_params *prm, int64_t *sums, double *lambda);
+int ampli_host_monitor_controls(const int32_t *recs, int32_t n, int64_t stride, int64_t P, const float *thr, const uint8_t *ref_code,
+                                const uint32_t *list_off, const uint32_t *list_cell, int32_t L, int64_t W, const int32_t *pairs, int32_t n_pairs,
+                                const uint32_t *cand_off, const uint32_t *cand_pos, int64_t n_cand, int32_t R, int32_t first_rep, uint64_t seed,
+                                const ampli_monitor_params *prm, int64_t *sums, double *lambda);
+int ampli_host_monitor_score(const int64_t *sums, const double *lambda, int64_t n_cells, float *q);
+uint32_t ampli_host_monitor_control_draw(uint32_t i, uint32_t r, uint32_t l, uint64_t seed, uint32_t m);
+int ampli_host_monitor_verdict(int64_t n_eval, int64_t n_seen, float q_fw, float q_bw, int64_t min_variants, int64_t min_seen, double q_min);
+double ampli_host_monitor_excess(int64_t K, double lam, int64_t D);
+int64_t ampli_host_monitor_count_ge(float obs_fw, float obs_bw, const float *ctl_q, int64_t R);
+double ampli_host_monitor_empirical_p(int64_t n_ge, int64_t R);
+int64_t ampli_host_monitor_lod_reads(double lam, double q_min, int32_t *evals);
+double ampli_host_monitor_lod(double lam_fw, double lam_bw, int64_t D_fw, int64_t D_bw, double q_min);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */

@@ -132,4 +132,26 @@ static_assert(sizeof(ampli_dilute_mix) == 32 && offsetof(ampli_dilute_mix, row_a
 static_assert(AMPLI_DILUTE_BAD_COUNT == 1 && AMPLI_DILUTE_BAD_MIXTURE == 2 && AMPLI_DILUTE_MAX_COUNT == (1 << 24) - 2, "the flag bits and the count range");
 #endif
 
+/* Tumour-informed monitoring: the order of the six int64 sums of a (sample, list), the score of a cell without an evaluated
+ * entry (outside [0, 100]; a tail that is not computable within its term bound gets it too), the verdict of a (sample, list), the rows
+ * a wave of monitor_sums_kernel owns, the tag in the fourth counter word of a control draw, the bound of the limit-of-detection walk,
+ * and the gates of an evaluated entry (coverage_cutoff >= 0, 0 <= max_vaf_pm <= 1000; 1000 switches the allele-fraction gate off). */
+#define AMPLI_MON_N_EVAL 0
+#define AMPLI_MON_N_SEEN 1
+#define AMPLI_MON_K_FW 2
+#define AMPLI_MON_K_BW 3
+#define AMPLI_MON_D_FW 4
+#define AMPLI_MON_D_BW 5
+#define AMPLI_MON_SUMS 6
+#define AMPLI_MON_NA (-1.0f)
+#define AMPLI_MON_NOT_EVALUABLE 0
+#define AMPLI_MON_NOT_DETECTED 1
+#define AMPLI_MON_DETECTED 2
+#define AMPLI_MON_STRIP 8
+#define AMPLI_MON_CONTROL_TAG 0x4D4F4E31u /* "MON1" */
+#define AMPLI_MON_LOD_MAX_EVALS 4096
+typedef struct ampli_monitor_params {
+    int32_t coverage_cutoff, max_vaf_pm;
+} ampli_monitor_params;
+
 #endif /* AMPLISOLVE_TYPES_H */
