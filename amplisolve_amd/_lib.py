@@ -57,6 +57,11 @@ class MonitorParams(C.Structure):
     _fields_ = [("coverage_cutoff", i32), ("max_vaf_pm", i32)]
 
 
+class AllelicParams(C.Structure):
+    """mirror of ampli_allelic_params: the gates of a tested het site"""
+    _fields_ = [("min_depth", i32), ("min_normals", i32), ("half_fallback", i32)]
+
+
 # every symbol include/amplisolve_hip.h declares: (restype, argtypes)
 HIP_SYMBOLS = {
     "ampli_abi_version": (C.c_int, []),
@@ -175,6 +180,9 @@ HIP_SYMBOLS = {
     "ampli_monitor_control_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, vp, vp, vp, i32, i64, vp, i32, vp, vp, i64, i32, i32, u64,
                                                 C.POINTER(MonitorParams), vp, vp]),
     "ampli_monitor_score": (C.c_int, [vp, vp, vp, i64, vp]),
+    "ampli_hetsite_reference_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, i32, vp]),
+    "ampli_allelic_site_records": (C.c_int, [vp, C.POINTER(Records), i64, vp, i32, vp, vp, C.POINTER(AllelicParams), vp, vp, vp, vp]),
+    "ampli_allelic_region_sums": (C.c_int, [vp, vp, vp, vp, vp, i32, i64, i32, vp, vp, i64, C.c_double, vp]),
 }
 
 class GenotypeParams(C.Structure):
@@ -294,6 +302,10 @@ HOST_SYMBOLS = {
     "ampli_host_monitor_empirical_p": (C.c_double, [i64, i64]),
     "ampli_host_monitor_lod_reads": (i64, [C.c_double, C.c_double, C.POINTER(i32)]),
     "ampli_host_monitor_lod": (C.c_double, [C.c_double, C.c_double, i64, i64, C.c_double]),
+    "ampli_host_allelic_site_batch": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, vp, C.POINTER(AllelicParams), vp, vp, vp, vp, vp]),
+    "ampli_host_allelic_pair": (C.c_int, [C.c_uint32]),
+    "ampli_host_allelic_site_sums": (C.c_int, [f32, i32, i32, C.c_double, C.POINTER(i64), C.POINTER(i64)]),
+    "ampli_host_allelic_region_verdict": (C.c_int, [vp, i64, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _hip = None

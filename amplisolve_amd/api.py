@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import AccTable, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, MonitorParams, Records, hip_lib
+from ._lib import AccTable, AllelicParams, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, MonitorParams, Records, hip_lib
 
 NT = "ACGT"
 POISSON_FULL = 0
@@ -68,6 +68,14 @@ MON_N_EVAL, MON_N_SEEN, MON_K_FW, MON_K_BW, MON_D_FW, MON_D_BW, MON_SUMS = 0, 1,
 MON_NA = -1.0
 MON_NOT_EVALUABLE, MON_NOT_DETECTED, MON_DETECTED = 0, 1, 2
 MON_STRIP = 8
+# allelic imbalance (AMPLI_AI_*): the planes of the het-site reference, the status of a cell (code = status * 8 + pair, pair 7: none), the
+# score of an untested cell, the five sums of a (sample, region) and the verdicts
+AI_REF_CNT, AI_REF_LO, AI_REF_HI = 0, 1, 2
+AI_NOT_HET, AI_ABSENT, AI_SHALLOW, AI_DEEP, AI_NO_REFERENCE, AI_TESTED_REF, AI_TESTED_HALF = 0, 1, 2, 3, 4, 5, 6
+AI_NO_PAIR = 7
+AI_NA = -999.0
+AI_SITES, AI_SIG, AI_DEPTH, AI_DEV16, AI_Q20, AI_SUMS = 0, 1, 2, 3, 4, 5
+AI_FEW, AI_BALANCED, AI_IMBALANCED = 0, 1, 2
 
 
 def _ptr(t):
@@ -810,6 +818,76 @@ class Context:
         assert q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == tuple(lam.shape)
         self._check(self.lib.ampli_monitor_score(self.h, _ptr(sums), _ptr(lam), sums.numel() // MON_SUMS, _ptr(q)))
         return q
+
+    def hetsite_reference(self, rec: Records, P: int, planes, min_depth: int = 100, ref=None):
+        """One resident chunk of normals into the het-site reference (ampli_hetsite_reference_records): ref int64 [3, 6, P]
+        (AI_REF_CNT / _LO / _HI per pair code and position) is ADDED TO -- a new one starts at zero, streamed chunks accumulate.  planes:
+        the genotype planes of the chunk's own rows, int64 [n, 6, W].  Only the primary records enter."""
+        import torch
+
+        n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
+        assert planes.dtype == torch.int64 and planes.is_cuda and planes.is_contiguous() and tuple(planes.shape) == (n, GENO_PLANES, W)
+        if ref is None:
+            ref = torch.zeros((3, 6, P), dtype=torch.int64, device=self.device)
+        assert ref.dtype == torch.int64 and ref.is_cuda and ref.is_contiguous() and tuple(ref.shape) == (3, 6, P)
+        self._check(self.lib.ampli_hetsite_reference_records(self.h, C.byref(rec), P, _ptr(planes), int(min_depth), _ptr(ref)))
+        return ref
+
+    def allelic_sites(self, rec: Records, P: int, planes_g, row_g, ref, min_depth: int = 100, min_normals: int = 5, half_fallback: bool = True,
+                      q=None, km=None, v=None, code=None):
+        """The allelic balance of every (sample of one resident chunk, position) at the het sites of the sample's germline
+        (ampli_allelic_site_records).  planes_g: genotype planes int64 [n_g, 6, W]; row_g: int32 [n] on the device, the plane row
+        of each sample's germline (outside [0, n_g): none); ref: the het-site reference int64 [3, 6, P].  Returns q float32 [n, P]
+        (signed score, AI_NA where untested), km int32 [n, P, 2] (k_lo, m), v float64 [n, P] (the expected share) and code uint8 [n, P]
+        (status * 8 + pair); given buffers (the chunk's rows of larger planes) are overwritten."""
+        import torch
+
+        n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
+        assert planes_g.dtype == torch.int64 and planes_g.is_cuda and planes_g.is_contiguous() and tuple(planes_g.shape[1:]) == (GENO_PLANES, W)
+        assert row_g.dtype == torch.int32 and row_g.is_cuda and row_g.is_contiguous() and tuple(row_g.shape) == (n,)
+        assert ref.dtype == torch.int64 and ref.is_cuda and ref.is_contiguous() and tuple(ref.shape) == (3, 6, P)
+        d = self.device
+        q = torch.empty((n, P), dtype=torch.float32, device=d) if q is None else q
+        km = torch.empty((n, P, 2), dtype=torch.int32, device=d) if km is None else km
+        v = torch.empty((n, P), dtype=torch.float64, device=d) if v is None else v
+        code = torch.empty((n, P), dtype=torch.uint8, device=d) if code is None else code
+        for t, dt, sh in ((q, torch.float32, (n, P)), (km, torch.int32, (n, P, 2)), (v, torch.float64, (n, P)), (code, torch.uint8, (n, P))):
+            assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == sh
+        prm = AllelicParams(int(min_depth), int(min_normals), int(bool(half_fallback)))
+        self._check(self.lib.ampli_allelic_site_records(self.h, C.byref(rec), P, _ptr(planes_g), int(planes_g.shape[0]), _ptr(row_g), _ptr(ref),
+                                                        C.byref(prm), _ptr(q), _ptr(km), _ptr(v), _ptr(code)))
+        return q, km, v, code
+
+    def allelic_regions(self, q, km, v, code, reg_off, reg_pos, site_q: float = 20.0, out=None):
+        """The five sums (AI_*) of every (sample, region) over the site planes of allelic_sites (ampli_allelic_region_sums):
+        int64 [S, R, 5].  reg_off [R + 1] and reg_pos [W]: the regions' position lists as a CSR -- device int32 tensors (read as uint32)
+        or host arrays, which are checked (monotone offsets, entries that fit 32 bits; an entry at or beyond P is none) and uploaded."""
+        import numpy as np
+        import torch
+
+        S, P = int(q.shape[0]), int(q.shape[1])
+        for t, dt, sh in ((q, torch.float32, (S, P)), (km, torch.int32, (S, P, 2)), (v, torch.float64, (S, P)), (code, torch.uint8, (S, P))):
+            assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == sh
+        if not isinstance(reg_off, torch.Tensor):
+            off, pos = np.asarray(reg_off, np.int64), np.asarray(reg_pos, np.int64)
+            assert off.ndim == 1 and len(off) >= 2 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= len(pos) < 1 << 27
+            assert ((pos >= 0) & (pos < 1 << 32)).all()
+            reg_off = torch.from_numpy(off.astype(np.uint32).view(np.int32)).to(self.device)
+            reg_pos = torch.from_numpy((pos if len(pos) else np.zeros(1, np.int64)).astype(np.uint32).view(np.int32)).to(self.device)
+            W = len(pos)
+        else:
+            W = reg_pos.numel()
+            if W == 0:  # a pointer is required even where nothing is read through it
+                reg_pos = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        for t in (reg_off, reg_pos):
+            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+        R = reg_off.numel() - 1
+        if out is None:
+            out = torch.empty((S, R, AI_SUMS), dtype=torch.int64, device=self.device)
+        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (S, R, AI_SUMS)
+        self._check(self.lib.ampli_allelic_region_sums(self.h, _ptr(q), _ptr(km), _ptr(v), _ptr(code), S, P, R, _ptr(reg_off), _ptr(reg_pos), W,
+                                                       float(site_q), _ptr(out)))
+        return out
 
     def dilution_records(self, out) -> Records:
         """the mixtures dilute wrote as Records (I32, dense, E = 0, a row per mixture): what detection_limits, nb_score and the others take"""

@@ -1603,4 +1603,171 @@ AMPLI_FN double ampli_mon_lod(double lam_fw, double lam_bw, int64_t D_fw, int64_
     return a > b ? a : b;
 }
 
+// ---------------------------------------------------------------------------
+// Allelic imbalance at germline het sites (the definition is tests/allelic_model.py).
+//
+// A het site of pair code c = 0..5, (lo, hi) = (A,C), (A,G), (A,T), (C,G), (C,T), (G,T), shows k_lo reads of its lower base among the
+// m = k_lo + k_hi reads of its two bases; the panel of normals expects the share v of them (depth-weighted over the normals that are het
+// with the same pair, or 0.5).  d = (double)k_lo - v (double)m, two operations:
+//   d == 0:  q = +0;   d > 0:  p = P[X >= k_lo], X ~ Bin(m, v);   d < 0:  p = P[X <= k_lo] = P[Y >= m - k_lo], Y ~ Bin(m, 1.0 - v);
+//   p2 = min(1, 2 p),  q = sign(d) (float)(-10 log10(max(p2, 1e-10))),  +0 where p2 >= 1, never -0, |q| <= 100.
+// A p2 within 1e-8 of 1 counts as 1 (AMPLI_AI_P2_ONE): the sums below end 1e-9 short of their tails, and a count half a read beyond
+// the mean of a symmetric law -- m odd under v = 0.5, the fallback's everyday case -- has 2 p = 1 exactly, which must give +0.
+// Both sides are the UPPER tail of a binomial from a count j strictly beyond its mean n w:
+//   * ONE term starts the sum, in the saddle-point form (ampli_binom_logpmf); the later ones come from the ratio
+//     (n - j) / (j + 1) * w / (1 - w), which is below 1 from the first step, falls from step to step and is 0 at the end of the support;
+//   * what is left after a term t with next ratio r is below t r / (1 - r): the sum ends once that is below AMPLI_AI_EPS of the sum
+//     (RELATIVE, as ampli_hyper_step).  A first term with t / (1 - r) < 0.5e-10 decides the score without a sum: +-100;
+//   * terms: the relative cut-off is reached within about 6.1 standard deviations of the mean when the sum starts there, and a sum that
+//     starts farther out than 6.5 is decided by its first term; sums never cross the mean.  A tail costs at most
+//     AMPLI_AI_TERMS(n w (1 - w)) terms (asserted in tests/test_allelic_host.py over a grid), below 2^19 for every m < 2^31.  The loop's
+//     own bound is AMPLI_AI_MAX_TERMS; a tail that would need more is a NaN and its score AMPLI_AI_NA, not a wrong number.
+// One ampli_ai_step is AMPLI_TAIL_RUN terms, so that a kernel runs all of a lane's cells in a single loop (as ampli_nb_step).
+// ---------------------------------------------------------------------------
+#define AMPLI_AI_EPS 1e-9
+#define AMPLI_AI_P2_ONE (1.0 - 1e-8)     // from here on 2 p is 1
+#define AMPLI_AI_MAX_TERMS (1 << 20)     // of one sum: the loop's own bound
+#define AMPLI_AI_TERMS(var) (8.0 * sqrt(var) + 64.0)
+#define AMPLI_AI_MAX_M 2147483647ll      // 2^31 - 1: a deeper site is AMPLI_AI_DEEP
+
+typedef struct {
+    double n, j, o;    // reads; index of the latest term; w / (1 - w)
+    double t, sum;     // the latest term; the terms so far
+    double res;        // the tail, once live == 0 (a NaN: not computable within the bound)
+    int32_t terms;     // pmf terms formed, the first one included
+    int32_t live;
+} ampli_ai_sum;
+
+// P[X >= j], X ~ Bin(n, w), for 0 < w < 1 and an integer j with n w < j <= n
+AMPLI_FN void ampli_ai_init(ampli_ai_sum *s, double n, double j, double w)
+{
+    double dev;
+    s->n = n; s->j = j; s->o = w / (1.0 - w);
+    s->t = s->sum = exp(ampli_binom_logpmf(n, j, w, &dev));
+    s->res = 0.0; s->terms = 1; s->live = 1;
+    const double r = (n - j) / (j + 1.0) * s->o;
+    if (!(r < 1.0)) { s->res = 1.0; s->live = 0; return; }            // not beyond the mode: no caller with d != 0 comes here
+    if (s->t < 0.5e-10 * (1.0 - r)) { s->res = 0.0; s->live = 0; }     // twice the whole tail is below 1e-10: decided without a sum
+}
+
+AMPLI_FN void ampli_ai_step(ampli_ai_sum *s)
+{
+    double j = s->j, t = s->t, sum = s->sum;
+    const double n = s->n, o = s->o;
+    int terms = s->terms, end = 0; // 1: the sum is complete, 2: the bound
+    for (int i = 0; i < AMPLI_TAIL_RUN; ++i) {
+        const double r = (n - j) / (j + 1.0) * o; // 0 at the end of the support
+        if (!(t * r >= AMPLI_AI_EPS * sum * (1.0 - r))) { end = 1; break; }
+        if (terms >= AMPLI_AI_MAX_TERMS) { end = 2; break; }
+        t *= r;
+        sum += t;
+        j += 1.0;
+        ++terms;
+    }
+    s->j = j; s->t = t; s->sum = sum; s->terms = terms;
+    if (!end) return;
+    s->live = 0;
+    s->res = end == 2 ? (double)NAN : (sum < 1.0 ? sum : 1.0);
+}
+
+// the signed score of a one-sided tail p on side sign: +0 for 2 p >= 1, AMPLI_AI_NA for a NaN
+AMPLI_FN float ampli_ai_q_from_p(double p, int sign)
+{
+    if (p != p) return AMPLI_AI_NA;
+    const double p2 = 2.0 * p;
+    if (p2 >= AMPLI_AI_P2_ONE) return 0.0f;
+    const float q = (float)(-10.0 * log10(p2 > 1e-10 ? p2 : 1e-10));
+    if (q == 0.0f) return 0.0f;
+    return sign > 0 ? q : -q;
+}
+
+// the pair code of the six plane bits of a (row, position): V and H set and exactly two of A, C, G, T; -1 for anything else
+AMPLI_FN int ampli_ai_pair(unsigned g)
+{
+    if ((g & (AMPLI_GENO_V | AMPLI_GENO_H)) != (unsigned)(AMPLI_GENO_V | AMPLI_GENO_H)) return -1;
+    const unsigned b = (g >> 1) & 15u; // A = 1, C = 2, G = 4, T = 8
+    return b == 3u ? 0 : b == 5u ? 1 : b == 9u ? 2 : b == 6u ? 3 : b == 10u ? 4 : b == 12u ? 5 : -1;
+}
+AMPLI_FN int ampli_ai_pair_lo(int c) { return c < 3 ? 0 : (c < 5 ? 1 : 2); }
+AMPLI_FN int ampli_ai_pair_hi(int c) { return c == 0 ? 1 : ((c == 1 || c == 3) ? 2 : 3); }
+
+// the status of a cell, the first rule that applies (include/amplisolve_hip.h); *v = the expected share of a tested cell, else 0
+AMPLI_FN int ampli_ai_site_status(int pair, int present, int64_t k_lo, int64_t k_hi, int64_t cnt, int64_t lo, int64_t hi, const ampli_allelic_params *prm,
+                                  double *v)
+{
+    *v = 0.0;
+    if (pair < 0) return AMPLI_AI_NOT_HET;
+    if (!present) return AMPLI_AI_ABSENT;
+    const int64_t m = k_lo + k_hi;
+    if (m < (int64_t)prm->min_depth) return AMPLI_AI_SHALLOW;
+    if (m > AMPLI_AI_MAX_M) return AMPLI_AI_DEEP;
+    if (cnt >= (int64_t)prm->min_normals && lo > 0 && hi > 0) {
+        *v = (double)lo / (double)(lo + hi);
+        return AMPLI_AI_TESTED_REF;
+    }
+    if (prm->half_fallback) {
+        *v = 0.5;
+        return AMPLI_AI_TESTED_HALF;
+    }
+    return AMPLI_AI_NO_REFERENCE;
+}
+
+// what a tested cell needs before its sum: returns the side (+1 / -1) with *s ready for ampli_ai_step while s->live, or 0 with *q the score
+AMPLI_FN int ampli_ai_site_begin(ampli_ai_sum *s, int64_t k_lo, int64_t m, double v, float *q)
+{
+    s->live = 0; s->terms = 0;
+    const double dk = (double)k_lo, dm = (double)m;
+    const double e = v * dm;
+    const double d = dk - e;
+    if (d == 0.0) { *q = 0.0f; return 0; }
+    const int sign = d > 0.0 ? 1 : -1;
+    if (sign > 0) ampli_ai_init(s, dm, dk, v);
+    else ampli_ai_init(s, dm, (double)(m - k_lo), 1.0 - v);
+    if (!s->live) { *q = ampli_ai_q_from_p(s->res, sign); return 0; }
+    return sign;
+}
+
+// the whole of one tested cell (host, tests); *terms (optional) = pmf terms formed
+AMPLI_FN float ampli_ai_site_score(int64_t k_lo, int64_t m, double v, int32_t *terms)
+{
+    ampli_ai_sum s;
+    float q;
+    const int sign = ampli_ai_site_begin(&s, k_lo, m, v, &q);
+    if (sign) {
+        while (s.live) ampli_ai_step(&s);
+        q = ampli_ai_q_from_p(s.res, sign);
+    }
+    if (terms) *terms = s.terms;
+    return q;
+}
+
+// what a tested cell adds to DEV16 and Q20 of a region
+AMPLI_FN int64_t ampli_ai_dev16(int64_t k_lo, int64_t m, double v)
+{
+    const double e = v * (double)m;
+    const double d = (double)k_lo - e;
+    return (int64_t)llrint(fabs(d) * 16.0);
+}
+AMPLI_FN int64_t ampli_ai_q20(float q) { return (int64_t)llrint((double)fabsf(q) * 1048576.0); }
+
+// The verdict of a region from its five sums (AMPLI_AI_SITES ..): Fisher's combination of the sites' two-sided p-values, chi-square
+// with 2 SITES degrees of freedom through the project's kf_gammaq, and the pooled deviation of the share.  *Q and *imbalance are NaN
+// where they do not exist (FEW; no depth).
+AMPLI_FN int ampli_ai_region_verdict(const int64_t *sums, int64_t min_sites, double q_min, double min_imbalance, double *Q, double *imbalance)
+{
+    const int64_t sites = sums[AMPLI_AI_SITES], depth = sums[AMPLI_AI_DEPTH];
+    *Q = (double)NAN;
+    *imbalance = depth > 0 ? (double)sums[AMPLI_AI_DEV16] / (16.0 * (double)depth) : (double)NAN;
+    if (sites < min_sites || sites < 1) return AMPLI_AI_FEW;
+    const double X = (2.302585092994046 / 5.0) * ((double)sums[AMPLI_AI_Q20] / 1048576.0);
+    const double p = ampli_kf_gammaq((double)sites, X / 2.0);
+    *Q = p >= 1.0 ? 0.0 : (p > 1e-30 ? -10.0 * log10(p) : 300.0);
+    return (*Q >= q_min && *imbalance >= min_imbalance) ? AMPLI_AI_IMBALANCED : AMPLI_AI_BALANCED;
+}
+
+// the tumour fraction an imbalance would imply: under copy-neutral LOH the share moves by f / 2, under the loss of one copy by
+// f / (2 (2 - f)) -- so f = 2 i and f = 4 i / (1 + 2 i)
+AMPLI_FN double ampli_ai_fraction_cnloh(double imbalance) { return 2.0 * imbalance; }
+AMPLI_FN double ampli_ai_fraction_loss(double imbalance) { return 4.0 * imbalance / (1.0 + 2.0 * imbalance); }
+
 #endif

@@ -322,6 +322,16 @@ struct MoArgs {
                 controls = "100", seed = "1", output_dir;
 };
 int run_variant_monitoring(const MoArgs &a);
+// AmpliSolveAllelicImbalance (ai_main.cpp, run_ai.cpp): the allelic balance at germline het sites, pooled per gene.  The het-site
+// reference from the normals; every file of tumour_dir (or, with "-", the normals again: the null calibration) at the het sites of its own
+// genotype or of the normal that `pairs` names (tumourName<TAB>normalName per line, or "self"); one region per gene string of the BED and
+// ALL.  Allelic_Reference.txt, Allelic_Sites.txt, Allelic_Genes.txt, Allelic_Summary.txt.  min_depth >= 1, min_normals >= 1, site_q in
+// [0, 100], min_sites >= 1, q_min in [0, 300], min_imbalance in [0, 1]; exit status 0 / 1
+struct AiArgs {
+    std::string panel_design, germline_dir, tumour_dir, pairs = "self", output_dir, min_depth = "100", min_normals = "5", site_q = "20", min_sites = "3",
+                q_min = "20", min_imbalance = "0.02";
+};
+int run_allelic_imbalance(const AiArgs &a);
 // ---- annotate.cpp ----
 double fisher_two_sided(int a, int b, int c, int d);                            // VC:3797-3814 (own hypergeometric pmf)
 double fisher_two_sided_direct(int a, int b, int c, int d);                     // the same, every term from log-gamma (check)

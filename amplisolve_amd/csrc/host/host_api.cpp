@@ -719,3 +719,40 @@ extern "C" double ampli_host_monitor_lod(double lam_fw, double lam_bw, int64_t D
 {
     return ampli_mon_lod(lam_fw, lam_bw, D_fw, D_bw, q_min);
 }
+
+// ---- allelic imbalance: the site stage cell by cell, and the region verdict ----
+extern "C" int ampli_host_allelic_site_batch(int64_t n, const int32_t *pair, const uint8_t *present, const int64_t *k_lo, const int64_t *k_hi, const int64_t *cnt,
+                                             const int64_t *lo, const int64_t *hi, const ampli_allelic_params *prm, float *q, int32_t *km, double *v,
+                                             uint8_t *code, int32_t *terms)
+{
+    if (n < 0 || !pair || !present || !k_lo || !k_hi || !cnt || !lo || !hi || !prm || !q || !km || !v || !code) return -1;
+    if (prm->min_depth < 1 || prm->min_normals < 1 || (prm->half_fallback != 0 && prm->half_fallback != 1)) return -1;
+    for (int64_t i = 0; i < n; ++i) {
+        const int c = pair[i] >= 0 && pair[i] < AMPLI_AI_PAIRS ? pair[i] : -1;
+        const int status = ampli_ai_site_status(c, present[i] != 0, k_lo[i], k_hi[i], cnt[i], lo[i], hi[i], prm, &v[i]);
+        const bool tested = status >= AMPLI_AI_TESTED_REF;
+        code[i] = (uint8_t)(status * 8 + (c >= 0 ? c : AMPLI_AI_NO_PAIR));
+        km[2 * i] = tested ? (int32_t)k_lo[i] : 0;
+        km[2 * i + 1] = tested ? (int32_t)(k_lo[i] + k_hi[i]) : 0;
+        int32_t t = 0;
+        q[i] = tested ? ampli_ai_site_score(k_lo[i], k_lo[i] + k_hi[i], v[i], &t) : AMPLI_AI_NA;
+        if (terms) terms[i] = t;
+    }
+    return 0;
+}
+
+extern "C" int ampli_host_allelic_pair(uint32_t plane_bits) { return ampli_ai_pair(plane_bits); }
+
+extern "C" int ampli_host_allelic_site_sums(float q, int32_t k_lo, int32_t m, double v, int64_t *dev16, int64_t *q20)
+{
+    if (!dev16 || !q20) return -1;
+    *dev16 = ampli_ai_dev16(k_lo, m, v);
+    *q20 = ampli_ai_q20(q);
+    return 0;
+}
+
+extern "C" int ampli_host_allelic_region_verdict(const int64_t *sums, int64_t min_sites, double q_min, double min_imbalance, double *Q, double *imbalance)
+{
+    if (!sums || !Q || !imbalance) return -1;
+    return ampli_ai_region_verdict(sums, min_sites, q_min, min_imbalance, Q, imbalance);
+}

@@ -156,6 +156,16 @@ extern "C" {
  *        of a row that a pair names and that lies in the chunk.
  *   (C24) monitoring scores: d_q of ampli_monitor_score is FULLY OVERWRITTEN, all [n_cells][2] scores, AMPLI_MON_NA included.  Nothing
  *        else is written; d_sums is read at [0, 6 n_cells) and d_lambda at [0, 2 n_cells).
+ *   (C25) het-site reference (tests/test_gpu_allelic_contracts.py): ampli_hetsite_reference_records ADDS TO d_ref, all [3][6][P] cells
+ *        and nothing else, with plain loads and stores (one lane owns a position: no atomics); the caller clears it once.  d_planes is
+ *        read at [0, n_samples 6 W'), W' = ceil(P / 64), a record only at a position below P of a row below n_samples.
+ *   (C26) allelic sites: d_q, d_km, d_v and d_code of ampli_allelic_site_records are FULLY OVERWRITTEN, all [n_samples][P] cells
+ *        ([n_samples][P][2] words of d_km), untested cells included (AMPLI_AI_NA, zeros, 0.0, the status), every cell stored exactly
+ *        once.  Nothing else is written -- the other chunks' rows of a larger plane included.  d_row_g is read at [0, n_samples),
+ *        d_planes_g only at rows in [0, n_g), d_ref at [0, 18 P).
+ *   (C27) allelic regions: d_sums of ampli_allelic_region_sums is FULLY OVERWRITTEN, all [S][R][5] sums, empty regions included
+ *        (zeros).  Nothing else is written.  d_reg_off is read at [0, R], d_reg_pos at [0, W) at most, the site planes only at a
+ *        listed position below P of a row below S.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -1012,6 +1022,48 @@ int ampli_monitor_control_records(ampli_ctx *ctx, const ampli_records *recs, int
                                   int32_t R, int32_t first_rep, uint64_t seed, const ampli_monitor_params *prm, int64_t *d_sums /* [n_pairs][R][6] */,
                                   double *d_lambda /* [n_pairs][R][2] */);
 int ampli_monitor_score(ampli_ctx *ctx, const int64_t *d_sums, const double *d_lambda, int64_t n_cells, float *d_q /* [n_cells][2] */);
+
+/*
+ * Allelic imbalance at germline het sites, pooled per region (the definition, in plain numpy, is tests/allelic_model.py): the
+ * companion of the copy ratio -- does a sample show the two alleles of its germline het sites in the share the panel of normals shows?
+ *   Bases A, C, G, T = 0..3; pair code c = 0..5 for (lo, hi) = (A,C), (A,G), (A,T), (C,G), (C,T), (G,T).  A row of genotype planes
+ *     (ampli_genotype_planes_records) is HET AT p WITH PAIR c when its V and H bits are set and exactly two of its A/C/G/T bits;
+ *     anything else -- malformed planes included -- is not a het site.  Only the PRIMARY record of (row, p) enters (slot p < P; extras
+ *     and an RD plane have no effect): k_lo = fw[lo] + bw[lo], k_hi likewise, m = k_lo + k_hi, in int64.
+ *   Stage R.  d_ref int64 [3][6][P] (AMPLI_AI_REF_CNT, _LO, _HI): for every row of the chunk and every position where the row (row i of
+ *     d_planes, the chunk's own planes [n][6][W']) is het with pair c, the record is present and m >= min_depth: CNT[c][p] += 1,
+ *     LO[c][p] += k_lo, HI[c][p] += k_hi.  The call ADDS TO d_ref (C25): the caller clears it once, streamed chunks accumulate.
+ *   Stage S.  Row s takes its germline from plane row g = d_row_g[s] of d_planes_g [n_g][6][W']; a g outside [0, n_g) means "none" and
+ *     is never dereferenced.  Status of (s, p), the first rule that applies: AMPLI_AI_NOT_HET (g is none, or g is not het at p),
+ *     _ABSENT (no record), _SHALLOW (m < min_depth), _DEEP (m > 2^31 - 1); then with c the pair of g at p: _TESTED_REF with
+ *     v = (double)LO / (double)(LO + HI) if CNT[c][p] >= min_normals and LO > 0 and HI > 0; else _TESTED_HALF with v = 0.5 if
+ *     half_fallback; else _NO_REFERENCE.  A tested cell: d = (double)k_lo - v (double)m, formed with two operations; d == 0: q = +0;
+ *     d > 0: p = P[X >= k_lo], X ~ Bin(m, v); d < 0: p = P[X <= k_lo], taken as the upper tail of m - k_lo under 1.0 - v;
+ *     q = (float)(-10 log10(max(min(1, 2 p), 1e-10))) signed by d, +0 where 2 p >= 1 - 1e-8, never -0, |q| <= 100; AMPLI_AI_NA where the tail
+ *     is not computable within its term bound (csrc/ampli_math.h says when: no int32 record's).  Outputs, FULLY OVERWRITTEN for the
+ *     chunk's rows (C26): d_q float [n][P] (AMPLI_AI_NA where untested), d_km int32 [n][P][2] = (k_lo, m) (zeros where untested),
+ *     d_v double [n][P] (0.0 where untested), d_code uint8 [n][P] = status * 8 + pair (pair AMPLI_AI_NO_PAIR = 7 where there is none).
+ *   Stage G.  Regions are a CSR IN DEVICE MEMORY as the amplicons of ampli_amplicon_depth_records: d_reg_off uint32 [R + 1],
+ *     d_reg_pos uint32 [W]; they may overlap, repeat and be empty, an entry >= P is none, offsets are cut to [0, W].  Over the tested
+ *     entries of a region (status >= AMPLI_AI_TESTED_REF and q != AMPLI_AI_NA), in the order AMPLI_AI_*: SITES += 1, SIG += 1 where
+ *     |q| >= site_q, DEPTH += m, DEV16 += llrint(|(double)k_lo - v (double)m| 16.0), Q20 += llrint((double)|q| 1048576.0).  Integer
+ *     additions only: order-free and exact.  d_sums int64 [S][R][5] is FULLY OVERWRITTEN (C27).
+ * Launch shapes: R -- a workgroup per 64-position tile, its four waves take the rows w, w + 4, ...; S -- a wave per (tile, run of up
+ * to 16 rows), all rows classified first, then all of a lane's tested cells in one loop of ampli_ai_step; G -- a wave per (region,
+ * AMPLI_AI_STRIP rows).  No atomics: the same inputs give the same bytes.  All three are asynchronous on the context's stream.
+ * Refusals, every output untouched.  AMPLI_E_INVALID: a null or misaligned pointer (prm is a host pointer), P <= 0, n_g < 1, S < 1,
+ *   R < 1, W < 0, min_depth < 1, min_normals < 1, half_fallback not 0 / 1, site_q < 0 or NaN, broken records.  AMPLI_E_RANGE:
+ *   P >= 2^31; P >= 2^28 with int32 records (R); n_samples > 4194240 (S); S > 2097120, W >= 2^27 (G).
+ * The verdict of a region is decided on the host (ampli_host_allelic_region_verdict, include/amplisolve_host.h).
+ */
+int ampli_hetsite_reference_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint64_t *d_planes /* [n][6][W'] */,
+                                    int32_t min_depth, int64_t *d_ref /* [3][6][P] */);
+int ampli_allelic_site_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const uint64_t *d_planes_g /* [n_g][6][W'] */, int32_t n_g,
+                               const int32_t *d_row_g /* [n] */, const int64_t *d_ref /* [3][6][P] */, const ampli_allelic_params *prm,
+                               float *d_q /* [n][P] */, int32_t *d_km /* [n][P][2] */, double *d_v /* [n][P] */, uint8_t *d_code /* [n][P] */);
+int ampli_allelic_region_sums(ampli_ctx *ctx, const float *d_q, const int32_t *d_km, const double *d_v, const uint8_t *d_code, int32_t S, int64_t P,
+                              int32_t R, const uint32_t *d_reg_off /* [R + 1] */, const uint32_t *d_reg_pos /* [W] */, int64_t W, double site_q,
+                              int64_t *d_sums /* [S][R][5] */);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

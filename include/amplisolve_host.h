@@ -335,6 +335,25 @@ double ampli_host_monitor_empirical_p(int64_t n_ge, int64_t R);
 int64_t ampli_host_monitor_lod_reads(double lam, double q_min, int32_t *evals);
 double ampli_host_monitor_lod(double lam_fw, double lam_bw, int64_t D_fw, int64_t D_bw, double q_min);
 
+/* Allelic imbalance at germline het sites (the definition is tests/allelic_model.py, in full in include/amplisolve_hip.h):
+ * csrc/ampli_math.h's functions, so that every status, share and score is pinned without a GPU.
+ * _allelic_site_batch: the site stage for n cells given apart: pair (the germline's pair code 0..5, anything else: not het), present,
+ *   the reads k_lo and k_hi of the pair's two bases, and the reference's CNT, LO and HI of (pair, position).  q, km [n][2], v and code
+ *   as ampli_allelic_site_records stores them; terms (optional) = pmf terms formed per cell.  Returns 0, or -1 with nothing written
+ *   for a null pointer, n < 0 or parameters the device entry point refuses.
+ * _allelic_pair: the pair code of six plane bits (V, A, C, G, T, H = bits 0..5), -1 where the bits are not a het site.
+ * _allelic_site_sums: what a tested cell adds to DEV16 and Q20 of a region.
+ * _allelic_region_verdict: AMPLI_AI_FEW if SITES < max(min_sites, 1); else X = (ln 10 / 5) (Q20 / 2^20), p = kf_gammaq(SITES, X / 2)
+ *   (Fisher's combination: chi-square with 2 SITES degrees of freedom), *Q = 0 for p >= 1, -10 log10(p) for p > 1e-30, else 300;
+ *   *imbalance = DEV16 / (16 DEPTH); AMPLI_AI_IMBALANCED iff *Q >= q_min and *imbalance >= min_imbalance, else AMPLI_AI_BALANCED.  *Q is
+ *   NaN for FEW, *imbalance NaN where DEPTH is 0.  -1 for a null pointer. */
+int ampli_host_allelic_site_batch(int64_t n, const int32_t *pair, const uint8_t *present, const int64_t *k_lo, const int64_t *k_hi, const int64_t *cnt,
+                                  const int64_t *lo, const int64_t *hi, const ampli_allelic_params *prm, float *q, int32_t *km, double *v, uint8_t *code,
+                                  int32_t *terms);
+int ampli_host_allelic_pair(uint32_t plane_bits);
+int ampli_host_allelic_site_sums(float q, int32_t k_lo, int32_t m, double v, int64_t *dev16, int64_t *q20);
+int ampli_host_allelic_region_verdict(const int64_t *sums /* [5] */, int64_t min_sites, double q_min, double min_imbalance, double *Q, double *imbalance);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */

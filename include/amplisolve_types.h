@@ -154,4 +154,37 @@ typedef struct ampli_monitor_params {
     int32_t coverage_cutoff, max_vaf_pm;
 } ampli_monitor_params;
 
+/* Allelic imbalance at germline het sites: the three int64 planes of the het-site reference [3][6][P], the status of a
+ * (sample, position) -- stored as status * 8 + pair code, the pair code 7 where there is none --, the score of a cell that is not
+ * tested (a tail that is not computable within its term bound gets it too), the order of the five int64 sums of a (sample, region),
+ * the rows a wave of allelic_region_kernel owns, the verdict of a region, and the parameters of the site stage (min_depth >= 1,
+ * min_normals >= 1, half_fallback 0 / 1). */
+#define AMPLI_AI_REF_CNT 0
+#define AMPLI_AI_REF_LO 1
+#define AMPLI_AI_REF_HI 2
+#define AMPLI_AI_REF_PLANES 3
+#define AMPLI_AI_PAIRS 6
+#define AMPLI_AI_NO_PAIR 7
+#define AMPLI_AI_NOT_HET 0
+#define AMPLI_AI_ABSENT 1
+#define AMPLI_AI_SHALLOW 2
+#define AMPLI_AI_DEEP 3
+#define AMPLI_AI_NO_REFERENCE 4
+#define AMPLI_AI_TESTED_REF 5
+#define AMPLI_AI_TESTED_HALF 6
+#define AMPLI_AI_NA (-999.0f)
+#define AMPLI_AI_SITES 0
+#define AMPLI_AI_SIG 1
+#define AMPLI_AI_DEPTH 2
+#define AMPLI_AI_DEV16 3
+#define AMPLI_AI_Q20 4
+#define AMPLI_AI_SUMS 5
+#define AMPLI_AI_STRIP 8
+#define AMPLI_AI_FEW 0
+#define AMPLI_AI_BALANCED 1
+#define AMPLI_AI_IMBALANCED 2
+typedef struct ampli_allelic_params {
+    int32_t min_depth, min_normals, half_fallback;
+} ampli_allelic_params;
+
 #endif /* AMPLISOLVE_TYPES_H */
