@@ -9,73 +9,58 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import AccTable, AllelicParams, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, MonitorParams, Records, hip_lib
+from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, MonitorParams, Records,
+                   hip_lib)
 
+# Every numeric AMPLI_X of the headers is this module's X, with the header's value (_lib.CONSTANTS).  Which family goes with what:
+#   POISSON_FULL / _PREFILTER              the mode of poisson_call, poisson_call_records and loo_call
+#   CALL_SHARDS, CALL_COUNTER_*            the compact call list (read_calls, read_loo_calls, n_calls_total)
+#   RECORDS_*                              the record layouts (Context.LAYOUTS)
+#   LIMIT_*                                detection_limits: status in bits 0-2, LIMIT_CALLED, LIMIT_RECHECK, the counters
+#   DISPERSION_*                           panel_dispersion's status
+#   GENO_PLANES, RELATION_*                genotype_planes, and the relation of ampli_host_concordance_relation
+#   CONTAM_*                               the nine sums of contamination
+#   AMP_*, AMPLICON_*, GENE_*              the four sums of amplicon_depth; amplicon_reference's statuses, the limit of N / A in the two
+#                                          stage-2 calls and the rows a wave of the depth kernel owns; ampli_host_amplicon_gene_status
+#   SPEC_*, SPECTRUM_*                     the nine sums of spectrum; its limit of C, the rows of a workgroup, the classes, types and
+#                                          channels of the command line's folds and the statuses of ampli_host_spectrum_score
+#   EXCEEDANCE_*                           exceedance: the cell that is not evaluated, the most normals of a panel, the launch shape
+#   NB_NA, PAIR_NA, FDR_NA                 a cell of nb_score / pair_score that is not evaluated, of fdr_adjust that is not tested
+#   DILUTE_BAD_*                           the flag word of a mixture of dilute
+#   MON_*                                  the six sums of monitor_sums, the score without an evaluated entry, the verdicts, the strip
+#   AI_*                                   allelic imbalance: the planes of the het-site reference, the status of a cell (code = status *
+#                                          8 + pair, AI_NO_PAIR: none), the untested score, the five sums of a region and the verdicts
+globals().update({name[len("AMPLI_"):]: value for name, value in CONSTANTS.items()})
+
+# Python's own
 NT = "ACGT"
-POISSON_FULL = 0
-POISSON_PREFILTER = 1
-CALL_SHARDS = 32            # AMPLI_CALL_SHARDS
-CALL_COUNTER_STRIDE = 16    # AMPLI_CALL_COUNTER_STRIDE
-CALL_COUNTER_WORDS = CALL_SHARDS * CALL_COUNTER_STRIDE
-# AMPLI_LIMIT_* of include/amplisolve_hip.h (Context.detection_limits)
-LIMIT_OK, LIMIT_REF, LIMIT_NOREF, LIMIT_LOWDEPTH, LIMIT_NOESTIMATE, LIMIT_UNREACHABLE, LIMIT_ABSENT = range(7)
-LIMIT_CALLED, LIMIT_RECHECK = 0x40, 0x80
-LIMIT_COUNTERS = 6
-# AMPLI_DISPERSION_* (Context.panel_dispersion)
-DISPERSION_OK, DISPERSION_FEW, DISPERSION_HIGH = 0, 1, 0x40
-# the planes of Context.genotype_planes (AMPLI_GENO_*: bit k of a classified record is plane k), the counts of Context.concordance
-# and AMPLI_RELATION_* of ampli_host_concordance_relation
-GENO_PLANES = 6
-GENO_V, GENO_A, GENO_C, GENO_G, GENO_T, GENO_H = range(6)
-CONC_SITES, CONC_MATCH, CONC_IBS0, CONC_HET_EITHER, CONC_HET_MATCH = range(5)
-RELATION_UNDETERMINED, RELATION_SAME, RELATION_DIFFERENT = range(3)
-# the nine sums of Context.contamination (AMPLI_CONTAM_*) and AMPLI_CONTAM_STATUS_* of ampli_host_contamination_estimate
-CONTAM_SUMS = 9
-(CONTAM_SITES_HOM, CONTAM_ALT_HOM, CONTAM_DEPTH_HOM, CONTAM_SITES_HET, CONTAM_ALT_HET, CONTAM_DEPTH_HET, CONTAM_SITES_BG, CONTAM_ALT_BG,
- CONTAM_DEPTH_BG) = range(9)
-CONTAM_UNDETERMINED, CONTAM_CLEAN, CONTAM_CONTAMINATED = range(3)
-# the four sums of Context.amplicon_depth (AMPLI_AMP_*), the amplicon statuses of Context.amplicon_reference (AMPLI_AMPLICON_*), the
-# limit of N / A in the two stage-2 calls, the rows a wave of the depth kernel owns, and AMPLI_GENE_* of ampli_host_amplicon_gene_status
-AMP_SUMS = 4
-AMP_PRESENT, AMP_DEPTH_FW, AMP_DEPTH_BW, AMP_CALLABLE = range(4)
-AMPLICON_OK, AMPLICON_FEW, AMPLICON_DARK = range(3)
-AMPLICON_MAX = 4096
-AMPLICON_STRIP = 8
-GENE_NEUTRAL, GENE_GAIN, GENE_LOSS = range(3)
-# the nine sums of Context.spectrum (AMPLI_SPEC_*), its limit of C and the rows a workgroup of the kernel owns, the classes, types and
-# channels of the command line's folds, and AMPLI_SPECTRUM_* of ampli_host_spectrum_score
-SPEC_SUMS = 9
-SPEC_SITES, SPEC_FW_A, SPEC_FW_C, SPEC_FW_G, SPEC_FW_T, SPEC_BW_A, SPEC_BW_C, SPEC_BW_G, SPEC_BW_T = range(9)
-SPECTRUM_MAX_CLASSES = 128
-SPECTRUM_STRIP = 4
-SPECTRUM_SKIP = 255
-SPECTRUM_CLASSES, SPECTRUM_TYPES, SPECTRUM_ALL, SPECTRUM_CHANNELS = 68, 13, 12, 96
-SPECTRUM_OK, SPECTRUM_LOW_SITES, SPECTRUM_NO_REFERENCE, SPECTRUM_ELEVATED, SPECTRUM_ASYMMETRIC = range(5)
-SPECTRUM_REF_OK, SPECTRUM_REF_FEW = range(2)
-# Context.exceedance (AMPLI_EXCEEDANCE_*): the value of a cell that is not evaluated, the most normals of a panel, the normal rows the
-# kernel decodes into LDS at a time and the tumour rows of one of its workgroups
-EXCEEDANCE_NA = 0xFFFF
-EXCEEDANCE_MAX_NORMALS = 65534
-EXCEEDANCE_STRIP = 8
-EXCEEDANCE_ROWS = 8
-NB_NA = -1.0  # a cell of nb_score that is not evaluated (AMPLI_NB_NA)
-PAIR_NA = -999.0  # a cell of pair_score that is not evaluated (AMPLI_PAIR_NA)
-FDR_NA = -999.0  # a cell of fdr_adjust that is not tested (AMPLI_FDR_NA)
-DILUTE_BAD_COUNT, DILUTE_BAD_MIXTURE = 1, 2  # the flag word of a mixture of dilute (AMPLI_DILUTE_BAD_*)
-DILUTE_KEEP_ALL = 1 << 32  # the threshold that keeps every read
-# the six sums of Context.monitor_sums (AMPLI_MON_*), the score of a cell without an evaluated entry, the verdicts and the strip of rows
-MON_N_EVAL, MON_N_SEEN, MON_K_FW, MON_K_BW, MON_D_FW, MON_D_BW, MON_SUMS = 0, 1, 2, 3, 4, 5, 6
-MON_NA = -1.0
-MON_NOT_EVALUABLE, MON_NOT_DETECTED, MON_DETECTED = 0, 1, 2
-MON_STRIP = 8
-# allelic imbalance (AMPLI_AI_*): the planes of the het-site reference, the status of a cell (code = status * 8 + pair, pair 7: none), the
-# score of an untested cell, the five sums of a (sample, region) and the verdicts
-AI_REF_CNT, AI_REF_LO, AI_REF_HI = 0, 1, 2
-AI_NOT_HET, AI_ABSENT, AI_SHALLOW, AI_DEEP, AI_NO_REFERENCE, AI_TESTED_REF, AI_TESTED_HALF = 0, 1, 2, 3, 4, 5, 6
-AI_NO_PAIR = 7
-AI_NA = -999.0
-AI_SITES, AI_SIG, AI_DEPTH, AI_DEV16, AI_Q20, AI_SUMS = 0, 1, 2, 3, 4, 5
-AI_FEW, AI_BALANCED, AI_IMBALANCED = 0, 1, 2
+GENO_V, GENO_A, GENO_C, GENO_G, GENO_T, GENO_H = (CONSTANTS["AMPLI_GENO_" + x].bit_length() - 1 for x in "VACGTH")  # planes: the headers hold the bits
+CONC_SITES, CONC_MATCH, CONC_IBS0, CONC_HET_EITHER, CONC_HET_MATCH = range(5)  # the counts of Context.concordance
+CONTAM_UNDETERMINED, CONTAM_CLEAN, CONTAM_CONTAMINATED = (CONSTANTS["AMPLI_CONTAM_STATUS_" + x] for x in ("UNDETERMINED", "CLEAN", "CONTAMINATED"))
+DILUTE_KEEP_ALL = 1 << 32  # the threshold of dilute that keeps every read
+
+
+def _ok(t, dtype, shape=None) -> bool:
+    """Is t a contiguous device tensor of dtype and shape?  None in shape is an axis of any size, a leading ... any leading axes."""
+    if not (t.dtype == dtype and t.is_cuda and t.is_contiguous()):
+        return False
+    if shape is None:
+        return True
+    have = tuple(t.shape)
+    if shape and shape[0] is ...:
+        shape = shape[1:]
+        have = have[len(have) - len(shape):]
+    return len(have) == len(shape) and all(want is None or want == got for want, got in zip(shape, have))
+
+
+def _fields(struct):
+    """the members of a ctypes struct as a flat numpy field list, a nested struct's in its place"""
+    import numpy as np
+
+    out = []
+    for name, t in struct._fields_:
+        out += _fields(t) if issubclass(t, C.Structure) else [(name, np.dtype(t))]
+    return out
 
 
 def _ptr(t):
@@ -182,8 +167,81 @@ class Context:
     def sync(self):
         self._check(self.lib.ampli_sync(self.h))
 
-    # ---- record layout (include/amplisolve_hip.h: AMPLI_RECORDS_I32 / AMPLI_RECORDS_U16) ----
-    LAYOUTS = {"i32": 0, "u16": 1, "u24": 2}
+    # ---- what the methods below share -------------------------------------------------------
+    def _out(self, t, dtype, shape, zero: bool = False):
+        """the caller's buffer or a new one (zeroed where the kernel adds to it), checked either way"""
+        import torch
+
+        if t is None:
+            t = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self.device)
+        assert _ok(t, dtype, shape)
+        return t
+
+    def _csr(self, off, ent, max_len: int, bound: int):
+        """Position lists as a CSR on the device: (off int32 [n + 1], ent int32 [W] -- both read as uint32 --, W).  Host arrays are
+        checked (monotone offsets, fewer than max_len entries, each in [0, bound)) and uploaded; device tensors are taken as they are."""
+        import numpy as np
+        import torch
+
+        if not isinstance(off, torch.Tensor):
+            o, e = np.asarray(off, np.int64), np.asarray(ent, np.int64)
+            assert o.ndim == 1 and len(o) >= 2 and o[0] >= 0 and (np.diff(o) >= 0).all() and o[-1] <= len(e) < max_len
+            assert ((e >= 0) & (e < bound)).all()
+            off = torch.from_numpy(o.astype(np.uint32).view(np.int32)).to(self.device)
+            ent = torch.from_numpy((e if len(e) else np.zeros(1, np.int64)).astype(np.uint32).view(np.int32)).to(self.device)
+            W = len(e)
+        else:
+            W = ent.numel()
+            if W == 0:  # a pointer is required even where nothing is read through it
+                ent = torch.zeros((1,), dtype=torch.int32, device=self.device)
+        assert _ok(off, torch.int32, (None,)) and _ok(ent, torch.int32, (None,))
+        return off, ent, W
+
+    def _positions_u8(self, x, P: int):
+        """uint8 [P] on the device (ref_code, a class per position): a device tensor, or a host array, which is checked and uploaded"""
+        import numpy as np
+        import torch
+
+        if not isinstance(x, torch.Tensor):
+            x = np.asarray(x)
+            assert x.dtype == np.uint8 and x.shape == (P,)
+            x = torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        assert _ok(x, torch.uint8, (P,))
+        return x
+
+    def _call_list(self, rows: int, R: int, entry, capacity: int, call_mask, calls_buf, n_calls):
+        """What the caller did not bring of a compact call list: the mask [rows, R] in a buffer of whole 4-byte words, room for
+        `capacity` entries, the shard counters.  Returns them with the capacity cut to whole shards."""
+        import torch
+
+        d = self.device
+        if call_mask is None:
+            call_mask = torch.empty(((rows * R + 3) // 4 * 4,), dtype=torch.uint8, device=d)[: rows * R].view(rows, R)
+        if capacity > 0 and calls_buf is None:
+            calls_buf = torch.empty((capacity * C.sizeof(entry),), dtype=torch.uint8, device=d)
+        if capacity > 0:
+            capacity -= capacity % CALL_SHARDS
+        if capacity > 0 and n_calls is None:
+            n_calls = torch.zeros((CALL_COUNTER_WORDS,), dtype=torch.int64, device=d)
+        return call_mask, calls_buf, capacity, n_calls
+
+    def _read_list(self, res, entry):
+        """the compact list of `entry` structs on the host, sorted by (sample, record, alt): a numpy record array of the struct's members"""
+        import numpy as np
+
+        counts = res["n_calls"][::CALL_COUNTER_STRIDE].cpu().numpy()
+        per = res["capacity"] // CALL_SHARDS
+        if (counts > per).any():
+            raise AmpliError(f"call list segment overflowed: {int(counts.max())} > {per}; rerun with a larger capacity")
+        sz = C.sizeof(entry)
+        raw = b"".join(res["calls_buf"][k * per * sz: (k * per + int(counts[k])) * sz].cpu().numpy().tobytes() for k in range(CALL_SHARDS))
+        dt = np.dtype(_fields(entry))
+        assert dt.itemsize == sz
+        a = np.frombuffer(raw, dtype=dt)
+        return a[np.lexsort((a["alt"], a["record"], a["sample"]))]
+
+    # ---- record layout (include/amplisolve_hip.h: AMPLI_RECORDS_*) ----
+    LAYOUTS = {"i32": RECORDS_I32, "u16": RECORDS_U16, "u24": RECORDS_U24}
 
     def _rec_dtype(self):
         import torch
@@ -206,7 +264,7 @@ class Context:
         """int32 [S, R, 8] records -> (int16 [S, R, 8] records, fits): fits is False when a count exceeds 65534."""
         import torch
 
-        assert recs.dtype == torch.int32 and recs.is_cuda and recs.is_contiguous() and recs.shape[-1] == 8
+        assert _ok(recs, torch.int32, (..., 8))
         out = torch.empty(recs.shape, dtype=torch.int16, device=recs.device)
         over = torch.zeros((1,), dtype=torch.int32, device=recs.device)
         self._check(self.lib.ampli_records_pack16(self.h, _ptr(recs), recs.numel() // 8, _ptr(out), _ptr(over)))
@@ -216,7 +274,7 @@ class Context:
         """int32 [S, R, 8] records -> (uint8 [S, R, 24] records, fits): fits is False when a count exceeds 2^24 - 2."""
         import torch
 
-        assert recs.dtype == torch.int32 and recs.is_cuda and recs.is_contiguous() and recs.shape[-1] == 8
+        assert _ok(recs, torch.int32, (..., 8))
         out = torch.empty(tuple(recs.shape[:-1]) + (24,), dtype=torch.uint8, device=recs.device)
         over = torch.zeros((1,), dtype=torch.int32, device=recs.device)
         self._check(self.lib.ampli_records_pack24(self.h, _ptr(recs), recs.numel() // 8, _ptr(out), _ptr(over)))
@@ -314,9 +372,7 @@ class Context:
 
     def error_reduce(self, recs, P: int, C_value: float = 0.002, cov: int = 100, E: int = 0, dup_off=None,
                      first_sample: int = 0, acc: Acc | None = None) -> Acc:
-        import torch
-
-        assert recs.dtype == self._rec_dtype() and recs.is_cuda and recs.is_contiguous()
+        assert _ok(recs, self._rec_dtype())
         S = recs.shape[0]
         assert recs.numel() == S * (P + E) * self._rec_elems()
         if acc is None:
@@ -366,18 +422,7 @@ class Context:
     def poisson_call_records(self, rec: Records, P: int, thr, ref_code, cov: int = 100, mode: int = POISSON_PREFILTER,
                              call_mask=None, capacity: int = 0, calls_buf=None, n_calls=None, q=None, af=None):
         """q / af: the caller's buffers for the dense scores (float64 [T, R, 4, 2], all-scores mode only) and VAFs (float32 [T, R, 4, 3])"""
-        import torch
-
-        T, R = rec.n_samples, P + rec.E
-        d = self.device
-        if call_mask is None:
-            call_mask = torch.empty(((T * R + 3) // 4 * 4,), dtype=torch.uint8, device=d)[: T * R].view(T, R)
-        if capacity > 0 and calls_buf is None:
-            calls_buf = torch.empty((capacity * C.sizeof(Call),), dtype=torch.uint8, device=d)
-        if capacity > 0:
-            capacity -= capacity % CALL_SHARDS
-        if (capacity > 0 or n_calls is not None) and n_calls is None:
-            n_calls = torch.zeros((CALL_COUNTER_WORDS,), dtype=torch.int64, device=d)
+        call_mask, calls_buf, capacity, n_calls = self._call_list(rec.n_samples, P + rec.E, Call, capacity, call_mask, calls_buf, n_calls)
         self._check(self.lib.ampli_poisson_call_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), cov, mode, _ptr(call_mask),
                                                         _ptr(calls_buf), capacity, _ptr(n_calls), _ptr(q), _ptr(af)))
         return dict(call_mask=call_mask, q=q, af=af, calls_buf=calls_buf, n_calls=n_calls, capacity=capacity)
@@ -482,9 +527,7 @@ class Context:
         import torch
 
         n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
-        if out is None:
-            out = torch.empty((n, GENO_PLANES, W), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, GENO_PLANES, W)
+        out = self._out(out, torch.int64, (n, GENO_PLANES, W))
         prm = GenotypeParams(min_depth, absent_max_pm, het_min_pm, het_max_pm, hom_min_pm)
         self._check(self.lib.ampli_genotype_planes_records(self.h, C.byref(rec), P, C.byref(prm), _ptr(out)))
         return out
@@ -495,8 +538,7 @@ class Context:
         import torch
 
         W = int(self.lib.ampli_concordance_words(P))
-        for t in (planes_a, planes_b):
-            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and tuple(t.shape[1:]) == (GENO_PLANES, W)
+        assert _ok(planes_a, torch.int64, (None, GENO_PLANES, W)) and _ok(planes_b, torch.int64, (None, GENO_PLANES, W))
         n_a, n_b = planes_a.shape[0], planes_b.shape[0]
         out = torch.empty((n_a, n_b, 5), dtype=torch.int32, device=self.device)
         self._check(self.lib.ampli_concordance_pairs(self.h, P, _ptr(planes_a), n_a, _ptr(planes_b), n_b, _ptr(out)))
@@ -510,13 +552,10 @@ class Context:
         import torch
 
         n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
-        for t in (planes_a, planes_b):
-            assert t.dtype == torch.int64 and t.is_cuda and t.is_contiguous() and tuple(t.shape[1:]) == (GENO_PLANES, W)
+        assert _ok(planes_a, torch.int64, (None, GENO_PLANES, W)) and _ok(planes_b, torch.int64, (None, GENO_PLANES, W))
         assert planes_a.shape[0] == n
         n_b = planes_b.shape[0]
-        if out is None:
-            out = torch.empty((n, n_b, CONTAM_SUMS), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, n_b, CONTAM_SUMS)
+        out = self._out(out, torch.int64, (n, n_b, CONTAM_SUMS))
         self._check(self.lib.ampli_contamination_records(self.h, C.byref(rec), P, _ptr(planes_a), _ptr(planes_b), n_b, _ptr(out)))
         return out
 
@@ -525,26 +564,11 @@ class Context:
         DESIGN 16).  amp_off [A + 1] and amp_pos [W] are the amplicons' position lists, a CSR over the BED walk with entries in [0, P):
         device int32 tensors (read as uint32) or host arrays, which are checked (monotone, in range) and uploaded.  Only the primary
         records enter.  out: the chunk's rows of a larger matrix (a contiguous int64 [n, A, 4] view), overwritten."""
-        import numpy as np
         import torch
 
-        if not isinstance(amp_off, torch.Tensor):
-            off, pos = np.asarray(amp_off, np.int64), np.asarray(amp_pos, np.int64)
-            assert off.ndim == 1 and len(off) >= 2 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= len(pos) < 1 << 28
-            assert ((pos >= 0) & (pos < P)).all()
-            amp_off = torch.from_numpy(off.astype(np.int32)).to(self.device)
-            amp_pos = torch.from_numpy((pos if len(pos) else np.zeros(1, np.int64)).astype(np.int32)).to(self.device)
-            W = len(pos)
-        else:
-            W = amp_pos.numel()
-            if W == 0:  # a pointer is required even where nothing is read through it
-                amp_pos = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        for t in (amp_off, amp_pos):
-            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+        amp_off, amp_pos, W = self._csr(amp_off, amp_pos, 1 << 28, P)
         n, A = rec.n_samples, amp_off.numel() - 1
-        if out is None:
-            out = torch.empty((n, A, AMP_SUMS), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, A, AMP_SUMS)
+        out = self._out(out, torch.int64, (n, A, AMP_SUMS))
         self._check(self.lib.ampli_amplicon_depth_records(self.h, C.byref(rec), P, A, _ptr(amp_off), _ptr(amp_pos), W, cov, _ptr(out)))
         return out
 
@@ -554,9 +578,9 @@ class Context:
         (ampli_amplicon_reference)."""
         import torch
 
-        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and sums.dim() == 3 and sums.shape[2] == AMP_SUMS
+        assert _ok(sums, torch.int64, (None, None, AMP_SUMS))
         N, A = sums.shape[0], sums.shape[1]
-        assert use.dtype == torch.uint8 and use.is_cuda and use.is_contiguous() and tuple(use.shape) == (A,)
+        assert _ok(use, torch.uint8, (A,))
         total = torch.empty((N,), dtype=torch.int64, device=self.device)
         ref = torch.empty((A, 2), dtype=torch.float64, device=self.device)
         status = torch.empty((A,), dtype=torch.uint8, device=self.device)
@@ -568,12 +592,11 @@ class Context:
         total int64 [S], centre float64 [S], k int32 [S], ratio and z float64 [S, A] (ampli_amplicon_ratio)."""
         import torch
 
-        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and sums.dim() == 3 and sums.shape[2] == AMP_SUMS
+        assert _ok(sums, torch.int64, (None, None, AMP_SUMS))
         S, A = sums.shape[0], sums.shape[1]
-        assert use.dtype == torch.uint8 and use.is_cuda and use.is_contiguous() and tuple(use.shape) == (A,)
+        assert _ok(use, torch.uint8, (A,))
         r, st = ref["ref"], ref["status"]
-        assert r.dtype == torch.float64 and r.is_cuda and r.is_contiguous() and tuple(r.shape) == (A, 2)
-        assert st.dtype == torch.uint8 and st.is_cuda and st.is_contiguous() and tuple(st.shape) == (A,)
+        assert _ok(r, torch.float64, (A, 2)) and _ok(st, torch.uint8, (A,))
         total = torch.empty((S,), dtype=torch.int64, device=self.device)
         centre = torch.empty((S,), dtype=torch.float64, device=self.device)
         k = torch.empty((S,), dtype=torch.int32, device=self.device)
@@ -590,23 +613,10 @@ class Context:
         primary records enter.  out: the chunk's rows of a larger matrix (a contiguous int64 [n, C, 9] view), overwritten."""
         import ctypes  # the module's alias C is this method's number of classes
 
-        import numpy as np
         import torch
 
-        def dev(x):
-            if isinstance(x, torch.Tensor):
-                return x
-            x = np.asarray(x)
-            assert x.dtype == np.uint8 and x.shape == (P,)
-            return torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
-
-        ref_code, cls = dev(ref_code), dev(cls)
-        for t in (ref_code, cls):
-            assert t.dtype == torch.uint8 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (P,)
-        n = rec.n_samples
-        if out is None:
-            out = torch.empty((n, C, SPEC_SUMS), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n, C, SPEC_SUMS)
+        ref_code, cls = self._positions_u8(ref_code, P), self._positions_u8(cls, P)
+        out = self._out(out, torch.int64, (rec.n_samples, C, SPEC_SUMS))
         self._check(self.lib.ampli_spectrum_records(self.h, ctypes.byref(rec), P, _ptr(ref_code), _ptr(cls), C, cov, max_alt_pm, _ptr(out)))
         return out
 
@@ -624,22 +634,13 @@ class Context:
         elig and ge of the earlier chunks, which must then be given."""
         import ctypes
 
-        import numpy as np
         import torch
 
-        if not isinstance(ref_code, torch.Tensor):
-            ref_code = np.asarray(ref_code)
-            assert ref_code.dtype == np.uint8 and ref_code.shape == (P,)
-            ref_code = torch.from_numpy(np.ascontiguousarray(ref_code)).to(self.device)
-        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        ref_code = self._positions_u8(ref_code, P)
         n_t = tumours.n_samples
         assert not accumulate or (elig is not None and ge is not None), "accumulate adds onto the outputs of the earlier chunks"
-        if elig is None:
-            elig = torch.empty((n_t, P), dtype=torch.int16, device=self.device)
-        if ge is None:
-            ge = torch.empty((n_t, P, 4, 2), dtype=torch.int16, device=self.device)
-        assert elig.dtype == torch.int16 and elig.is_cuda and elig.is_contiguous() and tuple(elig.shape) == (n_t, P)
-        assert ge.dtype == torch.int16 and ge.is_cuda and ge.is_contiguous() and tuple(ge.shape) == (n_t, P, 4, 2)
+        elig = self._out(elig, torch.int16, (n_t, P))
+        ge = self._out(ge, torch.int16, (n_t, P, 4, 2))
         self._check(self.lib.ampli_exceedance_records(self.h, ctypes.byref(tumours), ctypes.byref(normals), P, _ptr(ref_code), normal_cutoff, calling_cutoff,
                                                       first_t, first_n, int(bool(skip_same_index)), int(bool(accumulate)), _ptr(elig), _ptr(ge)))
         return elig, ge
@@ -653,9 +654,7 @@ class Context:
         if isinstance(chunks, Records):
             chunks = [chunks]
         assert not accumulate or s2 is not None, "accumulate adds onto the sums of the earlier chunks"
-        if s2 is None:
-            s2 = torch.empty((2, 4, P), dtype=torch.float64, device=self.device)
-        assert s2.dtype == torch.float64 and s2.is_cuda and s2.is_contiguous() and tuple(s2.shape) == (2, 4, P)
+        s2 = self._out(s2, torch.float64, (2, 4, P))
         for i, rec in enumerate(chunks):
             self._check(self.lib.ampli_overdispersion_records(self.h, C.byref(rec), P, C.byref(acc0.struct), cov, _ptr(s2),
                                                               int(bool(accumulate) or i > 0)))
@@ -666,10 +665,8 @@ class Context:
         (ampli_overdispersion_finalize): 0 in every cell that is not DISPERSION_HIGH."""
         import torch
 
-        if omega is None:
-            omega = torch.empty((2, 4, P), dtype=torch.float64, device=self.device)
-        for t, dt in ((x2, torch.float64), (s2, torch.float64), (status, torch.uint8), (omega, torch.float64)):
-            assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (2, 4, P)
+        omega = self._out(omega, torch.float64, (2, 4, P))
+        assert _ok(x2, torch.float64, (2, 4, P)) and _ok(s2, torch.float64, (2, 4, P)) and _ok(status, torch.uint8, (2, 4, P))
         self._check(self.lib.ampli_overdispersion_finalize(self.h, P, C.byref(acc0.struct), _ptr(x2), _ptr(s2), _ptr(status), _ptr(omega)))
         return omega
 
@@ -680,12 +677,10 @@ class Context:
         import torch
 
         n_t = tumours.n_samples
-        if q is None:
-            q = torch.empty((n_t, P, 4, 2), dtype=torch.float32, device=self.device)
-        assert q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == (n_t, P, 4, 2)
-        assert thr.dtype == torch.float32 and thr.is_cuda and thr.is_contiguous() and thr.numel() == 8 * P
-        assert omega is None or (omega.dtype == torch.float64 and omega.is_cuda and omega.is_contiguous() and omega.numel() == 8 * P)
-        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        q = self._out(q, torch.float32, (n_t, P, 4, 2))
+        assert _ok(thr, torch.float32) and thr.numel() == 8 * P
+        assert omega is None or (_ok(omega, torch.float64) and omega.numel() == 8 * P)
+        assert _ok(ref_code, torch.uint8, (P,))
         self._check(self.lib.ampli_nb_score_records(self.h, C.byref(tumours), P, _ptr(thr), _ptr(omega), _ptr(ref_code), calling_cutoff, _ptr(q)))
         return q
 
@@ -696,12 +691,10 @@ class Context:
         index outside its chunk makes the pair all NA.  ref_code: uint8 [P]."""
         import torch
 
-        assert pairs.dtype == torch.int32 and pairs.is_cuda and pairs.is_contiguous() and pairs.dim() == 2 and pairs.shape[1] == 2
+        assert _ok(pairs, torch.int32, (None, 2))
         n_pairs = int(pairs.shape[0])
-        if s is None:
-            s = torch.empty((n_pairs, P, 4, 2), dtype=torch.float32, device=self.device)
-        assert s.dtype == torch.float32 and s.is_cuda and s.is_contiguous() and tuple(s.shape) == (n_pairs, P, 4, 2)
-        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        s = self._out(s, torch.float32, (n_pairs, P, 4, 2))
+        assert _ok(ref_code, torch.uint8, (P,))
         self._check(self.lib.ampli_pair_score_records(self.h, C.byref(recs_a), C.byref(recs_b), P, _ptr(pairs), n_pairs, _ptr(ref_code),
                                                       depth_cutoff, _ptr(s)))
         return s
@@ -724,12 +717,8 @@ class Context:
             host = torch.frombuffer(bytearray(bytes((DiluteMix * len(rows))(*rows))), dtype=torch.uint8)
             d_mix = host.view(len(rows), C.sizeof(DiluteMix)).to(self.device)
         n_mix = int(d_mix.shape[0])
-        if out is None:
-            out = torch.empty((n_mix, P, 8), dtype=torch.int32, device=self.device)
-        if flags is None:
-            flags = torch.empty((n_mix,), dtype=torch.int32, device=self.device)
-        assert out.dtype == torch.int32 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (n_mix, P, 8)
-        assert flags.dtype == torch.int32 and flags.is_cuda and flags.is_contiguous() and tuple(flags.shape) == (n_mix,)
+        out = self._out(out, torch.int32, (n_mix, P, 8))
+        flags = self._out(flags, torch.int32, (n_mix,))
         self._check(self.lib.ampli_dilute_records(self.h, C.byref(recs_a), C.byref(recs_b) if recs_b is not None else None, P, _ptr(d_mix), n_mix,
                                                   _ptr(out), _ptr(flags)))
         return out, flags
@@ -738,24 +727,11 @@ class Context:
         """the arguments the two monitoring gathers share: (thr, ref_code, list_off, list_cell, L, W) on the device.  Host lists are
         checked (monotone offsets, cells that fit 32 bits -- an entry at or beyond P is none, by the definition) and uploaded; device lists
         are taken as they are (the kernels cut them)."""
-        import numpy as np
         import torch
 
-        if not isinstance(list_off, torch.Tensor):
-            off, cell = np.asarray(list_off, np.int64), np.asarray(list_cell, np.int64)
-            assert off.ndim == 1 and len(off) >= 2 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= len(cell) < 1 << 28
-            assert ((cell >= 0) & (cell < 1 << 32)).all()
-            list_off = torch.from_numpy(off.astype(np.uint32).view(np.int32)).to(self.device)
-            list_cell = torch.from_numpy((cell if len(cell) else np.zeros(1, np.int64)).astype(np.uint32).view(np.int32)).to(self.device)
-            W = len(cell)
-        else:
-            W = list_cell.numel()
-            if W == 0:  # a pointer is required even where nothing is read through it
-                list_cell = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        for t in (list_off, list_cell):
-            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.dim() == 1
-        assert thr.dtype == torch.float32 and thr.is_cuda and thr.is_contiguous() and thr.numel() == 8 * P
-        assert ref_code.dtype == torch.uint8 and ref_code.is_cuda and ref_code.is_contiguous() and tuple(ref_code.shape) == (P,)
+        list_off, list_cell, W = self._csr(list_off, list_cell, 1 << 28, 1 << 32)
+        assert _ok(thr, torch.float32) and thr.numel() == 8 * P
+        assert _ok(ref_code, torch.uint8, (P,))
         return thr, ref_code, list_off, list_cell, list_off.numel() - 1, W
 
     def monitor_sums(self, rec: Records, P: int, thr, ref_code, list_off, list_cell, cov: int = 100, max_vaf_pm: int = 1000, sums=None, lam=None):
@@ -767,12 +743,8 @@ class Context:
 
         thr, ref_code, list_off, list_cell, L, W = self._monitor_lists(P, thr, ref_code, list_off, list_cell)
         n = rec.n_samples
-        if sums is None:
-            sums = torch.empty((n, L, MON_SUMS), dtype=torch.int64, device=self.device)
-        if lam is None:
-            lam = torch.empty((n, L, 2), dtype=torch.float64, device=self.device)
-        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and tuple(sums.shape) == (n, L, MON_SUMS)
-        assert lam.dtype == torch.float64 and lam.is_cuda and lam.is_contiguous() and tuple(lam.shape) == (n, L, 2)
+        sums = self._out(sums, torch.int64, (n, L, MON_SUMS))
+        lam = self._out(lam, torch.float64, (n, L, 2))
         prm = MonitorParams(int(cov), int(max_vaf_pm))
         self._check(self.lib.ampli_monitor_sums_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), _ptr(list_off), _ptr(list_cell), L, W,
                                                         C.byref(prm), _ptr(sums), _ptr(lam)))
@@ -788,18 +760,13 @@ class Context:
         import torch
 
         thr, ref_code, list_off, list_cell, L, W = self._monitor_lists(P, thr, ref_code, list_off, list_cell)
-        assert pairs.dtype == torch.int32 and pairs.is_cuda and pairs.is_contiguous() and pairs.dim() == 2 and pairs.shape[1] == 2
-        assert cand_off.dtype == torch.int32 and cand_off.is_cuda and cand_off.is_contiguous() and tuple(cand_off.shape) == (5,)
-        assert cand_pos.dtype == torch.int32 and cand_pos.is_cuda and cand_pos.is_contiguous() and cand_pos.dim() == 1
+        assert _ok(pairs, torch.int32, (None, 2))
+        assert _ok(cand_off, torch.int32, (5,)) and _ok(cand_pos, torch.int32, (None,))
         n_pairs, n_cand = int(pairs.shape[0]), int(cand_pos.numel())
         if n_cand == 0:
             cand_pos = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        if sums is None:
-            sums = torch.empty((n_pairs, R, MON_SUMS), dtype=torch.int64, device=self.device)
-        if lam is None:
-            lam = torch.empty((n_pairs, R, 2), dtype=torch.float64, device=self.device)
-        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and tuple(sums.shape) == (n_pairs, R, MON_SUMS)
-        assert lam.dtype == torch.float64 and lam.is_cuda and lam.is_contiguous() and tuple(lam.shape) == (n_pairs, R, 2)
+        sums = self._out(sums, torch.int64, (n_pairs, R, MON_SUMS))
+        lam = self._out(lam, torch.float64, (n_pairs, R, 2))
         prm = MonitorParams(int(cov), int(max_vaf_pm))
         self._check(self.lib.ampli_monitor_control_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), _ptr(list_off), _ptr(list_cell), L, W,
                                                            _ptr(pairs), n_pairs, _ptr(cand_off), _ptr(cand_pos), n_cand, R, first_rep,
@@ -811,11 +778,9 @@ class Context:
         float32 [..., 2], MON_NA (-1) where no entry was evaluated."""
         import torch
 
-        assert sums.dtype == torch.int64 and sums.is_cuda and sums.is_contiguous() and sums.shape[-1] == MON_SUMS
-        assert lam.dtype == torch.float64 and lam.is_cuda and lam.is_contiguous() and tuple(lam.shape) == tuple(sums.shape[:-1]) + (2,)
-        if q is None:
-            q = torch.empty(tuple(lam.shape), dtype=torch.float32, device=self.device)
-        assert q.dtype == torch.float32 and q.is_cuda and q.is_contiguous() and tuple(q.shape) == tuple(lam.shape)
+        assert _ok(sums, torch.int64, (..., MON_SUMS))
+        assert _ok(lam, torch.float64, tuple(sums.shape[:-1]) + (2,))
+        q = self._out(q, torch.float32, tuple(lam.shape))
         self._check(self.lib.ampli_monitor_score(self.h, _ptr(sums), _ptr(lam), sums.numel() // MON_SUMS, _ptr(q)))
         return q
 
@@ -826,10 +791,8 @@ class Context:
         import torch
 
         n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
-        assert planes.dtype == torch.int64 and planes.is_cuda and planes.is_contiguous() and tuple(planes.shape) == (n, GENO_PLANES, W)
-        if ref is None:
-            ref = torch.zeros((3, 6, P), dtype=torch.int64, device=self.device)
-        assert ref.dtype == torch.int64 and ref.is_cuda and ref.is_contiguous() and tuple(ref.shape) == (3, 6, P)
+        assert _ok(planes, torch.int64, (n, GENO_PLANES, W))
+        ref = self._out(ref, torch.int64, (3, 6, P), zero=True)
         self._check(self.lib.ampli_hetsite_reference_records(self.h, C.byref(rec), P, _ptr(planes), int(min_depth), _ptr(ref)))
         return ref
 
@@ -843,16 +806,9 @@ class Context:
         import torch
 
         n, W = rec.n_samples, int(self.lib.ampli_concordance_words(P))
-        assert planes_g.dtype == torch.int64 and planes_g.is_cuda and planes_g.is_contiguous() and tuple(planes_g.shape[1:]) == (GENO_PLANES, W)
-        assert row_g.dtype == torch.int32 and row_g.is_cuda and row_g.is_contiguous() and tuple(row_g.shape) == (n,)
-        assert ref.dtype == torch.int64 and ref.is_cuda and ref.is_contiguous() and tuple(ref.shape) == (3, 6, P)
-        d = self.device
-        q = torch.empty((n, P), dtype=torch.float32, device=d) if q is None else q
-        km = torch.empty((n, P, 2), dtype=torch.int32, device=d) if km is None else km
-        v = torch.empty((n, P), dtype=torch.float64, device=d) if v is None else v
-        code = torch.empty((n, P), dtype=torch.uint8, device=d) if code is None else code
-        for t, dt, sh in ((q, torch.float32, (n, P)), (km, torch.int32, (n, P, 2)), (v, torch.float64, (n, P)), (code, torch.uint8, (n, P))):
-            assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == sh
+        assert _ok(planes_g, torch.int64, (None, GENO_PLANES, W)) and _ok(row_g, torch.int32, (n,)) and _ok(ref, torch.int64, (3, 6, P))
+        q, km = self._out(q, torch.float32, (n, P)), self._out(km, torch.int32, (n, P, 2))
+        v, code = self._out(v, torch.float64, (n, P)), self._out(code, torch.uint8, (n, P))
         prm = AllelicParams(int(min_depth), int(min_normals), int(bool(half_fallback)))
         self._check(self.lib.ampli_allelic_site_records(self.h, C.byref(rec), P, _ptr(planes_g), int(planes_g.shape[0]), _ptr(row_g), _ptr(ref),
                                                         C.byref(prm), _ptr(q), _ptr(km), _ptr(v), _ptr(code)))
@@ -862,29 +818,13 @@ class Context:
         """The five sums (AI_*) of every (sample, region) over the site planes of allelic_sites (ampli_allelic_region_sums):
         int64 [S, R, 5].  reg_off [R + 1] and reg_pos [W]: the regions' position lists as a CSR -- device int32 tensors (read as uint32)
         or host arrays, which are checked (monotone offsets, entries that fit 32 bits; an entry at or beyond P is none) and uploaded."""
-        import numpy as np
         import torch
 
         S, P = int(q.shape[0]), int(q.shape[1])
-        for t, dt, sh in ((q, torch.float32, (S, P)), (km, torch.int32, (S, P, 2)), (v, torch.float64, (S, P)), (code, torch.uint8, (S, P))):
-            assert t.dtype == dt and t.is_cuda and t.is_contiguous() and tuple(t.shape) == sh
-        if not isinstance(reg_off, torch.Tensor):
-            off, pos = np.asarray(reg_off, np.int64), np.asarray(reg_pos, np.int64)
-            assert off.ndim == 1 and len(off) >= 2 and off[0] >= 0 and (np.diff(off) >= 0).all() and off[-1] <= len(pos) < 1 << 27
-            assert ((pos >= 0) & (pos < 1 << 32)).all()
-            reg_off = torch.from_numpy(off.astype(np.uint32).view(np.int32)).to(self.device)
-            reg_pos = torch.from_numpy((pos if len(pos) else np.zeros(1, np.int64)).astype(np.uint32).view(np.int32)).to(self.device)
-            W = len(pos)
-        else:
-            W = reg_pos.numel()
-            if W == 0:  # a pointer is required even where nothing is read through it
-                reg_pos = torch.zeros((1,), dtype=torch.int32, device=self.device)
-        for t in (reg_off, reg_pos):
-            assert t.dtype == torch.int32 and t.is_cuda and t.is_contiguous() and t.dim() == 1
+        assert _ok(q, torch.float32, (S, P)) and _ok(km, torch.int32, (S, P, 2)) and _ok(v, torch.float64, (S, P)) and _ok(code, torch.uint8, (S, P))
+        reg_off, reg_pos, W = self._csr(reg_off, reg_pos, 1 << 27, 1 << 32)
         R = reg_off.numel() - 1
-        if out is None:
-            out = torch.empty((S, R, AI_SUMS), dtype=torch.int64, device=self.device)
-        assert out.dtype == torch.int64 and out.is_cuda and out.is_contiguous() and tuple(out.shape) == (S, R, AI_SUMS)
+        out = self._out(out, torch.int64, (S, R, AI_SUMS))
         self._check(self.lib.ampli_allelic_region_sums(self.h, _ptr(q), _ptr(km), _ptr(v), _ptr(code), S, P, R, _ptr(reg_off), _ptr(reg_pos), W,
                                                        float(site_q), _ptr(out)))
         return out
@@ -905,22 +845,18 @@ class Context:
         tensor of at least fdr_workspace_bytes(rows, P) bytes; allocated here when not given."""
         import torch
 
-        assert s.dtype == torch.float32 and s.is_cuda and s.is_contiguous() and s.dim() == 4 and tuple(s.shape[2:]) == (4, 2)
+        assert _ok(s, torch.float32, (None, None, 4, 2))
         rows, P = int(s.shape[0]), int(s.shape[1])
-        if a is None:
-            a = torch.empty((rows, P, 4), dtype=torch.float32, device=self.device)
-        if m is None:
-            m = torch.empty((rows,), dtype=torch.int32, device=self.device)
+        a = self._out(a, torch.float32, (rows, P, 4))
+        m = self._out(m, torch.int32, (rows,))
         if rank is True:
             rank = torch.empty((rows, P, 4), dtype=torch.int32, device=self.device)
         elif rank is False:
             rank = None
         if work is None:
             work = torch.empty((self.fdr_workspace_bytes(rows, P),), dtype=torch.uint8, device=self.device)
-        assert a.dtype == torch.float32 and a.is_cuda and a.is_contiguous() and tuple(a.shape) == (rows, P, 4)
-        assert m.dtype == torch.int32 and m.is_cuda and m.is_contiguous() and tuple(m.shape) == (rows,)
-        assert rank is None or (rank.dtype == torch.int32 and rank.is_cuda and rank.is_contiguous() and tuple(rank.shape) == (rows, P, 4))
-        assert work.dtype == torch.uint8 and work.is_cuda and work.is_contiguous()
+        assert rank is None or _ok(rank, torch.int32, (rows, P, 4))
+        assert _ok(work, torch.uint8)
         self._check(self.lib.ampli_fdr_adjust(self.h, _ptr(s), rows, P, int(bool(two_sided)), _ptr(work), work.numel(), _ptr(a), _ptr(m), _ptr(rank)))
         return (a, m) if rank is None else (a, m, rank)
 
@@ -936,14 +872,7 @@ class Context:
 
         n, R = rec.n_samples, P + rec.E
         d = self.device
-        if call_mask is None:
-            call_mask = torch.empty(((n * R + 3) // 4 * 4,), dtype=torch.uint8, device=d)[: n * R].view(n, R)
-        if capacity > 0 and calls_buf is None:
-            calls_buf = torch.empty((capacity * C.sizeof(LooCall),), dtype=torch.uint8, device=d)
-        if capacity > 0:
-            capacity -= capacity % CALL_SHARDS
-        if capacity > 0 and n_calls is None:
-            n_calls = torch.zeros((CALL_COUNTER_WORDS,), dtype=torch.int64, device=d)
+        call_mask, calls_buf, capacity, n_calls = self._call_list(n, R, LooCall, capacity, call_mask, calls_buf, n_calls)
         if callable_pos is None:
             callable_pos = torch.zeros((P,), dtype=torch.int32, device=d)
         if callable_sample is None:
@@ -960,20 +889,7 @@ class Context:
 
     def read_loo_calls(self, res):
         """The leave-one-out call list on the host, sorted by (sample, record, alt): the fields of read_calls + thr_fw, thr_bw, code."""
-        import numpy as np
-
-        counts = res["n_calls"][::CALL_COUNTER_STRIDE].cpu().numpy()
-        per = res["capacity"] // CALL_SHARDS
-        if (counts > per).any():
-            raise AmpliError(f"call list segment overflowed: {int(counts.max())} > {per}; rerun with a larger capacity")
-        sz = C.sizeof(LooCall)
-        raw = b"".join(res["calls_buf"][k * per * sz: (k * per + int(counts[k])) * sz].cpu().numpy().tobytes() for k in range(CALL_SHARDS))
-        dt = np.dtype([("sample", "<i4"), ("record", "<i4"), ("alt", "<i4"), ("rd", "<i4"), ("q_fw", "<f8"),
-                       ("q_bw", "<f8"), ("af", "<f4"), ("af_fw", "<f4"), ("af_bw", "<f4"), ("k_fw", "<i4"), ("k_bw", "<i4"),
-                       ("fw", "<i4"), ("bw", "<i4"), ("flags", "<i4"), ("thr_fw", "<f4"), ("thr_bw", "<f4"), ("code", "<i4"), ("pad", "<i4")])
-        assert dt.itemsize == sz
-        a = np.frombuffer(raw, dtype=dt)
-        return a[np.lexsort((a["alt"], a["record"], a["sample"]))]
+        return self._read_list(res, LooCall)
 
     def _new_error_table(self, P: int) -> ErrorTable:
         import torch
@@ -1118,21 +1034,7 @@ class Context:
 
     def read_calls(self, res) -> list[dict]:
         """Copy the compact call list to the host, sorted into the reference's emission order."""
-        import numpy as np
-
-        counts = res["n_calls"][::CALL_COUNTER_STRIDE].cpu().numpy()
-        per = res["capacity"] // CALL_SHARDS
-        if (counts > per).any():
-            raise AmpliError(f"call list segment overflowed: {int(counts.max())} > {per}; rerun with a larger capacity")
-        sz = C.sizeof(Call)
-        raw = b"".join(res["calls_buf"][k * per * sz: (k * per + int(counts[k])) * sz].cpu().numpy().tobytes() for k in range(CALL_SHARDS))
-        dt = np.dtype([("sample", "<i4"), ("record", "<i4"), ("alt", "<i4"), ("rd", "<i4"), ("q_fw", "<f8"),
-                       ("q_bw", "<f8"), ("af", "<f4"), ("af_fw", "<f4"), ("af_bw", "<f4"), ("k_fw", "<i4"), ("k_bw", "<i4"),
-                       ("fw", "<i4"), ("bw", "<i4"), ("flags", "<i4")])
-        assert dt.itemsize == sz
-        a = np.frombuffer(raw, dtype=dt)
-        a = a[np.lexsort((a["alt"], a["record"], a["sample"]))]
-        return a
+        return self._read_list(res, Call)
 
     def score_batch(self, k, rd, err):
         import torch
