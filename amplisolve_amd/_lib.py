@@ -65,6 +65,7 @@ Records = _abi.structs["ampli_records"]
 DiluteMix = _abi.structs["ampli_dilute_mix"]
 MonitorParams = _abi.structs["ampli_monitor_params"]
 AllelicParams = _abi.structs["ampli_allelic_params"]
+FractionParams = _abi.structs["ampli_fraction_params"]
 GenotypeParams = _abi.structs["ampli_genotype_params"]
 SpectrumParams = _abi.structs["ampli_spectrum_params"]
 ExceedanceParams = _abi.structs["ampli_exceedance_params"]

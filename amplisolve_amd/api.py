@@ -9,7 +9,7 @@ from __future__ import annotations
 import ctypes as C
 from dataclasses import dataclass
 
-from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice, Call, DiluteMix, GenotypeParams, LooCall, MonitorParams, Records,
+from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice, Call, DiluteMix, FractionParams, GenotypeParams, LooCall, MonitorParams, Records,
                    hip_lib)
 
 # Every numeric AMPLI_X of the headers is this module's X, with the header's value (_lib.CONSTANTS).  Which family goes with what:
@@ -28,6 +28,8 @@ from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice
 #   NB_NA, PAIR_NA, FDR_NA                 a cell of nb_score / pair_score that is not evaluated, of fdr_adjust that is not tested
 #   DILUTE_BAD_*                           the flag word of a mixture of dilute
 #   MON_*                                  the six sums of monitor_sums, the score without an evaluated entry, the verdicts, the strip
+#   TF_*                                   tumour_fraction: the four values and two counts of a (sample, list), the value where nothing is
+#                                          estimated, the bisection's steps, the z2 of three confidence levels, verdicts and changes
 #   AI_*                                   allelic imbalance: the planes of the het-site reference, the status of a cell (code = status *
 #                                          8 + pair, AI_NO_PAIR: none), the untested score, the five sums of a region and the verdicts
 globals().update({name[len("AMPLI_"):]: value for name, value in CONSTANTS.items()})
@@ -783,6 +785,32 @@ class Context:
         q = self._out(q, torch.float32, tuple(lam.shape))
         self._check(self.lib.ampli_monitor_score(self.h, _ptr(sums), _ptr(lam), sums.numel() // MON_SUMS, _ptr(q)))
         return q
+
+    def tumour_fraction(self, rec: Records, P: int, thr, ref_code, list_off, list_cell, list_w, cov: int = 100, max_vaf_pm: int = 1000,
+                        z2: float = None, est=None, count=None):
+        """The tumour fraction of every (sample of one resident chunk, weighted variant list) (ampli_fraction_records): est
+        float64 [n, L, 4] (TF_F_HAT, TF_F_LO, TF_F_HI, TF_T0: the score estimate, the ends of its Rao score interval at the squared normal
+        quantile z2 -- TF_Z2_95 by default -- and the signed squared score at zero; all TF_NA where nothing can be estimated) and count
+        int64 [n, L, 2] (TF_N_EVAL, TF_N_SEEN).  thr, ref_code, list_off, list_cell as monitor_sums takes them; list_w: float32 [W], the
+        weight of every entry in (0, 1] -- a device tensor, or a host array, which is uploaded.  est, count: the chunk's rows of larger
+        matrices (contiguous views), overwritten."""
+        import numpy as np
+        import torch
+
+        thr, ref_code, list_off, list_cell, L, W = self._monitor_lists(P, thr, ref_code, list_off, list_cell)
+        if not isinstance(list_w, torch.Tensor):
+            w = np.ascontiguousarray(list_w, np.float32)
+            list_w = torch.from_numpy(w if len(w) else np.zeros(1, np.float32)).to(self.device)
+        elif list_w.numel() == 0:  # a pointer is required even where nothing is read through it
+            list_w = torch.zeros((1,), dtype=torch.float32, device=self.device)
+        assert _ok(list_w, torch.float32, (None,)) and list_w.numel() >= W
+        n = rec.n_samples
+        est = self._out(est, torch.float64, (n, L, TF_VALS))
+        count = self._out(count, torch.int64, (n, L, TF_COUNTS))
+        prm = FractionParams(int(cov), int(max_vaf_pm), float(TF_Z2_95 if z2 is None else z2))
+        self._check(self.lib.ampli_fraction_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), _ptr(list_off), _ptr(list_cell), _ptr(list_w), L, W,
+                                                    C.byref(prm), _ptr(est), _ptr(count)))
+        return est, count
 
     def hetsite_reference(self, rec: Records, P: int, planes, min_depth: int = 100, ref=None):
         """One resident chunk of normals into the het-site reference (ampli_hetsite_reference_records): ref int64 [3, 6, P]

@@ -1770,4 +1770,114 @@ AMPLI_FN int ampli_ai_region_verdict(const int64_t *sums, int64_t min_sites, dou
 AMPLI_FN double ampli_ai_fraction_cnloh(double imbalance) { return 2.0 * imbalance; }
 AMPLI_FN double ampli_ai_fraction_loss(double imbalance) { return 4.0 * imbalance / (1.0 + 2.0 * imbalance); }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Tumour fraction per (sample, list) (the definition is tests/fraction_model.py): how much of a patient's tumour is in this
+// plasma sample, within what bounds.
+//   Lists.  The CSR of monitoring (list_off, list_cell, an entry c = 4 p + y) and list_w float32 [W], the weight a of every entry: the
+//     variant's allele fraction per unit of tumour fraction.  An entry with p >= P is none; a cell listed twice counts twice.
+//   Evaluated entry of a row: monitoring's rule (ampli_mon_entry_ok, ampli_mon_record_ok; e == 0 replaced by 0.0010008f), and a weight
+//     that is finite, > 0 and <= 1 (ampli_tf_weight_ok).  It gives two cells, fw then bw, each with k, d, e as doubles, a = (double)w and
+//     ad = a * d.  A cell is modelled as a Poisson count of mean d (e + f a).
+//   Score and information at f, per cell: r = e + f * a; g = a / r; U += g * k - ad; I += g * ad -- seven IEEE operations, unfused.  Lane
+//     j of 64 takes entries j, j + 64, ... ascending, fw before bw, into two accumulators that start at +0.0 (an entry that is not
+//     evaluated adds nothing); the 64 pairs are combined by x += x[lane ^ off] for off = 32, 16, 8, 4, 2, 1.  T(f) = U * |U| / I.
+//   N_EVAL == 0 or I(0) <= 0 makes all four values AMPLI_TF_NA.  Otherwise, every bisection AMPLI_TF_ITERS steps of mid = 0.5 * (lo + hi)
+//   and the result 0.5 * (lo + hi):
+//     F_HAT: 0 if U(0) <= 0; 1 if U(1) >= 0; else on [0, 1], U(mid) > 0 ? lo = mid : hi = mid.
+//     F_LO:  0 if T(0) <= z2; else on [0, F_HAT], T(mid) > z2 ? lo = mid : hi = mid.  T need not be monotone there in contrived lists:
+//            the bisection's result is the definition.
+//     F_HI:  0 if F_HAT == 0 and -T(0) >= z2; 1 if -T(1) < z2; else on [F_HAT, 1], -T(mid) < z2 ? lo = mid : hi = mid.
+//     T0 = T(0).
+//   At most 2 + 3 AMPLI_TF_ITERS = 182 evaluations of the sums.  r > 0 always (e > 0, f >= 0, a > 0), so no quotient is a NaN.
+// ------------------------------------------------------------------------------------------------------------------------------------
+AMPLI_FN int ampli_tf_weight_ok(float w) { return w > 0.0f && w <= 1.0f; } // a NaN, an infinity, 0 and a negative value fail
+
+// what one cell (k reads of the listed base among a depth with a d = ad, threshold e, weight a) adds to the score U and the information I at f
+AMPLI_FN void ampli_tf_cell_terms(double f, double k, double ad, double a, double e, double *U, double *I)
+{
+    const double fa = f * a;
+    const double r = e + fa;
+    const double g = a / r;
+    const double gk = g * k;
+    *U = *U + (gk - ad);
+    *I = *I + g * ad;
+}
+
+AMPLI_FN double ampli_tf_T(double U, double I) { return U * fabs(U) / I; }
+
+#ifdef __cplusplus
+// The estimate and its interval over `sum_at(f, &U, &I)`, which gives the two combined sums at f.  The host library's twin and the
+// kernel run this text; on the device every lane of a wave holds the same sums, so every branch is wave-uniform.
+template <class SumAt>
+AMPLI_FN void ampli_tf_solve(SumAt sum_at, int64_t n_eval, double z2, double *out /* [AMPLI_TF_VALS] */)
+{
+    out[AMPLI_TF_F_HAT] = out[AMPLI_TF_F_LO] = out[AMPLI_TF_F_HI] = out[AMPLI_TF_T0] = AMPLI_TF_NA;
+    if (n_eval <= 0) return;
+    double U0, I0, U, I;
+    sum_at(0.0, &U0, &I0);
+    if (!(I0 > 0.0)) return;
+    const double T0 = ampli_tf_T(U0, I0);
+    double U1, I1;
+    sum_at(1.0, &U1, &I1);
+    double fh;
+    if (U0 <= 0.0) fh = 0.0;
+    else if (U1 >= 0.0) fh = 1.0;
+    else {
+        double lo = 0.0, hi = 1.0;
+        for (int i = 0; i < AMPLI_TF_ITERS; ++i) {
+            const double mid = 0.5 * (lo + hi);
+            sum_at(mid, &U, &I);
+            if (U > 0.0) lo = mid; else hi = mid;
+        }
+        fh = 0.5 * (lo + hi);
+    }
+    double fl = 0.0;
+    if (T0 > z2) {
+        double lo = 0.0, hi = fh;
+        for (int i = 0; i < AMPLI_TF_ITERS; ++i) {
+            const double mid = 0.5 * (lo + hi);
+            sum_at(mid, &U, &I);
+            if (ampli_tf_T(U, I) > z2) lo = mid; else hi = mid;
+        }
+        fl = 0.5 * (lo + hi);
+    }
+    double fu;
+    if (fh == 0.0 && -T0 >= z2) fu = 0.0;
+    else if (-ampli_tf_T(U1, I1) < z2) fu = 1.0;
+    else {
+        double lo = fh, hi = 1.0;
+        for (int i = 0; i < AMPLI_TF_ITERS; ++i) {
+            const double mid = 0.5 * (lo + hi);
+            sum_at(mid, &U, &I);
+            if (-ampli_tf_T(U, I) < z2) lo = mid; else hi = mid;
+        }
+        fu = 0.5 * (lo + hi);
+    }
+    out[AMPLI_TF_F_HAT] = fh;
+    out[AMPLI_TF_F_LO] = fl;
+    out[AMPLI_TF_F_HI] = fu;
+    out[AMPLI_TF_T0] = T0;
+}
+#endif
+
+// NOT_EVALUABLE below min_variants evaluated entries (and where nothing could be estimated); QUANTIFIED if the lower end is above zero;
+// else BELOW, and F_HI is the reportable upper bound
+AMPLI_FN int ampli_tf_verdict(int64_t n_eval, double f_hat, double f_lo, int64_t min_variants)
+{
+    if (n_eval < min_variants || f_hat < 0.0) return AMPLI_TF_NOT_EVALUABLE;
+    return f_lo > 0.0 ? AMPLI_TF_QUANTIFIED : AMPLI_TF_BELOW;
+}
+
+// the change from draw A to draw B of one list, from the draws' verdicts and values; *ratio = F_HAT_B / F_HAT_A, AMPLI_TF_NA where
+// either draw is not evaluable or F_HAT_A is zero
+AMPLI_FN int ampli_tf_change(int verdict_a, const double *a, int verdict_b, const double *b, double *ratio)
+{
+    *ratio = AMPLI_TF_NA;
+    if (verdict_a == AMPLI_TF_NOT_EVALUABLE || verdict_b == AMPLI_TF_NOT_EVALUABLE) return AMPLI_TF_CHANGE_NOT_EVALUABLE;
+    if (a[AMPLI_TF_F_HAT] > 0.0) *ratio = b[AMPLI_TF_F_HAT] / a[AMPLI_TF_F_HAT];
+    if (b[AMPLI_TF_F_LO] > a[AMPLI_TF_F_HI]) return AMPLI_TF_RISING;
+    if (b[AMPLI_TF_F_HI] < a[AMPLI_TF_F_LO]) return AMPLI_TF_FALLING;
+    return AMPLI_TF_STABLE;
+}
+
 #endif

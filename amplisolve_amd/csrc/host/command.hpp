@@ -48,6 +48,18 @@ void load_cohort(CohortInputs &in, const std::string &panel_design, const std::s
 using ChunkFn = std::function<void(const ampli_records &r, Chunk &c, int first)>;
 void for_each_chunk(Dev &dev, const CohortInputs &in, DevSlot &slot, const ChunkFn &fn, int first_set = 0);
 
+// ---- the variant lists and assignments of the monitoring commands (run_mo.cpp) ----
+// list<TAB>chrom<TAB>pos<TAB>ref<TAB>alt per line, with <TAB>weight in (0, 1] where `weighted`, as a CSR of cells 4 p + y in the order of
+// the lines (w is empty unless weighted); and sample<TAB>list per line, or "-" for none, as (file index, list index).  Both refuse what
+// they cannot read, with the line's number.
+struct VariantLists {
+    std::vector<std::string> names;  // in the order of their first line
+    std::vector<uint32_t> off, cell; // the CSR: a list's entries in the order of its lines
+    std::vector<float> w;            // the entries' weights
+};
+VariantLists read_variant_lists(const std::string &path, const Panel &panel, bool weighted);
+std::vector<std::pair<int, int>> read_assignments(const std::string &path, const FileSet &files, const VariantLists &lists, const std::string &sample_dir);
+
 // ---- resident: every chunk of `files` stays on the device ----
 struct Resident {
     ampli_records r;

@@ -322,6 +322,13 @@ struct MoArgs {
                 controls = "100", seed = "1", output_dir;
 };
 int run_variant_monitoring(const MoArgs &a);
+// AmpliSolveTumourFraction (tf_main.cpp, run_tf.cpp): the tumour fraction of every (sample, list) with its score interval, the
+// assigned pairs, and the change between consecutive draws of one list.  variants carries a sixth column, the weight; confidence is one of
+// 0.90, 0.95, 0.99.  Fraction_Matrix.txt, Fraction_Own.txt, Fraction_Change.txt, Fraction_Summary.txt; exit status 0 / 1
+struct TfArgs {
+    std::string error_file, sample_dir, variants, assign = "-", coverage_cutoff = "100", min_variants = "5", max_vaf = "1", confidence = "0.95", output_dir;
+};
+int run_tumour_fraction(const TfArgs &a);
 // AmpliSolveAllelicImbalance (ai_main.cpp, run_ai.cpp): the allelic balance at germline het sites, pooled per gene.  The het-site
 // reference from the normals; every file of tumour_dir (or, with "-", the normals again: the null calibration) at the het sites of its own
 // genotype or of the normal that `pairs` names (tumourName<TAB>normalName per line, or "self"); one region per gene string of the BED and

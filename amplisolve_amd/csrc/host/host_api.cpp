@@ -1,5 +1,6 @@
 // amplisolve_amd/csrc/host/host_api.cpp -- C ABI over the host library (include/amplisolve_host.h).
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 
 #include "../../../include/amplisolve_host.h"
@@ -718,6 +719,99 @@ extern "C" int64_t ampli_host_monitor_lod_reads(double lam, double q_min, int32_
 extern "C" double ampli_host_monitor_lod(double lam_fw, double lam_bw, int64_t D_fw, int64_t D_bw, double q_min)
 {
     return ampli_mon_lod(lam_fw, lam_bw, D_fw, D_bw, q_min);
+}
+
+// ---- tumour fraction: csrc/ampli_math.h's functions in the order of the definition ------------------------------------------
+
+namespace {
+
+// an evaluated entry of one (row, list): the lane it belongs to and its two cells
+struct TfHostCell {
+    int lane;
+    double kf, kb, adf, adb, a, ef, eb;
+};
+
+// the evaluated entries of one (row, list) in the order of the list, and the two counts
+void tf_cells(const int32_t *row, int64_t P, const float *thr, const uint8_t *ref_code, const uint32_t *cell, const float *w, size_t len,
+              const ampli_fraction_params *prm, std::vector<TfHostCell> &out, int64_t *count)
+{
+    out.clear();
+    count[AMPLI_TF_N_EVAL] = count[AMPLI_TF_N_SEEN] = 0;
+    for (size_t i = 0; i < len; ++i) {
+        const uint32_t p = cell[i] >> 2, y = cell[i] & 3u;
+        if ((int64_t)p >= P) continue;
+        const uint32_t ref = ref_code[p];
+        if (ref > 3u) continue;
+        float ef = thr[(size_t)y * (size_t)P + p], eb = thr[(size_t)(4 + y) * (size_t)P + p];
+        if (!ampli_mon_entry_ok(ref, y, ef, eb) || !ampli_tf_weight_ok(w[i])) continue;
+        const int32_t *r = row + (size_t)p * 8;
+        const int64_t FW = (int64_t)r[0] + r[1] + r[2] + r[3], BW = (int64_t)r[4] + r[5] + r[6] + r[7];
+        const int64_t kf = r[y], kb = r[4 + y];
+        if (!ampli_mon_record_ok(r[0] != AMPLI_ABSENT, kf, kb, FW, BW, prm->coverage_cutoff, prm->max_vaf_pm)) continue;
+        if (ef == 0.0f) ef = 0.0010008f;
+        if (eb == 0.0f) eb = 0.0010008f;
+        const double a = (double)w[i];
+        out.push_back({(int)(i & 63), (double)kf, (double)kb, a * (double)FW, a * (double)BW, a, (double)ef, (double)eb});
+        count[AMPLI_TF_N_EVAL] += 1;
+        count[AMPLI_TF_N_SEEN] += kf + kb >= 1 ? 1 : 0;
+    }
+}
+
+// the 64 accumulators combined: x += x[lane ^ off] for off = 32, 16, 8, 4, 2, 1
+double tf_butterfly(double *x)
+{
+    for (int off = 32; off >= 1; off >>= 1) {
+        double nx[64];
+        for (int j = 0; j < 64; ++j) nx[j] = x[j] + x[j ^ off];
+        memcpy(x, nx, sizeof nx);
+    }
+    return x[0];
+}
+
+} // namespace
+
+extern "C" int ampli_host_fraction(const int32_t *recs, int32_t n, int64_t stride, int64_t P, const float *thr, const uint8_t *ref_code, const uint32_t *list_off,
+                                   const uint32_t *list_cell, const float *list_w, int32_t L, int64_t W, const ampli_fraction_params *prm, double *est,
+                                   int64_t *count)
+{
+    if (!recs || !thr || !ref_code || !list_off || !list_cell || !list_w || !prm || !est || !count || n < 1 || P <= 0 || L < 0 || W < 0 ||
+        prm->coverage_cutoff < 0 || prm->max_vaf_pm < 0 || prm->max_vaf_pm > 1000 || !std::isfinite(prm->z2) || !(prm->z2 > 0.0))
+        return AMPLI_E_INVALID;
+    if (stride == 0) stride = P;
+    if (stride < P) return AMPLI_E_INVALID;
+    if (P >= 0x7FFFFFFFll || W >= (1ll << 28)) return AMPLI_E_RANGE;
+    std::vector<TfHostCell> cells;
+    for (int32_t l = 0; l < L; ++l) {
+        uint32_t off, end;
+        mon_bounds(list_off, l, W, off, end);
+        for (int32_t s = 0; s < n; ++s) {
+            int64_t *oc = count + ((size_t)s * L + l) * AMPLI_TF_COUNTS;
+            tf_cells(recs + (size_t)s * (size_t)stride * 8, P, thr, ref_code, list_cell + off, list_w + off, end - off, prm, cells, oc);
+            auto sum_at = [&](const double f, double *U, double *I) {
+                double u[64], i[64];
+                for (int j = 0; j < 64; ++j) u[j] = i[j] = 0.0;
+                for (const TfHostCell &c : cells) {
+                    ampli_tf_cell_terms(f, c.kf, c.adf, c.a, c.ef, &u[c.lane], &i[c.lane]);
+                    ampli_tf_cell_terms(f, c.kb, c.adb, c.a, c.eb, &u[c.lane], &i[c.lane]);
+                }
+                *U = tf_butterfly(u);
+                *I = tf_butterfly(i);
+            };
+            ampli_tf_solve(sum_at, oc[AMPLI_TF_N_EVAL], prm->z2, est + ((size_t)s * L + l) * AMPLI_TF_VALS);
+        }
+    }
+    return 0;
+}
+
+extern "C" int ampli_host_fraction_verdict(int64_t n_eval, double f_hat, double f_lo, int64_t min_variants)
+{
+    return ampli_tf_verdict(n_eval, f_hat, f_lo, min_variants);
+}
+
+extern "C" int ampli_host_fraction_change(int32_t verdict_a, const double *a, int32_t verdict_b, const double *b, double *ratio)
+{
+    if (!a || !b || !ratio) return -1;
+    return ampli_tf_change(verdict_a, a, verdict_b, b, ratio);
 }
 
 // ---- allelic imbalance: the site stage cell by cell, and the region verdict ----

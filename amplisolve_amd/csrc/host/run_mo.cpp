@@ -30,26 +30,25 @@ std::vector<std::string> mo_fields(std::string line)
     return t;
 }
 
-struct MoLists {
-    std::vector<std::string> names;  // in the order of their first line
-    std::vector<uint32_t> off, cell; // the CSR: a list's entries in the order of its lines
-};
+} // namespace
 
-// list<TAB>chrom<TAB>pos<TAB>ref<TAB>alt per line; refuses a line of another shape (an empty one too), a position that is not a whole
-// positive number, a variant off the panel, a ref that is not the table's base, an alt that is no base or is the ref, an empty file
-MoLists read_variants(const std::string &path, const Panel &panel)
+// list<TAB>chrom<TAB>pos<TAB>ref<TAB>alt per line, and <TAB>weight where `weighted`; refuses a line of another shape (an empty one too), a
+// position that is not a whole positive number, a variant off the panel, a ref that is not the table's base, an alt that is no base or
+// is the ref, a weight that is not a number in (0, 1], an empty file
+VariantLists read_variant_lists(const std::string &path, const Panel &panel, const bool weighted)
 {
     std::ifstream f(path);
     if (!f) throw Error{AMPLI_E_INVALID, "variants: cannot read '" + path + "'"};
     std::map<std::string, int> index;
     std::vector<std::vector<uint32_t>> cells;
-    MoLists out;
+    std::vector<std::vector<float>> weights;
+    VariantLists out;
     std::string line;
     for (int n = 1; std::getline(f, line); ++n) {
         const std::vector<std::string> t = mo_fields(line);
         const std::string at = "variants: line " + std::to_string(n);
-        if (t.size() != 5 || t[0].empty() || t[1].empty())
-            throw Error{AMPLI_E_INVALID, at + " of '" + path + "' is not list<TAB>chrom<TAB>pos<TAB>ref<TAB>alt"};
+        if (t.size() != (weighted ? 6u : 5u) || t[0].empty() || t[1].empty())
+            throw Error{AMPLI_E_INVALID, at + " of '" + path + "' is not list<TAB>chrom<TAB>pos<TAB>ref<TAB>alt" + (weighted ? "<TAB>weight" : "")};
         char *end = nullptr;
         errno = 0;
         const long pos = std::strtol(t[2].c_str(), &end, 10);
@@ -59,19 +58,28 @@ MoLists read_variants(const std::string &path, const Panel &panel)
         const size_t alt = t[4].size() == 1 ? std::string("ACGT").find(t[4][0]) : std::string::npos;
         if (ref == std::string::npos || alt == std::string::npos) throw Error{AMPLI_E_INVALID, at + ": ref and alt must each be one of A, C, G, T, got '" + t[3] + "' and '" + t[4] + "'"};
         if (ref == alt) throw Error{AMPLI_E_INVALID, at + ": alt equals ref ('" + t[3] + "')"};
+        float w = 1.0f;
+        if (weighted) {
+            errno = 0;
+            w = std::strtof(t[5].c_str(), &end);
+            if (t[5].empty() || *end || errno || t[5].find_first_not_of("0123456789.eE+-") != std::string::npos || !ampli_tf_weight_ok(w))
+                throw Error{AMPLI_E_INVALID, at + ": weight must be a number in (0, 1], got '" + t[5] + "'"};
+        }
         const int p = panel.find(t[1], (int)pos);
         if (p < 0) throw Error{AMPLI_E_INVALID, at + ": " + t[1] + ":" + t[2] + " is not a position of the error table"};
         if (panel.ref_code[(size_t)p] != (uint8_t)ref)
             throw Error{AMPLI_E_INVALID, at + ": ref '" + t[3] + "' is not the table's base '" + panel.ref_base[(size_t)p] + "' at " + t[1] + ":" + t[2]};
         if (p >= (1 << 30)) throw Error{AMPLI_E_RANGE, at + ": the position index does not fit a list entry"};
         const auto it = index.emplace(t[0], (int)out.names.size());
-        if (it.second) { out.names.push_back(t[0]); cells.emplace_back(); }
+        if (it.second) { out.names.push_back(t[0]); cells.emplace_back(); weights.emplace_back(); }
         cells[(size_t)it.first->second].push_back((uint32_t)p * 4u + (uint32_t)alt);
+        weights[(size_t)it.first->second].push_back(w);
     }
     if (out.names.empty()) throw Error{AMPLI_E_INVALID, "variants: '" + path + "' lists no variant"};
     out.off.push_back(0);
-    for (const auto &c : cells) {
-        out.cell.insert(out.cell.end(), c.begin(), c.end());
+    for (size_t l = 0; l < cells.size(); ++l) {
+        out.cell.insert(out.cell.end(), cells[l].begin(), cells[l].end());
+        if (weighted) out.w.insert(out.w.end(), weights[l].begin(), weights[l].end());
         out.off.push_back((uint32_t)out.cell.size());
     }
     if (out.cell.size() >= ((size_t)1 << 28)) throw Error{AMPLI_E_RANGE, "variants: more than 2^28 - 1 entries"};
@@ -79,7 +87,7 @@ MoLists read_variants(const std::string &path, const Panel &panel)
 }
 
 // sample<TAB>list per line, or "-" for none; refuses a line of another shape, an unknown sample or list
-std::vector<std::pair<int, int>> read_assign(const std::string &path, const FileSet &files, const MoLists &lists, const std::string &sample_dir)
+std::vector<std::pair<int, int>> read_assignments(const std::string &path, const FileSet &files, const VariantLists &lists, const std::string &sample_dir)
 {
     std::vector<std::pair<int, int>> out;
     if (path == "-") return out;
@@ -101,6 +109,8 @@ std::vector<std::pair<int, int>> read_assign(const std::string &path, const File
     }
     return out;
 }
+
+namespace {
 
 const char *mo_verdict_name(const int v) { return v == AMPLI_MON_DETECTED ? "DETECTED" : v == AMPLI_MON_NOT_DETECTED ? "NOT_DETECTED" : "NOT_EVALUABLE"; }
 
@@ -138,8 +148,8 @@ int run_variant_monitoring(const MoArgs &a)
         if (F == 0) throw Error{AMPLI_E_INVALID, "no count files in " + a.sample_dir};
         in.n_tumours = F;
         in.P = P;
-        const MoLists lists = read_variants(a.variants, panel);
-        const std::vector<std::pair<int, int>> own = read_assign(a.assign, files, lists, a.sample_dir);
+        const VariantLists lists = read_variant_lists(a.variants, panel, false);
+        const std::vector<std::pair<int, int>> own = read_assignments(a.assign, files, lists, a.sample_dir);
         const int L = (int)lists.names.size();
         const int64_t W = (int64_t)lists.cell.size();
         long batch_cap = 0; // AMPLISOLVE_MONITOR_BATCH: control replicates of one batch at most (tests; 0 = what 64 MiB hold)

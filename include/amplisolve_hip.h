@@ -166,6 +166,11 @@ extern "C" {
  *   (C27) allelic regions: d_sums of ampli_allelic_region_sums is FULLY OVERWRITTEN, all [S][R][5] sums, empty regions included
  *        (zeros).  Nothing else is written.  d_reg_off is read at [0, R], d_reg_pos at [0, W) at most, the site planes only at a
  *        listed position below P of a row below S.
+ *   (C28) tumour fraction (tests/test_gpu_fraction_contracts.py): d_est and d_count of ampli_fraction_records are FULLY OVERWRITTEN, all
+ *        [recs->n_samples][L][4] doubles and [recs->n_samples][L][2] counts, with plain stores (one wave owns a cell: nothing is
+ *        cleared, nothing is added to), empty lists included (AMPLI_TF_NA and zeros).  Nothing else is written -- the other chunks' rows
+ *        of a larger matrix included.  d_list_off is read at [0, L], d_list_cell and d_list_w at [0, W) at most, d_ref_code at [0, P),
+ *        d_thr at [0, 8 P), a record only at a listed position below P of a row below n_samples.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -1064,6 +1069,48 @@ int ampli_allelic_site_records(ampli_ctx *ctx, const ampli_records *recs, int64_
 int ampli_allelic_region_sums(ampli_ctx *ctx, const float *d_q, const int32_t *d_km, const double *d_v, const uint8_t *d_code, int32_t S, int64_t P,
                               int32_t R, const uint32_t *d_reg_off /* [R + 1] */, const uint32_t *d_reg_pos /* [W] */, int64_t W, double site_q,
                               int64_t *d_sums /* [S][R][5] */);
+
+/*
+ * Tumour fraction per (sample, list) (the definition, in plain numpy, is tests/fraction_model.py): how much of a patient's
+ * tumour is in this plasma sample, and within what bounds -- the score estimate of f and its Rao score interval.
+ *   Lists.  The CSR of ampli_monitor_sums_records IN DEVICE MEMORY (d_list_off uint32 [L + 1], d_list_cell uint32 [W], an entry
+ *     c = 4 p + y) and d_list_w float32 [W], the weight a of every entry: the variant's allele fraction per unit of tumour fraction, for
+ *     example its tissue VAF divided by the purity.  A cell named twice counts twice; an entry with p >= P is none; offsets are cut to
+ *     [0, W].  W >= 2^28 is AMPLI_E_RANGE.
+ *   Evaluated entry of a row: exactly the rule of ampli_monitor_sums_records (PRIMARY record only, both strand depths >=
+ *     coverage_cutoff, the max_vaf_pm cap, a reference base in 0..3 that y differs from, both thresholds finite and >= 0, e == 0
+ *     replaced by 0.0010008f), and a weight that is finite, > 0 and <= 1.  It gives two cells, fw then bw, each with its count k of
+ *     base y, its strand's depth d and its threshold e as doubles, a = (double)w and ad = a * d.  A cell is modelled as a Poisson
+ *     count of mean d (e + f a): f is the fraction ABOVE THE TABLE'S RATES.
+ *   Score and information at f; the operation sequence is part of the definition.  Per cell r = e + f * a; g = a / r; U += g * k - ad;
+ *     I += g * ad.  Lane j of 64 takes the list's entries j, j + 64, ... in ascending order, fw before bw, into two accumulators that
+ *     start at +0.0 (an entry that is not evaluated adds nothing); the 64 pairs are combined by x += x[lane ^ off] for off = 32, 16,
+ *     8, 4, 2, 1.  T(f) = U * |U| / I.  Unfused IEEE operations, a correctly rounded division: the model, the host library and the
+ *     device agree bit for bit.
+ *   Values per (sample, list), in the order AMPLI_TF_*.  N_EVAL == 0 or I(0) <= 0: all four are AMPLI_TF_NA.  Every bisection takes
+ *     AMPLI_TF_ITERS steps mid = 0.5 * (lo + hi) and gives 0.5 * (lo + hi).
+ *     F_HAT: 0 if U(0) <= 0; 1 if U(1) >= 0; else on [0, 1] with U(mid) > 0 ? lo = mid : hi = mid.
+ *     F_LO:  0 if T(0) <= z2; else on [0, F_HAT] with T(mid) > z2 ? lo = mid : hi = mid (T need not be monotone there in contrived
+ *            lists: the bisection's result is the definition).
+ *     F_HI:  0 if F_HAT == 0 and -T(0) >= z2; 1 if -T(1) < z2; else on [F_HAT, 1] with -T(mid) < z2 ? lo = mid : hi = mid.
+ *     T0:    T(0), the signed squared score at zero.
+ *   Counts per (sample, list): N_EVAL, the evaluated entries, and N_SEEN, those of them with k_fw + k_bw >= 1.
+ *
+ * ampli_fraction_records: d_est double [recs->n_samples][L][AMPLI_TF_VALS] and d_count int64 [recs->n_samples][L][AMPLI_TF_COUNTS],
+ *   8-byte aligned, FULLY OVERWRITTEN with plain stores (C28); a streamed cohort passes each chunk its rows of one matrix.  A wave owns
+ *   one list and 8 consecutive rows; lists of up to 256 entries keep their entries and the row's cells in registers, an evaluation of
+ *   the sums is then one division per cell and the butterfly; longer lists are gathered again for each of the up to 182 evaluations
+ *   (slow).  L == 0 writes nothing and succeeds.
+ * Refusals, every output untouched.  AMPLI_E_INVALID: a null or misaligned pointer (prm is a host pointer), P <= 0, L < 0, W < 0,
+ *   coverage_cutoff < 0, max_vaf_pm outside 0..1000, z2 not finite or <= 0, broken records.  AMPLI_E_RANGE: P >= 2^31, W >= 2^28,
+ *   n_samples > 2097120.
+ * No LDS, no barrier, no atomics: the same inputs give the same bytes.  Asynchronous on the context's stream.  The verdict of a
+ * (sample, list) and the change between two draws are decided on the host (include/amplisolve_host.h).
+ */
+int ampli_fraction_records(ampli_ctx *ctx, const ampli_records *recs, int64_t P, const float *d_thr, const uint8_t *d_ref_code,
+                           const uint32_t *d_list_off, const uint32_t *d_list_cell, const float *d_list_w, int32_t L, int64_t W,
+                           const ampli_fraction_params *prm, double *d_est /* [n][L][4]: F_HAT, F_LO, F_HI, T0 */,
+                           int64_t *d_count /* [n][L][2]: N_EVAL, N_SEEN */);
 
 /* free and total bytes of the context's device (hipMemGetInfo), for callers that keep a whole cohort resident */
 int ampli_mem_info(ampli_ctx *ctx, size_t *free_bytes, size_t *total_bytes);

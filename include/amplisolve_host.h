@@ -354,6 +354,22 @@ int ampli_host_allelic_pair(uint32_t plane_bits);
 int ampli_host_allelic_site_sums(float q, int32_t k_lo, int32_t m, double v, int64_t *dev16, int64_t *q20);
 int ampli_host_allelic_region_verdict(const int64_t *sums /* [5] */, int64_t min_sites, double q_min, double min_imbalance, double *Q, double *imbalance);
 
+/* Tumour fraction per (sample, list) (the definition is tests/fraction_model.py, in full in include/amplisolve_hip.h):
+ * csrc/ampli_math.h's functions in the order of the definition, so that every double is pinned without a GPU.
+ * _fraction: the device entry point over int32 records on the host.  recs int32 [n][stride][8], stride in records (0 = P), of which
+ *   the first P records of a row enter; the other arrays as on the device.  est [n][L][AMPLI_TF_VALS] and count [n][L][AMPLI_TF_COUNTS]
+ *   are fully overwritten.  Returns 0, or AMPLI_E_INVALID (-1) / AMPLI_E_RANGE (-6) with nothing written where the device entry point
+ *   refuses.
+ * _fraction_verdict: AMPLI_TF_NOT_EVALUABLE if n_eval < min_variants or the values are AMPLI_TF_NA (f_hat < 0); else AMPLI_TF_QUANTIFIED if
+ *   f_lo > 0; else AMPLI_TF_BELOW, and F_HI is the reportable upper bound.
+ * _fraction_change: from draw A to draw B of one list, a and b the draws' four values: AMPLI_TF_CHANGE_NOT_EVALUABLE if either verdict is
+ *   AMPLI_TF_NOT_EVALUABLE; else AMPLI_TF_RISING if F_LO_B > F_HI_A; else AMPLI_TF_FALLING if F_HI_B < F_LO_A; else AMPLI_TF_STABLE.
+ *   *ratio = F_HAT_B / F_HAT_A, AMPLI_TF_NA where either draw is not evaluable or F_HAT_A is 0.  -1 for a null pointer. */
+int ampli_host_fraction(const int32_t *recs, int32_t n, int64_t stride, int64_t P, const float *thr, const uint8_t *ref_code, const uint32_t *list_off,
+                        const uint32_t *list_cell, const float *list_w, int32_t L, int64_t W, const ampli_fraction_params *prm, double *est, int64_t *count);
+int ampli_host_fraction_verdict(int64_t n_eval, double f_hat, double f_lo, int64_t min_variants);
+int ampli_host_fraction_change(int32_t verdict_a, const double *a /* [4] */, int32_t verdict_b, const double *b /* [4] */, double *ratio);
+
 /* two-sided Fisher exact test of the post-call annotation (VC:3797-3814; own pmf, parity unpinned vs Boost) */
 double ampli_host_fisher(int a, int b, int c, int d);
 /* the same sum with every term taken from the log-gamma form (slow; the check of the recurrence ampli_host_fisher walks) */

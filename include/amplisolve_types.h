@@ -187,4 +187,34 @@ typedef struct ampli_allelic_params {
     int32_t min_depth, min_normals, half_fallback;
 } ampli_allelic_params;
 
+/* Tumour fraction per (sample, list): the order of the four doubles of a (sample, list) -- the score estimate, the two ends of
+ * its Rao score interval and the signed squared score at zero --, the order of the two int64 counts, the value of all four doubles where
+ * nothing can be estimated, the steps of every bisection, the verdict of a (sample, list), the change between two draws of one list, and
+ * the parameters: the gates of an evaluated entry as ampli_monitor_params has them, and z2, the squared normal quantile of the interval
+ * (finite and > 0; AMPLI_TF_Z2_95 is the default). */
+#define AMPLI_TF_F_HAT 0
+#define AMPLI_TF_F_LO 1
+#define AMPLI_TF_F_HI 2
+#define AMPLI_TF_T0 3
+#define AMPLI_TF_VALS 4
+#define AMPLI_TF_N_EVAL 0
+#define AMPLI_TF_N_SEEN 1
+#define AMPLI_TF_COUNTS 2
+#define AMPLI_TF_NA (-1.0)
+#define AMPLI_TF_ITERS 60
+#define AMPLI_TF_Z2_90 2.705543
+#define AMPLI_TF_Z2_95 3.841459
+#define AMPLI_TF_Z2_99 6.634897
+#define AMPLI_TF_NOT_EVALUABLE 0
+#define AMPLI_TF_BELOW 1
+#define AMPLI_TF_QUANTIFIED 2
+#define AMPLI_TF_CHANGE_NOT_EVALUABLE 0
+#define AMPLI_TF_STABLE 1
+#define AMPLI_TF_RISING 2
+#define AMPLI_TF_FALLING 3
+typedef struct ampli_fraction_params {
+    int32_t coverage_cutoff, max_vaf_pm;
+    double z2;
+} ampli_fraction_params;
+
 #endif /* AMPLISOLVE_TYPES_H */
