@@ -32,6 +32,7 @@ from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice
 #                                          estimated, the bisection's steps, the z2 of three confidence levels, verdicts and changes
 #   AI_*                                   allelic imbalance: the planes of the het-site reference, the status of a cell (code = status *
 #                                          8 + pair, AI_NO_PAIR: none), the untested score, the five sums of a region and the verdicts
+#   INDEL_LEN_BINS                         indel_count: the length bins per (position, kind) of its second output
 globals().update({name[len("AMPLI_"):]: value for name, value in CONSTANTS.items()})
 
 # Python's own
@@ -811,6 +812,25 @@ class Context:
         self._check(self.lib.ampli_fraction_records(self.h, C.byref(rec), P, _ptr(thr), _ptr(ref_code), _ptr(list_off), _ptr(list_cell), _ptr(list_w), L, W,
                                                     C.byref(prm), _ptr(est), _ptr(count)))
         return est, count
+
+    def indel_count(self, bam, rec_off, keys, mbq: int = 20, mrq: int = 20, counts=None, lengths=None, stats=None):
+        """Indel junction counts of a batch of alignment records (ampli_pileup_indel_count).  bam: uint8 device tensor, the
+        uncompressed records, 16-byte aligned and readable for 16 bytes behind the last record; rec_off: int64 [n_reads], ascending
+        offsets of the records' block_size fields; keys: int64 [P], the panel as (reference id << 32 | 1-based position), ascending.
+        Returns (counts, lengths, stats): counts int32 [P, 8] (slot 0 reference junctions, 1 insertions, 2 deletions, 4..6 the same on the
+        reverse strand; 3 and 7 untouched), lengths int32 [P, 2, INDEL_LEN_BINS] and stats int64 [2] (reads kept, junctions counted).
+        All three are ADDED TO: a given buffer accumulates, None starts a new one at zero; lengths=False / stats=False: that output is
+        not computed (NULL) and returned as None."""
+        import torch
+
+        assert _ok(bam, torch.uint8, (None,)) and bam.data_ptr() % 16 == 0 and _ok(rec_off, torch.int64, (None,)) and _ok(keys, torch.int64, (None,))
+        n_reads, P = int(rec_off.numel()), int(keys.numel())
+        counts = self._out(counts, torch.int32, (P, 8), zero=True)
+        lengths = None if lengths is False else self._out(lengths, torch.int32, (P, 2, INDEL_LEN_BINS), zero=True)
+        stats = None if stats is False else self._out(stats, torch.int64, (2,), zero=True)
+        self._check(self.lib.ampli_pileup_indel_count(self.h, _ptr(bam), _ptr(rec_off), n_reads, _ptr(keys), P, int(mbq), int(mrq), _ptr(counts), _ptr(lengths),
+                                                      _ptr(stats)))
+        return counts, lengths, stats
 
     def hetsite_reference(self, rec: Records, P: int, planes, min_depth: int = 100, ref=None):
         """One resident chunk of normals into the het-site reference (ampli_hetsite_reference_records): ref int64 [3, 6, P]

@@ -8,6 +8,8 @@
 // Parity: UNPINNED -- the upstream program cannot run here (Mach-O, no source) and the reference holds no BAM fixture; the
 // semantics restate the published PILEUP mode (htslib pileup defaults) and are checked against an independent Python
 // restatement (oracle/pileup_oracle.py) on synthetic BAM files.
+// walk_bam (bam_walk.hpp) is the walk over the file itself -- positions, batches, header, carry, scanner -- with "what to launch
+// per batch" left to its caller: run_compute_counts below, and run_compute_indel_counts of run_ci.cpp.
 #include <fcntl.h>
 #include <sys/mman.h>
 #include <sys/stat.h>
@@ -24,6 +26,7 @@
 #include <sstream>
 #include <thread>
 
+#include "bam_walk.hpp"
 #include "hip_loader.hpp"
 #include "host.hpp"
 
@@ -134,12 +137,6 @@ void inflate_range(const Mapped &f, const std::vector<Block> &blocks, size_t b0,
     for (auto &t : th) t.join();
     if (failed.load()) throw Error{AMPLI_E_INVALID, why};
 }
-
-struct VcfLine {
-    std::string chrom, id, ref, alt;
-    int64_t pos = 0;
-    int64_t key_index = -1; // index into the sorted unique keys, -1: the chromosome is not in the BAM header
-};
 
 std::vector<VcfLine> read_positions(const std::string &path)
 {
@@ -270,54 +267,30 @@ void bam_scan(const std::string &bam, int n_threads, int64_t stats[4])
     stats[3] = malformed;
 }
 
-int run_compute_counts(const CcArgs &a)
+static double now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+double BamWalk::seconds() const { return now() - t_start; }
+
+BamWalk walk_bam(const std::string &vcf, const std::string &bam, int n_threads, BamDevice &dev, const BamSink &sink)
 {
-    try {
-        if (a.vcf.empty() || a.bam.empty() || a.out_dir.empty()) throw Error{AMPLI_E_INVALID, "vcf=, bam= and out= are required"};
-        const int threads = a.threads > 0 ? a.threads : 4;
-        auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-        const double t_start = now();
-        double t_inflate = 0, t_wait = 0;
+    BamWalk w;
+    const int threads = w.threads = n_threads > 0 ? n_threads : 4;
+    w.t_start = now();
+    double &t_inflate = w.t_inflate, &t_wait = w.t_wait;
+    {
         std::string why;
         const HipApi *api = hip_api(&why);
         if (!api) throw Error{AMPLI_E_HIP, "libamplisolve_hip.so could not be loaded (" + why + "); there is no CPU fallback"};
         if (api->device_count() <= 0) throw Error{AMPLI_E_HIP, "no MI355X visible; there is no CPU fallback"};
-        std::vector<VcfLine> lines = read_positions(a.vcf);
-        if (lines.empty()) throw Error{AMPLI_E_INVALID, "no position could be read from " + a.vcf};
+        w.lines = read_positions(vcf);
+        std::vector<VcfLine> &lines = w.lines;
+        if (lines.empty()) throw Error{AMPLI_E_INVALID, "no position could be read from " + vcf};
 
-        Mapped f(a.bam);
-        const auto blocks = bgzf_blocks(f, a.bam);
-        if (blocks.empty()) throw Error{AMPLI_E_INVALID, a.bam + ": empty BAM file"};
+        Mapped f(bam);
+        const auto blocks = bgzf_blocks(f, bam);
+        if (blocks.empty()) throw Error{AMPLI_E_INVALID, bam + ": empty BAM file"};
+        for (auto &b : blocks) w.total_bytes += b.isize;
 
-        struct Ctx {
-            const HipApi *api;
-            ampli_ctx *ctx = nullptr;
-            std::vector<void *> allocs;
-            ~Ctx()
-            {
-                if (ctx) {
-                    for (void *p : allocs) api->dev_free(ctx, p);
-                    api->ctx_destroy(ctx);
-                }
-            }
-            void check(int rc, const char *what)
-            {
-                if (rc != AMPLI_OK) throw Error{rc, std::string(what) + ": " + api->strerror_(rc) + (ctx ? std::string(" -- ") + api->last_error(ctx) : "")};
-            }
-            void *alloc(size_t n)
-            {
-                void *p = nullptr;
-                check(api->dev_alloc(ctx, n ? n : 16, &p), "ampli_dev_alloc");
-                allocs.push_back(p);
-                return p;
-            }
-            void release(void *p) // a slot's buffer is replaced by a larger one
-            {
-                if (!p) return;
-                allocs.erase(std::remove(allocs.begin(), allocs.end(), p), allocs.end());
-                check(api->dev_free(ctx, p), "ampli_dev_free");
-            }
-        } dev{api, nullptr, {}};
+        dev.api = api;
         int device = 0;
         if (const char *e = getenv("AMPLISOLVE_DEVICE")) device = atoi(e);
         dev.check(api->ctx_create(device, nullptr, &dev.ctx), "ampli_ctx_create");
@@ -338,10 +311,8 @@ int run_compute_counts(const CcArgs &a)
         Header hdr;
         bool have_header = false;
         uint64_t *d_keys = nullptr;
-        int32_t *d_counts = nullptr;
-        uint64_t *d_stats = nullptr;
         std::vector<uint64_t> keys;
-        int64_t P = 0, n_records = 0, malformed = 0;
+        int64_t &P = w.P, &n_records = w.n_records, &malformed = w.malformed;
 
         std::vector<unsigned char> carry; // the incomplete record (or header) at the end of the previous batch
         uint64_t stream_pos = 0;          // uncompressed bytes inflated so far (for messages)
@@ -360,16 +331,16 @@ int run_compute_counts(const CcArgs &a)
             hb.ensure(api, carry.size() + bytes + 16);
             if (!carry.empty()) memcpy(hb.p, carry.data(), carry.size());
             const double i0 = now();
-            inflate_range(f, blocks, b0, b1, hb.p + carry.size(), threads, a.bam);
+            inflate_range(f, blocks, b0, b1, hb.p + carry.size(), threads, bam);
             t_inflate += now() - i0;
             const size_t n = carry.size() + bytes;
             size_t from = 0;
             if (!have_header) {
-                if (!parse_header(hb.p, n, hdr, a.bam)) { // header longer than this batch: keep everything and read on
+                if (!parse_header(hb.p, n, hdr, bam)) { // header longer than this batch: keep everything and read on
                     carry.assign(hb.p, hb.p + n);
                     stream_pos += bytes;
                     b0 = b1;
-                    if (b0 >= blocks.size()) throw Error{AMPLI_E_INVALID, a.bam + ": truncated BAM header"};
+                    if (b0 >= blocks.size()) throw Error{AMPLI_E_INVALID, bam + ": truncated BAM header"};
                     continue;
                 }
                 have_header = true;
@@ -392,15 +363,12 @@ int run_compute_counts(const CcArgs &a)
                 }
                 if (P > 0) {
                     d_keys = (uint64_t *)dev.alloc((size_t)P * 8);
-                    d_counts = (int32_t *)dev.alloc((size_t)P * 8 * sizeof(int32_t));
-                    d_stats = (uint64_t *)dev.alloc(16);
                     dev.check(api->copy_h2d(dev.ctx, d_keys, keys.data(), (size_t)P * 8), "ampli_copy_h2d");
-                    dev.check(api->memset_d(dev.ctx, d_counts, 0, (size_t)P * 8 * sizeof(int32_t)), "ampli_memset_d");
-                    dev.check(api->memset_d(dev.ctx, d_stats, 0, 16), "ampli_memset_d");
+                    sink.panel(dev, P);
                 }
             }
             offs[slot].clear();
-            const size_t done = scan_records(hb.p, from, n, offs[slot], malformed, a.bam, stream_pos - carry.size());
+            const size_t done = scan_records(hb.p, from, n, offs[slot], malformed, bam, stream_pos - carry.size());
             stream_pos += bytes;
             carry.assign(hb.p + done, hb.p + n);
             n_records += (int64_t)offs[slot].size();
@@ -412,17 +380,43 @@ int run_compute_counts(const CcArgs &a)
                 if (d_off_cap[slot] < ob) { dev.release(d_off[slot]); d_off[slot] = dev.alloc(ob + ob / 8); d_off_cap[slot] = ob + ob / 8; }
                 dev.check(api->copy_h2d(dev.ctx, d_bam[slot], hb.p, done), "ampli_copy_h2d");
                 dev.check(api->copy_h2d(dev.ctx, d_off[slot], offs[slot].data(), ob), "ampli_copy_h2d");
-                dev.check(api->pileup_count(dev.ctx, (const uint8_t *)d_bam[slot], (const uint64_t *)d_off[slot], (int64_t)offs[slot].size(), d_keys, P,
-                                            a.mbq, a.mrq, d_counts, d_stats), "ampli_pileup_count");
+                sink.batch(dev, (const uint8_t *)d_bam[slot], (const uint64_t *)d_off[slot], (int64_t)offs[slot].size(), d_keys, P);
                 dev.check(api->event_record(dev.ctx, ev[slot]), "ampli_event_record");
                 busy[slot] = true;
             }
             b0 = b1;
             slot ^= 1;
         }
-        if (!have_header) throw Error{AMPLI_E_INVALID, a.bam + ": truncated BAM header"};
+        w.ref_names = hdr.ref_names;
+        if (!have_header) throw Error{AMPLI_E_INVALID, bam + ": truncated BAM header"};
         if (!carry.empty()) // a cut-off file or a desynchronised stream: no counts file is written from part of the reads
-            throw Error{AMPLI_E_INVALID, a.bam + ": " + std::to_string(carry.size()) + " bytes behind the last complete alignment record (truncated or corrupt file)"};
+            throw Error{AMPLI_E_INVALID, bam + ": " + std::to_string(carry.size()) + " bytes behind the last complete alignment record (truncated or corrupt file)"};
+        dev.check(api->sync(dev.ctx), "ampli_sync"); // the last uploads read the pinned buffers freed below
+    } // the events, the pinned buffers and the mapping go here; dev and what the sink allocated under it stay for the caller
+    return w;
+}
+
+int run_compute_counts(const CcArgs &a)
+{
+    try {
+        if (a.vcf.empty() || a.bam.empty() || a.out_dir.empty()) throw Error{AMPLI_E_INVALID, "vcf=, bam= and out= are required"};
+        BamDevice dev;
+        int32_t *d_counts = nullptr;
+        uint64_t *d_stats = nullptr;
+        BamSink sink;
+        sink.panel = [&](BamDevice &d, int64_t P) {
+            d_counts = (int32_t *)d.alloc((size_t)P * 8 * sizeof(int32_t));
+            d_stats = (uint64_t *)d.alloc(16);
+            d.check(d.api->memset_d(d.ctx, d_counts, 0, (size_t)P * 8 * sizeof(int32_t)), "ampli_memset_d");
+            d.check(d.api->memset_d(d.ctx, d_stats, 0, 16), "ampli_memset_d");
+        };
+        sink.batch = [&](BamDevice &d, const uint8_t *d_bam, const uint64_t *d_off, int64_t n_reads, const uint64_t *d_keys, int64_t P) {
+            d.check(d.api->pileup_count(d.ctx, d_bam, d_off, n_reads, d_keys, P, a.mbq, a.mrq, d_counts, d_stats), "ampli_pileup_count");
+        };
+        const BamWalk w = walk_bam(a.vcf, a.bam, a.threads, dev, sink);
+        const HipApi *api = dev.api;
+        const std::vector<VcfLine> &lines = w.lines;
+        const int64_t P = w.P, n_records = w.n_records, malformed = w.malformed;
 
         std::vector<int32_t> counts((size_t)P * 8, 0);
         uint64_t st[2] = {0, 0};
@@ -456,10 +450,8 @@ int run_compute_counts(const CcArgs &a)
                   << st[0] << " kept (mrq " << a.mrq << "), " << st[1] << " bases counted (mbq " << a.mbq << ") over " << lines.size() << " listed positions\n\t"
                   << written << " lines with depth >= " << a.mdc << " written to " << out_path << std::endl;
         if (getenv("AMPLISOLVE_TIMING")) {
-            size_t total = 0;
-            for (auto &b : blocks) total += b.isize;
-            std::cerr << "TIMING total " << now() - t_start << " inflate " << t_inflate << " (" << threads << " threads, " << total << " bytes) device_wait " << t_wait
-                      << std::endl;
+            std::cerr << "TIMING total " << w.seconds() << " inflate " << w.t_inflate << " (" << w.threads << " threads, " << w.total_bytes << " bytes) device_wait "
+                      << w.t_wait << std::endl;
         }
         if (a.stats) { a.stats[0] = n_records; a.stats[1] = (int64_t)st[0]; a.stats[2] = (int64_t)st[1]; a.stats[3] = written; }
         return 0;

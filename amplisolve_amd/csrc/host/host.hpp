@@ -209,6 +209,15 @@ struct CcArgs {
     std::string *error = nullptr;
 };
 int run_compute_counts(const CcArgs &a);
+// ---- run_ci.cpp ----
+// computeIndelCounts: one BAM file -> <out_dir>/<name>.INDEL.PILEUP.ASEQ + <name>.INDEL.LENGTHS.txt (+ the table at refbases)
+struct CiArgs {
+    std::string vcf, bam, out_dir, refbases; // refbases: optional path of the `chrom pos A` table for AMPLISOLVE_REFBASES_FILE
+    int threads = 4, mbq = 20, mrq = 20, mdc = 20;
+    int64_t *stats = nullptr; // optional [4]: records, reads kept, junctions counted, lines written
+    std::string *error = nullptr;
+};
+int run_compute_indel_counts(const CiArgs &a);
 // BGZF + BAM structure only (no GPU): stats[4] = alignment records, uncompressed bytes, references, malformed records
 void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // ---- pipeline.cpp ----

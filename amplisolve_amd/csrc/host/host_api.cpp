@@ -239,6 +239,19 @@ extern "C" int ampli_host_compute_counts(const char *vcf, const char *bam, const
     return rc;
 }
 
+extern "C" int ampli_host_compute_indel_counts(const char *vcf, const char *bam, const char *out_dir, const char *refbases, int32_t threads, int32_t mbq,
+                                               int32_t mrq, int32_t mdc, int64_t *stats)
+{
+    if (!vcf || !bam || !out_dir) { g_err = "vcf, bam and out_dir are required"; return AMPLI_E_INVALID; }
+    CiArgs a;
+    a.vcf = vcf; a.bam = bam; a.out_dir = out_dir; a.refbases = refbases ? refbases : ""; a.threads = threads; a.mbq = mbq; a.mrq = mrq; a.mdc = mdc; a.stats = stats;
+    std::string err;
+    a.error = &err;
+    const int rc = run_compute_indel_counts(a);
+    if (rc) g_err = err;
+    return rc;
+}
+
 extern "C" int ampli_host_bam_scan(const char *bam, int32_t threads, int64_t *stats)
 {
     if (!bam || !stats) { g_err = "bam and stats are required"; return AMPLI_E_INVALID; }

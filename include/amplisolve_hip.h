@@ -1196,6 +1196,42 @@ int ampli_synth_ref(ampli_ctx *ctx, uint8_t *d_ref_code, int64_t P, uint64_t see
 int ampli_pileup_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *d_rec_off, int64_t n_reads, const uint64_t *d_keys, int64_t P,
                        int32_t mbq, int32_t mrq, int32_t *d_counts, uint64_t *d_stats);
 
+/*
+ * Indel counting over the same alignment records: per panel position and read strand, how many reads show an insertion, a
+ * deletion or neither at the junction behind that position, written into the record slots every other entry point reads.  The stream
+ * contract is ampli_pileup_count's (d_bam, d_rec_off ascending, 16-byte alignment, 16 readable bytes behind the last record, d_keys).
+ *
+ * Kept reads are exactly those of ampli_pileup_count: placed, none of the flags 0x4 / 0x100 / 0x200 / 0x400, and MAPQ >= mrq.
+ * Effective operations: a read's CIGAR is taken with every operation of length 0 and every P operation removed.  What remains are the
+ * read's effective operations.
+ * Junction p is the boundary between reference positions p and p + 1 (1-based).  p must be a panel key.  p + 1 need not be.
+ * Observing a junction: a read observes junction p when its base at p lies in an M, = or X column and that base's quality is >= mbq.
+ * There is no condition on the base's letter.  The next effective column or operation must be one of these:
+ *   another M / = / X column at p + 1, in the same operation or the next one          slot 0, A ("reference junction")
+ *   one I of length L >= 1, followed directly by an M / = / X operation                slot 1, C (insertion)
+ *   one D of length L >= 1, followed directly by an M / = / X operation                slot 2, G (deletion)
+ * Anything else leaves the junction unobserved by that read, and it is counted nowhere.  That covers the read's last aligned column, a
+ * soft or hard clip, an N, I then D, D then I, two I, and an indel that opens or closes the alignment.
+ * Reverse-strand reads (flag 0x10) also add to slot + 4.  Slots 3 and 7 (T) are never written.  So per position A + C + G is the number
+ * of kept reads that observed the junction, and the record's depth is what the existing gates expect it to be.
+ *
+ * State machine: the definition is a state machine over the effective operations and needs no look-ahead.  Its state is "previous
+ * effective operation was a match run, ending at column p with query index q" plus at most one pending indel.
+ *   A match run first settles what is pending: the pending event at its anchor, or a reference junction between two adjacent match runs.
+ *   It then counts its own len - 1 inner junctions as reference junctions.
+ *   I or D behind a match run with nothing pending becomes pending.
+ *   Every other case clears both states.
+ *
+ * d_counts int32 [P][8] is ACCUMULATED into.  d_lengths (optional, may be NULL) int32 [P][2][AMPLI_INDEL_LEN_BINS] is accumulated into:
+ * kind 0 is insertion and kind 1 is deletion, the bin is min(L, 32) - 1, both strands are pooled, and over the bins of a kind the sum
+ * equals slot 1 (kind 0) or slot 2 (kind 1).  d_stats (optional, 2 words, accumulated): reads kept, junctions counted over all three
+ * slots.  Bad arguments give AMPLI_E_INVALID ("bad argument").  n_reads == 0 or P == 0 is a no-op that returns AMPLI_OK.
+ * Limits: events are taken where the aligner placed them (no left-alignment), the inserted bases are not recorded, all lengths at a
+ * junction share one count, complex events (I next to D) are ignored.
+ */
+int ampli_pileup_indel_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *d_rec_off, int64_t n_reads, const uint64_t *d_keys, int64_t P,
+                             int32_t mbq, int32_t mrq, int32_t *d_counts, int32_t *d_lengths, uint64_t *d_stats);
+
 /* tuning knobs.  reduce_sample_splits: 0 = automatic.  reduce_general: 0 = the fast error_reduce kernel
  * (valid while every strand depth is < 2^22; it raises AMPLI_FLAG_RERUN_GENERAL otherwise), 1 = the literal
  * kernel that follows the reference operation by operation for any depth (slower).  reduce_lane_groups: lane

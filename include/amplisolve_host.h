@@ -157,6 +157,12 @@ int ampli_host_run_variant_calling_sharded(const char *error_file, const char *t
  * kept, bases counted, lines written. */
 int ampli_host_compute_counts(const char *vcf, const char *bam, const char *out_dir, int32_t threads, int32_t mbq, int32_t mrq, int32_t mdc,
                               int64_t *stats);
+/* computeIndelCounts: the same walk with ampli_pileup_indel_count per batch -> <out_dir>/<bam name>.INDEL.PILEUP.ASEQ (ref A,
+ * A = reference junctions, C = insertions, G = deletions behind the position) and <out_dir>/<bam name>.INDEL.LENGTHS.txt, and, when refbases
+ * is not NULL or empty, the `chrom pos A` table at that path.  A failure leaves no output file behind.  stats (optional) [4]: alignment
+ * records, reads kept, junctions counted, lines written. */
+int ampli_host_compute_indel_counts(const char *vcf, const char *bam, const char *out_dir, const char *refbases, int32_t threads, int32_t mbq,
+                                    int32_t mrq, int32_t mdc, int64_t *stats);
 /* the container only (no GPU): stats[4] = alignment records, uncompressed bytes, reference sequences, malformed records (complete
  * records whose CIGAR does not add up to their l_seq or whose fields overrun their block: counted and skipped).  Bytes behind the
  * last complete record -- a truncated or desynchronised stream -- are an error (AMPLI_E_INVALID), not a count: since round 3 the call

@@ -217,4 +217,8 @@ typedef struct ampli_fraction_params {
     double z2;
 } ampli_fraction_params;
 
+/* Indel counting from alignments: the length bins per (position, kind) of ampli_pileup_indel_count's second output, kind 0 =
+ * insertion, kind 1 = deletion; an event of length L falls into bin min(L, AMPLI_INDEL_LEN_BINS) - 1, so the last bin holds L >= 32. */
+#define AMPLI_INDEL_LEN_BINS 32
+
 #endif /* AMPLISOLVE_TYPES_H */
