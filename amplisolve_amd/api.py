@@ -832,6 +832,57 @@ class Context:
                                                       _ptr(stats)))
         return counts, lengths, stats
 
+    def _amplicons(self, lo, hi, reach, amp_off, counts):
+        """the four sorted amplicon arrays of amplicon_count / amplicon_layers, checked: (lo, hi, reach, amp_off, A, W).  W is the rows of
+        `counts` where the caller has them (no read-back), amp_off[A] otherwise.  A pointer is required even where nothing is read
+        through it (A = 0)."""
+        import torch
+
+        A = int(lo.numel())
+        assert _ok(lo, torch.int64, (A,)) and _ok(hi, torch.int64, (A,)) and _ok(reach, torch.int64, (A,)) and _ok(amp_off, torch.int64, (A + 1,))
+        W = int(counts.shape[0]) if counts is not None else int(amp_off[-1])
+        if A == 0:
+            lo = hi = reach = torch.zeros((1,), dtype=torch.int64, device=self.device)
+        return lo, hi, reach, amp_off, A, W
+
+    def amplicon_count(self, bam, rec_off, lo, hi, reach, amp_off, mbq: int = 20, mrq: int = 20, min_overlap: int = 50, counts=None, amp_reads=None,
+                       stats=None):
+        """Amplicon-resolved counts of a batch of alignment records (ampli_pileup_amplicon_count): every kept read is assigned
+        to one amplicon and counted inside it only.  bam, rec_off as indel_count takes them; lo, hi, reach: int64 [A], the amplicons as
+        (reference id << 32 | first / last position), sorted by lo then hi, and the running maximum of hi; amp_off: int64 [A + 1], the
+        exclusive prefix sum of their lengths (amp_off[A] = W).  Returns (counts, amp_reads, stats): counts int32 [W, 8] per walk entry
+        amp_off[a] + (x - first[a]), amp_reads int64 [A, 2] (assigned forward and reverse reads) and stats int64 [4] (reads kept, reads
+        assigned, bases counted, bases clipped).  All three are ADDED TO: a given buffer accumulates, None starts a new one at zero;
+        stats=False: not computed (NULL) and returned as None."""
+        import torch
+
+        assert _ok(bam, torch.uint8, (None,)) and _ok(rec_off, torch.int64, (None,))
+        lo, hi, reach, amp_off, A, W = self._amplicons(lo, hi, reach, amp_off, counts)
+        counts = self._out(counts, torch.int32, (W, 8), zero=True)
+        amp_reads = self._out(amp_reads, torch.int64, (A, 2), zero=True)
+        stats = None if stats is False else self._out(stats, torch.int64, (4,), zero=True)
+        self._check(self.lib.ampli_pileup_amplicon_count(self.h, _ptr(bam), _ptr(rec_off), int(rec_off.numel()), _ptr(lo), _ptr(hi), _ptr(reach), _ptr(amp_off), A, W,
+                                                         int(mbq), int(mrq), int(min_overlap), _ptr(counts), _ptr(amp_reads), _ptr(stats)))
+        return counts, amp_reads, stats
+
+    def amplicon_layers(self, counts, lo, hi, reach, amp_off, keys, L: int = 2, layers=None, layer_amp=None, total=None):
+        """The counts of amplicon_count gathered per listed position (ampli_amplicon_layers).  keys: int64 [P], positions as
+        (reference id << 32 | 1-based position), any order, repeats allowed.  Returns (layers, layer_amp, total): layers int32 [L, P, 8],
+        the record of the l-th amplicon over the position in sorted order (slot 0 = INT32_MIN, the rest 0, where there is none);
+        layer_amp int32 [L, P], that amplicon's sorted index or -1; total int32 [P, 8], the sum over all amplicons over the position.
+        All three are overwritten."""
+        import torch
+
+        lo, hi, reach, amp_off, A, W = self._amplicons(lo, hi, reach, amp_off, counts)
+        P = int(keys.numel())
+        assert _ok(keys, torch.int64, (P,)) and _ok(counts, torch.int32, (W, 8))
+        layers = self._out(layers, torch.int32, (L, P, 8))
+        layer_amp = self._out(layer_amp, torch.int32, (L, P))
+        total = self._out(total, torch.int32, (P, 8))
+        self._check(self.lib.ampli_amplicon_layers(self.h, _ptr(counts), _ptr(lo), _ptr(hi), _ptr(reach), _ptr(amp_off), A, W, _ptr(keys), P, int(L), _ptr(layers),
+                                                   _ptr(layer_amp), _ptr(total)))
+        return layers, layer_amp, total
+
     def hetsite_reference(self, rec: Records, P: int, planes, min_depth: int = 100, ref=None):
         """One resident chunk of normals into the het-site reference (ampli_hetsite_reference_records): ref int64 [3, 6, P]
         (AI_REF_CNT / _LO / _HI per pair code and position) is ADDED TO -- a new one starts at zero, streamed chunks accumulate.  planes:

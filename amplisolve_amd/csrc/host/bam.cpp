@@ -345,6 +345,7 @@ BamWalk walk_bam(const std::string &vcf, const std::string &bam, int n_threads, 
                 }
                 have_header = true;
                 from = hdr.end;
+                if (sink.header) sink.header(hdr.ref_names);
                 // the panel as sorted unique keys (BAM reference id << 32 | position)
                 std::unordered_map<std::string, int> rid;
                 for (size_t i = 0; i < hdr.ref_names.size(); ++i) rid.emplace(hdr.ref_names[i], (int)i);

@@ -3,7 +3,10 @@
 // while batch k is uploaded and counted), the header that may span batches, the incomplete record carried from batch to batch, the
 // record scanner.  What differs between the commands is what they launch per batch: a BamSink.  The body is in bam.cpp.
 #pragma once
+#include <unistd.h>
+
 #include <algorithm>
+#include <cstdio>
 #include <functional>
 #include <string>
 #include <vector>
@@ -55,6 +58,9 @@ struct BamDevice {
 
 // what to launch per batch
 struct BamSink {
+    // optional; once, when the BAM header is read, before `panel` and whatever P is: the names of the file's reference sequences, in
+    // the order of their ids (what a sink needs to turn chromosome names of its own into keys)
+    std::function<void(const std::vector<std::string> &ref_names)> header;
     // once, when the BAM header is read and the panel has P > 0 positions in it: allocate and clear the outputs
     std::function<void(BamDevice &dev, int64_t P)> panel;
     // per batch with records (only when P > 0): n_reads records of d_bam at d_off, enqueued on the context's stream
@@ -69,6 +75,38 @@ struct BamWalk {
     int threads = 0;
     size_t total_bytes = 0; // uncompressed
     double seconds() const; // since t_start
+};
+
+// the output files of a command that writes several: all of them or none
+struct TempFiles { // <path>.tmp<pid> for every output; renamed into place by commit(), removed by the destructor otherwise
+    std::vector<std::pair<std::string, std::string>> files; // temporary name, final name
+    bool done = false;
+    FILE *open(const std::string &path)
+    {
+        const std::string tmp = path + ".tmp" + std::to_string((long long)getpid());
+        FILE *o = fopen(tmp.c_str(), "w");
+        if (!o) throw Error{AMPLI_E_INVALID, "cannot write " + path};
+        files.emplace_back(tmp, path);
+        return o;
+    }
+    void close(FILE *o, const std::string &path)
+    {
+        if (fclose(o) != 0) throw Error{AMPLI_E_INVALID, "cannot write " + path};
+    }
+    void commit()
+    {
+        for (size_t i = 0; i < files.size(); ++i)
+            if (rename(files[i].first.c_str(), files[i].second.c_str()) != 0) {
+                for (size_t k = 0; k < i; ++k) unlink(files[k].second.c_str());
+                throw Error{AMPLI_E_INVALID, "cannot write " + files[i].second};
+            }
+        done = true;
+    }
+    ~TempFiles()
+    {
+        if (!done)
+            for (auto &f : files) unlink(f.first.c_str());
+    }
 };
 
 // Loads the HIP library, reads the positions, opens the file, creates dev's context and walks the file.  Throws Error.

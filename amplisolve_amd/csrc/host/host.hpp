@@ -150,6 +150,7 @@ struct PhaseClock {
 };
 // ---- panel.cpp ----
 void panel_from_bed(const std::string &bed_path, Panel &out);                   // throws Error
+std::vector<BedRow> bed_rows(const std::string &bed_path);                      // the rows alone, as Panel::rows keeps them; throws Error
 void panel_load_refbases_file(Panel &p, const std::string &path);               // chrom pos base per line (EE:963)
 void panel_load_fasta(Panel &p, const std::string &fasta_path);                 // replaces `samtools faidx` (EE:644)
 void panel_write_interm_files(const Panel &p, const std::string &dir, int seed);// EE:601, 657-664
@@ -218,6 +219,45 @@ struct CiArgs {
     std::string *error = nullptr;
 };
 int run_compute_indel_counts(const CiArgs &a);
+// ---- run_ca.cpp ----
+// The amplicons of a BED file as ampli_pileup_amplicon_count takes them: the rows whose chromosome is among ref_names and
+// whose interval is 1 <= start <= end < 2^31, as keys sorted by lo, then hi (ties in BED order), with reach, the walk offsets and the
+// permutation back to BED order.  A row that is left out keeps sorted_of_row = -1: it is still reported, with zeros.
+struct AmpliconArrays {
+    std::vector<uint64_t> lo, hi, reach; // [A]: ref_id << 32 | first, ref_id << 32 | last, max(hi[0..a])
+    std::vector<int64_t> amp_off;        // [A + 1]: exclusive prefix sum of the lengths
+    std::vector<int32_t> row_of;         // [A]: sorted index -> BED row
+    std::vector<int32_t> sorted_of_row;  // [rows]: BED row -> sorted index, or -1
+    int64_t A() const { return (int64_t)lo.size(); }
+    int64_t W() const { return amp_off.empty() ? 0 : amp_off.back(); }
+    // the sorted indices [first, last] among which the amplicons over `key` lie (those with hi[a] >= key); empty when first > last
+    void candidates(uint64_t key, int64_t &first, int64_t &last) const;
+};
+AmpliconArrays amplicon_arrays(const std::vector<BedRow> &rows, const std::vector<std::string> &ref_names); // Error{AMPLI_E_RANGE}: W >= 2^31
+// computeAmpliconCounts: one BAM file -> <out_dir>/<name>.AMPLICON.PILEUP.ASEQ, .AMPLICON.READS.txt, .AMPLICON.OVERLAPS.txt and,
+// with layers_dir, <layers_dir>/<name>.AMP1.PILEUP.ASEQ, .AMP2.PILEUP.ASEQ and <name>.pairs.txt.  The numbers as the command line gives them.
+struct CaArgs {
+    std::string vcf, bam, bed, out_dir, layers_dir;
+    std::string threads = "4", mbq = "20", mrq = "20", mdc = "20", min_overlap = "50";
+    int64_t *stats = nullptr; // optional [6]: records, reads kept, reads assigned, bases counted, bases clipped, lines written
+    std::string *error = nullptr;
+};
+int run_compute_amplicon_counts(const CaArgs &a);
+// what the device computed for one file, on the host, and the writer of the command's files from it (no device: tools/amplicon_count_sanitize.cpp)
+struct AmpliconCounts {
+    std::vector<int32_t> counts;               // [W][8]
+    std::vector<int64_t> amp_reads;            // [A][2]
+    uint64_t stats[4] = {0, 0, 0, 0};          // reads kept, reads assigned, bases counted, bases clipped
+    std::vector<uint64_t> keys;                // [n]: the listed positions with a known chromosome, in the list's order
+    std::vector<int32_t> layers, layer_amp, total; // [2][n][8], [2][n], [n][8] over `keys`
+};
+struct AmpliconListed { // one listed position: what the ASEQ line prints, and its index into AmpliconCounts::keys (-1: unknown chromosome)
+    std::string chrom, id, ref, alt;
+    int64_t pos = 0, slot = -1;
+};
+// returns the lines written to <name>.AMPLICON.PILEUP.ASEQ; every file under a temporary name, renamed into place at the end
+int64_t write_amplicon_files(const std::string &out_dir, const std::string &layers_dir, const std::string &name, const std::vector<BedRow> &rows,
+                             const AmpliconArrays &amps, const std::vector<AmpliconListed> &listed, const AmpliconCounts &c, int mdc);
 // BGZF + BAM structure only (no GPU): stats[4] = alignment records, uncompressed bytes, references, malformed records
 void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // ---- pipeline.cpp ----

@@ -252,6 +252,45 @@ extern "C" int ampli_host_compute_indel_counts(const char *vcf, const char *bam,
     return rc;
 }
 
+extern "C" int ampli_host_compute_amplicon_counts(const char *vcf, const char *bam, const char *bed, const char *out_dir, const char *layers_dir, int32_t threads,
+                                                  int32_t mbq, int32_t mrq, int32_t mdc, int32_t min_overlap, int64_t *stats)
+{
+    if (!vcf || !bam || !bed || !out_dir) { g_err = "vcf, bam, bed and out_dir are required"; return AMPLI_E_INVALID; }
+    CaArgs a;
+    a.vcf = vcf; a.bam = bam; a.bed = bed; a.out_dir = out_dir; a.layers_dir = layers_dir ? layers_dir : "";
+    a.threads = std::to_string(threads); a.mbq = std::to_string(mbq); a.mrq = std::to_string(mrq); a.mdc = std::to_string(mdc);
+    a.min_overlap = std::to_string(min_overlap); a.stats = stats;
+    std::string err;
+    a.error = &err;
+    const int rc = run_compute_amplicon_counts(a);
+    if (rc) g_err = err;
+    return rc;
+}
+
+extern "C" int64_t ampli_host_amplicon_arrays(const char *bed, const char *ref_names, int64_t cap, uint64_t *lo, uint64_t *hi, uint64_t *reach, int64_t *amp_off,
+                                              int32_t *row_of, int64_t *n_rows)
+{
+    if (!bed || !ref_names || cap < 0 || !lo || !hi || !reach || !amp_off || !row_of) { g_err = "bad argument"; return AMPLI_E_INVALID; }
+    try {
+        const std::vector<BedRow> rows = bed_rows(bed);
+        std::vector<std::string> names;
+        for (const char *p = ref_names; *p;) {
+            const char *e = strchr(p, '\n');
+            names.emplace_back(p, e ? (size_t)(e - p) : strlen(p));
+            p = e ? e + 1 : p + strlen(p);
+        }
+        const AmpliconArrays a = amplicon_arrays(rows, names);
+        if (n_rows) *n_rows = (int64_t)rows.size();
+        if (a.A() > cap) { g_err = "more amplicons than the buffers hold"; return AMPLI_E_RANGE; }
+        for (int64_t i = 0; i < a.A(); ++i) { lo[i] = a.lo[i]; hi[i] = a.hi[i]; reach[i] = a.reach[i]; amp_off[i] = a.amp_off[i]; row_of[i] = a.row_of[i]; }
+        amp_off[a.A()] = a.W();
+        return a.A();
+    } catch (const Error &e) {
+        g_err = e.msg;
+        return e.code ? e.code : -1;
+    }
+}
+
 extern "C" int ampli_host_bam_scan(const char *bam, int32_t threads, int64_t *stats)
 {
     if (!bam || !stats) { g_err = "bam and stats are required"; return AMPLI_E_INVALID; }

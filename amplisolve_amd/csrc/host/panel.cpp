@@ -62,25 +62,45 @@ void Panel::set_ref(uint32_t p, const std::string &base)
 
 // Lines as `fscanf("%1000[^\n]\n")` + `sscanf("%s\t%d\t%d...")` see them (EE:615-633): blank lines vanish,
 // CR is whitespace, columns beyond the third do not enter the position index (the fourth and the sixth are kept with the row).
+// one line of a BED file; false: a whitespace-only line
+static bool bed_row_of_line(std::string line, BedRow &r)
+{
+    char chrom[1024], name[1024], gene[1024];
+    int a = -1, b = -1;
+    if (line.size() > 1000) line.resize(1000);
+    const int got = sscanf(line.c_str(), "%1000s %d %d %1000s %*s %1000s", chrom, &a, &b, name, gene);
+    if (got < 1) return false;
+    r.chrom = chrom;
+    r.start = a;
+    r.end = b;
+    if (got >= 4) r.name = name; // the position index does not depend on these two
+    if (got >= 5) r.gene = gene;
+    return true;
+}
+
+std::vector<BedRow> bed_rows(const std::string &bed_path)
+{
+    std::ifstream in(bed_path);
+    if (!in) throw Error{AMPLI_E_INVALID, "Cannot open file: " + bed_path};
+    std::vector<BedRow> rows;
+    std::string line;
+    while (std::getline(in, line)) {
+        BedRow r;
+        if (bed_row_of_line(line, r)) rows.push_back(r);
+    }
+    return rows;
+}
+
 void panel_from_bed(const std::string &bed_path, Panel &out)
 {
     std::ifstream in(bed_path);
     if (!in) throw Error{AMPLI_E_INVALID, "Cannot open file: " + bed_path};
     std::string line;
     while (std::getline(in, line)) {
-        char chrom[1024], name[1024], gene[1024];
-        int a = -1, b = -1;
-        if (line.size() > 1000) line.resize(1000);
-        const int got = sscanf(line.c_str(), "%1000s %d %d %1000s %*s %1000s", chrom, &a, &b, name, gene);
-        if (got < 1) continue; // whitespace-only line
         BedRow r;
-        r.chrom = chrom;
-        r.start = a;
-        r.end = b;
-        if (got >= 4) r.name = name; // the position index below does not depend on these two
-        if (got >= 5) r.gene = gene;
+        if (!bed_row_of_line(line, r)) continue;
         out.rows.push_back(r);
-        for (int idx = a; idx <= b; ++idx) {
+        for (int idx = r.start; idx <= r.end; ++idx) {
             const size_t before = out.pos_coord.size();
             const int p = out.add_position(r.chrom, idx);
             if (out.pos_coord.size() == before) out.dup[p] = 1; // listed again: `sort | uniq -d` (EE:663)

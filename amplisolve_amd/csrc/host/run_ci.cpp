@@ -14,41 +14,6 @@
 
 namespace ampli {
 
-namespace {
-
-struct TempFiles { // <path>.tmp<pid> for every output; renamed into place by commit(), removed by the destructor otherwise
-    std::vector<std::pair<std::string, std::string>> files; // temporary name, final name
-    bool done = false;
-    FILE *open(const std::string &path)
-    {
-        const std::string tmp = path + ".tmp" + std::to_string((long long)getpid());
-        FILE *o = fopen(tmp.c_str(), "w");
-        if (!o) throw Error{AMPLI_E_INVALID, "cannot write " + path};
-        files.emplace_back(tmp, path);
-        return o;
-    }
-    void close(FILE *o, const std::string &path)
-    {
-        if (fclose(o) != 0) throw Error{AMPLI_E_INVALID, "cannot write " + path};
-    }
-    void commit()
-    {
-        for (size_t i = 0; i < files.size(); ++i)
-            if (rename(files[i].first.c_str(), files[i].second.c_str()) != 0) {
-                for (size_t k = 0; k < i; ++k) unlink(files[k].second.c_str());
-                throw Error{AMPLI_E_INVALID, "cannot write " + files[i].second};
-            }
-        done = true;
-    }
-    ~TempFiles()
-    {
-        if (!done)
-            for (auto &f : files) unlink(f.first.c_str());
-    }
-};
-
-} // namespace
-
 int run_compute_indel_counts(const CiArgs &a)
 {
     try {

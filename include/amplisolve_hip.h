@@ -171,6 +171,13 @@ extern "C" {
  *        cleared, nothing is added to), empty lists included (AMPLI_TF_NA and zeros).  Nothing else is written -- the other chunks' rows
  *        of a larger matrix included.  d_list_off is read at [0, L], d_list_cell and d_list_w at [0, W) at most, d_ref_code at [0, P),
  *        d_thr at [0, 8 P), a record only at a listed position below P of a row below n_samples.
+ *   (C29) amplicon-resolved counting (tests/test_gpu_amplicon_count_contracts.py): ampli_pileup_amplicon_count ADDS TO d_counts inside
+ *        [0, W) records, to d_amp_reads inside [0, A) pairs and, when it is not NULL, to the four words of d_stats (zero them for the
+ *        counts of one call; batches of one file add up).  Nothing else is written.  d_lo, d_hi, d_reach are read at [0, A), d_amp_off
+ *        at [0, A).
+ *   (C30) amplicon layers: ampli_amplicon_layers FULLY OVERWRITES d_layers [L][P][8], d_layer_amp [L][P] and d_total [P][8] with plain
+ *        stores (one lane owns the cells of a position: nothing is cleared, nothing is added to), positions under no amplicon included
+ *        (absent-record markers, -1 and zeros).  Nothing else is written.  d_counts is read only at walk entries below W.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -1231,6 +1238,61 @@ int ampli_pileup_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *d_r
  */
 int ampli_pileup_indel_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *d_rec_off, int64_t n_reads, const uint64_t *d_keys, int64_t P,
                              int32_t mbq, int32_t mrq, int32_t *d_counts, int32_t *d_lengths, uint64_t *d_stats);
+
+/*
+ * Amplicon-resolved counting over the same alignment records: every kept read is assigned to the amplicon it came from and
+ * counted there only, so that a position under two amplicons keeps two records.  The stream contract is ampli_pileup_count's (d_bam,
+ * d_rec_off; this kernel reads the records straight from global memory and needs neither ascending offsets nor the 16 bytes behind).
+ *
+ * Amplicons.  There are A intervals on the BAM's references, 1-based and inclusive.  They are given as keys
+ * lo[a] = ref_id << 32 | first and hi[a] = ref_id << 32 | last.  They are sorted by lo ascending, then hi ascending.  The host sorts
+ * them and keeps the permutation back to BED order.  Intervals may overlap, nest and repeat.  reach[a] = max(hi[0..a]).  It is
+ * monotone, so the candidates of a read form a contiguous index range even with nested amplicons.  amp_off[a] is the exclusive prefix
+ * sum of the lengths last - first + 1, and W = amp_off[A].  Walk entry w = amp_off[a] + (x - first[a]) is the cell "position x as seen
+ * by amplicon a".  This is the same order as DESIGN 16's amp_off / amp_pos CSR for BED rows.
+ * Kept reads.  These are exactly the reads ampli_pileup_count keeps: the read is placed; none of the flags 0x4 / 0x100 / 0x200 / 0x400
+ * is set; MAPQ >= mrq.
+ * Span.  span_first = pos + 1.  span_last = pos + R, where R is the sum of the lengths of the read's M = X D N operations.  A read with
+ * R = 0 is unassigned.
+ * Overlap.  The overlap of a read with amplicon a is the number of reference positions in both intervals on the same reference.  It is
+ * 0 if there are none.
+ * Assignment.
+ *   1. The read belongs to the amplicon of largest overlap.
+ *   2. Among ties, it belongs to the amplicon with the smallest anchor distance: |span_first - first[a]| for a forward read;
+ *      |span_last - last[a]| for a read with flag 0x10.  Amplicon reads start at their amplicon's own end.
+ *   3. Among ties still, it belongs to the lowest index a in the sorted order.
+ *   4. The assignment stands only if overlap >= 1 and overlap x 100 >= min_overlap x (span_last - span_first + 1).  The arithmetic is
+ *      int64 integer arithmetic.  min_overlap is an integer in [1, 100] and defaults to 50.
+ *   5. Otherwise the read is off-target.  It is counted in the statistics and nowhere else.
+ * Counting.  For a read assigned to a, every M / = / X column adds 1 to counts[w][nt] when all of these hold: its reference position x
+ * satisfies first[a] <= x <= last[a]; its base is A/C/G/T; its base quality is >= mbq.  A reverse read also adds 1 to
+ * counts[w][4 + nt].  A column outside the amplicon's interval is clipped.  It is counted in no cell and tallied in the statistics
+ * (whatever its base and its quality).
+ * Outputs.  d_counts: int32 [W][8], accumulated into.  d_amp_reads: int64 [A][2], assigned forward and reverse reads, accumulated.
+ * d_stats: optional (may be NULL), uint64 [4], accumulated.  Its four words are reads kept, reads assigned, bases counted and bases
+ * clipped.  d_amp_off is read at [0, A); W is passed beside it.
+ * Refusals.  AMPLI_E_RANGE: W >= 2^31; more than 2^31 - 1 read groups.  AMPLI_E_INVALID: min_overlap outside [1, 100]; a null required
+ * pointer; negative sizes.  A = 0 or n_reads = 0 is a successful no-op.
+ * Stated limits.  A read is assigned from its alignment alone, not from its primer sequence.  A chimeric read is given to its larger
+ * part.  An amplicon wholly inside another wins only reads that fit it better by the anchor rule.
+ */
+int ampli_pileup_amplicon_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *d_rec_off, int64_t n_reads, const uint64_t *d_lo,
+                                const uint64_t *d_hi, const uint64_t *d_reach, const int64_t *d_amp_off, int64_t A, int64_t W, int32_t mbq,
+                                int32_t mrq, int32_t min_overlap, int32_t *d_counts, int64_t *d_amp_reads, uint64_t *d_stats);
+/*
+ * Layers (a gather over the counts of ampli_pileup_amplicon_count).  For every listed panel position d_keys[p] (reference id
+ * << 32 | 1-based position; any order, repeats allowed), take the amplicons that cover it, in sorted order.  Layer l < L is the record
+ * of the l-th covering amplicon.  Where there is none, it is the project's absent-record marker: slot 0 = INT32_MIN, the rest 0.
+ * d_layers: int32 [L][P][8].  d_layer_amp: int32 [L][P], that amplicon's sorted index, or -1.  d_total: int32 [P][8], the sum over ALL
+ * covering amplicons, including those beyond L.  Every output cell has one owner and is overwritten, not accumulated.  A position under
+ * no amplicon gets zeros in d_total.  d_counts, d_layers and d_total are 16-byte aligned.  L = 0 gives the totals alone (d_layers and
+ * d_layer_amp may then be NULL).
+ * Refusals as above (AMPLI_E_RANGE: W >= 2^31; AMPLI_E_INVALID: a null required pointer, negative sizes).  A = 0 or P = 0 is a
+ * successful no-op.  Layer order is genomic and not biological.
+ */
+int ampli_amplicon_layers(ampli_ctx *ctx, const int32_t *d_counts, const uint64_t *d_lo, const uint64_t *d_hi, const uint64_t *d_reach,
+                          const int64_t *d_amp_off, int64_t A, int64_t W, const uint64_t *d_keys, int64_t P, int32_t L, int32_t *d_layers,
+                          int32_t *d_layer_amp, int32_t *d_total);
 
 /* tuning knobs.  reduce_sample_splits: 0 = automatic.  reduce_general: 0 = the fast error_reduce kernel
  * (valid while every strand depth is < 2^22; it raises AMPLI_FLAG_RERUN_GENERAL otherwise), 1 = the literal

@@ -163,6 +163,19 @@ int ampli_host_compute_counts(const char *vcf, const char *bam, const char *out_
  * records, reads kept, junctions counted, lines written. */
 int ampli_host_compute_indel_counts(const char *vcf, const char *bam, const char *out_dir, const char *refbases, int32_t threads, int32_t mbq,
                                     int32_t mrq, int32_t mdc, int64_t *stats);
+/* computeAmpliconCounts: the same walk with ampli_pileup_amplicon_count per batch and one ampli_amplicon_layers behind it ->
+ * <out_dir>/<bam name>.AMPLICON.PILEUP.ASEQ, .AMPLICON.READS.txt, .AMPLICON.OVERLAPS.txt and, when layers_dir is not NULL or empty (and differs
+ * from out_dir), <layers_dir>/<bam name>.AMP1.PILEUP.ASEQ, .AMP2.PILEUP.ASEQ and <bam name>.pairs.txt.  bed: the panel's amplicons.  Bad numbers
+ * (min_overlap outside 1 .. 100) and unreadable inputs are refused before the device is opened; a failure leaves no output file behind.
+ * stats (optional) [6]: alignment records, reads kept, reads assigned, bases counted, bases clipped, lines written. */
+int ampli_host_compute_amplicon_counts(const char *vcf, const char *bam, const char *bed, const char *out_dir, const char *layers_dir, int32_t threads,
+                                       int32_t mbq, int32_t mrq, int32_t mdc, int32_t min_overlap, int64_t *stats);
+/* The amplicons of a BED file as ampli_pileup_amplicon_count takes them (no GPU).  ref_names: the BAM header's reference names in
+ * the order of their ids, separated by '\n'.  A row enters iff its chromosome is among them and 1 <= start <= end.  Sorted by lo, then hi (ties
+ * in BED order): lo, hi, reach [cap], amp_off [cap + 1] (amp_off[A] = W), row_of [cap] (sorted index -> BED row, 0-based); *n_rows (optional): the
+ * rows of the file.  Returns A >= 0, or a negative code: AMPLI_E_RANGE when A > cap or W >= 2^31, AMPLI_E_INVALID for a bad argument or file. */
+int64_t ampli_host_amplicon_arrays(const char *bed, const char *ref_names, int64_t cap, uint64_t *lo, uint64_t *hi, uint64_t *reach, int64_t *amp_off,
+                                   int32_t *row_of, int64_t *n_rows);
 /* the container only (no GPU): stats[4] = alignment records, uncompressed bytes, reference sequences, malformed records (complete
  * records whose CIGAR does not add up to their l_seq or whose fields overrun their block: counted and skipped).  Bytes behind the
  * last complete record -- a truncated or desynchronised stream -- are an error (AMPLI_E_INVALID), not a count: since round 3 the call
