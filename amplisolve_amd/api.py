@@ -33,6 +33,7 @@ from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice
 #   AI_*                                   allelic imbalance: the planes of the het-site reference, the status of a cell (code = status *
 #                                          8 + pair, AI_NO_PAIR: none), the untested score, the five sums of a region and the verdicts
 #   INDEL_LEN_BINS                         indel_count: the length bins per (position, kind) of its second output
+#   EVIDENCE_*                             read_evidence: the metrics per (position, nt), their indices and the bins of each
 globals().update({name[len("AMPLI_"):]: value for name, value in CONSTANTS.items()})
 
 # Python's own
@@ -882,6 +883,38 @@ class Context:
         self._check(self.lib.ampli_amplicon_layers(self.h, _ptr(counts), _ptr(lo), _ptr(hi), _ptr(reach), _ptr(amp_off), A, W, _ptr(keys), P, int(L), _ptr(layers),
                                                    _ptr(layer_amp), _ptr(total)))
         return layers, layer_amp, total
+
+    def read_evidence(self, bam, rec_off, keys, mbq: int = 20, mrq: int = 20, hist=None, stats=None):
+        """Read-level evidence of a batch of alignment records (ampli_pileup_evidence).  bam, rec_off, keys as indel_count takes
+        them.  Returns (hist, stats): hist int32 [P, 4, EVIDENCE_METRICS, EVIDENCE_BINS] in the order (position, nt, metric, bin) -- per
+        counted column one count in the bin of its base quality (EVIDENCE_BQ), its read's MAPQ / 4 (EVIDENCE_MQ) and its distance to the
+        nearer end of the read (EVIDENCE_POS), each clamped at 63 -- and stats int64 [2] (reads kept, columns counted).  Both are ADDED TO:
+        a given buffer accumulates, None starts a new one at zero; stats=False: not computed (NULL) and returned as None."""
+        import torch
+
+        assert _ok(bam, torch.uint8, (None,)) and _ok(rec_off, torch.int64, (None,)) and _ok(keys, torch.int64, (None,))
+        n_reads, P = int(rec_off.numel()), int(keys.numel())
+        hist = self._out(hist, torch.int32, (P, 4, EVIDENCE_METRICS, EVIDENCE_BINS), zero=True)
+        stats = None if stats is False else self._out(stats, torch.int64, (2,), zero=True)
+        self._check(self.lib.ampli_pileup_evidence(self.h, _ptr(bam), _ptr(rec_off), n_reads, _ptr(keys), P, int(mbq), int(mrq), _ptr(hist), _ptr(stats)))
+        return hist, stats
+
+    def evidence_score(self, hist, ref_nt, alt_nt, ints=None, med=None, z2=None, alt_used=None):
+        """The rank-sum score of alt reads against ref reads per (position, metric) of read_evidence's histograms (ampli_evidence_score,
+        DESIGN 29).  ref_nt, alt_nt: int8 [P], 0 .. 3 = A C G T; an alt of -1 takes the non-reference nt with the most reads.  Returns
+        (ints, med, z2, alt_used): ints int64 [P, 3, 3] (n_ref, n_alt, u2; u2 = -1: untested), med int32 [P, 3, 2] (median bin of the ref
+        and of the alt reads, -1 without reads), z2 float64 [P, 3] (the signed squared normal score, < 0: alt ranks below ref) and alt_used
+        int8 [P].  All four are overwritten."""
+        import torch
+
+        P = int(hist.shape[0])
+        assert _ok(hist, torch.int32, (P, 4, EVIDENCE_METRICS, EVIDENCE_BINS)) and _ok(ref_nt, torch.int8, (P,)) and _ok(alt_nt, torch.int8, (P,))
+        ints = self._out(ints, torch.int64, (P, EVIDENCE_METRICS, 3))
+        med = self._out(med, torch.int32, (P, EVIDENCE_METRICS, 2))
+        z2 = self._out(z2, torch.float64, (P, EVIDENCE_METRICS))
+        alt_used = self._out(alt_used, torch.int8, (P,))
+        self._check(self.lib.ampli_evidence_score(self.h, _ptr(hist), P, _ptr(ref_nt), _ptr(alt_nt), _ptr(ints), _ptr(med), _ptr(z2), _ptr(alt_used)))
+        return ints, med, z2, alt_used
 
     def hetsite_reference(self, rec: Records, P: int, planes, min_depth: int = 100, ref=None):
         """One resident chunk of normals into the het-site reference (ampli_hetsite_reference_records): ref int64 [3, 6, P]

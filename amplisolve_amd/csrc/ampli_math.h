@@ -1880,4 +1880,74 @@ AMPLI_FN int ampli_tf_change(int verdict_a, const double *a, int verdict_b, cons
     return AMPLI_TF_STABLE;
 }
 
+// ------------------------------------------------------------------------------------------------------------------------------------
+// Read-level evidence (the definition is the contract comment of ampli_evidence_score, restated in tests/evidence_model.py): do
+// the reads that carry the alt allele at a position rank below the reads that carry the ref allele, in base quality, MAPQ or distance to
+// the read's end.  One cell per (position, metric) over two 64-bin histograms a (alt) and r (ref); a side without a usable nt is NULL and
+// reads as zeros.
+//   n1 = sum a, n2 = sum r, N = n1 + n2, t_b = a_b + r_b.  Medians: the smallest b with 2 cum_b >= n, -1 for n = 0.
+//   U2 = sum_b a_b (2 R_<b + r_b): twice the Mann-Whitney U of alt over ref, ties counted half.  D = U2 - n1 n2.
+//   Td = sum_b ascending (t t t - t), Nd = N, c = (Nd + 1) - Td / (Nd (Nd - 1)), v = n1 n2 c, z2 = 3 D D / v, negated for D < 0: every
+//   operation one IEEE operation in this order (the build contracts nothing), so device, host and the numpy model agree bit for bit.
+//   Untested (u2 = -1, z2 = 0; counts and medians still written): n1 = 0, n2 = 0, N >= 2^30 (keeps U2 < 2^63), !(v > 0).
+// ------------------------------------------------------------------------------------------------------------------------------------
+// the alt nt a position is scored with, or -1: `alt` itself when it is 0 .. 3 and not `ref`; for alt == -1 ("choose") the nt other than
+// ref with the largest total over the BQ bins, ties to the lowest index; -1 for a ref outside 0 .. 3 and for any other alt
+AMPLI_FN int ampli_ev_alt(const int32_t *hist /* [4][METRICS][BINS] of one position */, int ref, int alt)
+{
+    if (ref < 0 || ref > 3) return -1;
+    if (alt != -1) return (alt < 0 || alt > 3 || alt == ref) ? -1 : alt;
+    int best = -1;
+    int64_t best_n = 0;
+    for (int nt = 0; nt < 4; ++nt) {
+        if (nt == ref) continue;
+        const int32_t *h = hist + (nt * AMPLI_EVIDENCE_METRICS + AMPLI_EVIDENCE_BQ) * AMPLI_EVIDENCE_BINS;
+        int64_t n = 0;
+        for (int b = 0; b < AMPLI_EVIDENCE_BINS; ++b) n += h[b];
+        if (best < 0 || n > best_n) { best = nt; best_n = n; }
+    }
+    return best;
+}
+
+// one cell: o_int = {n_ref, n_alt, u2}, o_med = {med_ref, med_alt}, *o_z2 the signed squared score
+AMPLI_FN void ampli_ev_cell(const int32_t *a, const int32_t *r, int64_t *o_int, int32_t *o_med, double *o_z2)
+{
+    int64_t n1 = 0, n2 = 0;
+    for (int b = 0; b < AMPLI_EVIDENCE_BINS; ++b) {
+        n1 += a ? a[b] : 0;
+        n2 += r ? r[b] : 0;
+    }
+    const int64_t N = n1 + n2;
+    int64_t c1 = 0, c2 = 0; // alt and ref reads in the bins up to b; c2 before its update is R_<b
+    int32_t m1 = -1, m2 = -1;
+    uint64_t u2 = 0; // wraps only where the cell is untested (N >= 2^30)
+    double Td = 0.0;
+    for (int b = 0; b < AMPLI_EVIDENCE_BINS; ++b) {
+        const int64_t ab = a ? a[b] : 0, rb = r ? r[b] : 0;
+        u2 += (uint64_t)ab * (uint64_t)(2 * c2 + rb);
+        c1 += ab;
+        c2 += rb;
+        if (m1 < 0 && n1 > 0 && 2 * c1 >= n1) m1 = b;
+        if (m2 < 0 && n2 > 0 && 2 * c2 >= n2) m2 = b;
+        const double t = (double)(ab + rb);
+        const double t3 = t * t * t;
+        Td = Td + (t3 - t);
+    }
+    o_int[0] = n2;
+    o_int[1] = n1;
+    o_int[2] = -1;
+    o_med[0] = m2;
+    o_med[1] = m1;
+    *o_z2 = 0.0;
+    if (n1 <= 0 || n2 <= 0 || N >= (1ll << 30)) return;
+    const double Nd = (double)N;
+    const double c = (Nd + 1.0) - Td / (Nd * (Nd - 1.0));
+    const double v = (double)n1 * (double)n2 * c;
+    if (!(v > 0.0)) return;
+    const int64_t D = (int64_t)u2 - n1 * n2;
+    const double z2 = 3.0 * (double)D * (double)D / v;
+    o_int[2] = (int64_t)u2;
+    *o_z2 = D < 0 ? -z2 : z2;
+}
+
 #endif

@@ -22,7 +22,7 @@
     X(monitor_sums_records) X(monitor_control_records) X(monitor_score)                                                           \
     X(hetsite_reference_records) X(allelic_site_records) X(allelic_region_sums) X(fraction_records)                               \
     X(event_create) X(event_destroy) X(event_record) X(event_sync) X(pileup_count) X(pileup_indel_count) X(comm_create)           \
-    X(comm_destroy) X(pileup_amplicon_count) X(amplicon_layers)                                                                   \
+    X(comm_destroy) X(pileup_amplicon_count) X(amplicon_layers) X(pileup_evidence) X(evidence_score)                              \
     X(comm_reduce_scatter_f64) X(comm_all_to_all_f32) X(comm_all_gather_bytes) X(comm_all_reduce_max_i32)                         \
     X(comm_exclusive_sum_i64) X(comm_barrier)
 

@@ -258,6 +258,29 @@ struct AmpliconListed { // one listed position: what the ASEQ line prints, and i
 // returns the lines written to <name>.AMPLICON.PILEUP.ASEQ; every file under a temporary name, renamed into place at the end
 int64_t write_amplicon_files(const std::string &out_dir, const std::string &layers_dir, const std::string &name, const std::vector<BedRow> &rows,
                              const AmpliconArrays &amps, const std::vector<AmpliconListed> &listed, const AmpliconCounts &c, int mdc);
+// ---- run_re.cpp ----
+// computeReadEvidence: one BAM file and a list of calls -> <out_dir>/<name>.EVIDENCE.txt + <name>.EVIDENCE.HIST.txt.  The numbers
+// as the command line gives them.
+struct ReArgs {
+    std::string vcf, bam, out_dir;
+    std::string threads = "4", mbq = "20", mrq = "20", min_alt = "4", z_min = "3";
+    int64_t *stats = nullptr; // optional [4]: records, reads kept, columns counted, lines written
+    std::string *error = nullptr;
+};
+int run_compute_read_evidence(const ReArgs &a);
+// the nt code of a listed allele: 0 .. 3 for one of A C G T (either case), -1 for "." where `choose` allows it, -2 for anything else
+int evidence_nt(const std::string &allele, bool choose);
+// the score of ampli_evidence_score on the host (ampli_ev_* of csrc/ampli_math.h): the same planes, the same bits
+void evidence_score_host(const int32_t *hist, int64_t P, const int8_t *ref_nt, const int8_t *alt_nt, int64_t *o_int, int32_t *o_med, double *o_z2, int8_t *alt_used);
+// one listed line with the planes of its position, and the writer of the command's two files from host arrays alone (no device:
+// tools/evidence_sanitize.cpp); returns the lines written to <name>.EVIDENCE.txt; both files under temporary names, renamed at the end
+struct EvidenceListed {
+    std::string chrom, ref, alt;
+    int64_t pos = 0;
+};
+int64_t write_evidence_files(const std::string &out_dir, const std::string &name, const std::vector<EvidenceListed> &listed, const int32_t *hist /* [L][4][3][64] */,
+                             const int64_t *v_int /* [L][3][3] */, const int32_t *v_med /* [L][3][2] */, const double *v_z2 /* [L][3] */,
+                             const int8_t *ref_nt, const int8_t *alt_used /* [L] */, int64_t min_alt, double z_min);
 // BGZF + BAM structure only (no GPU): stats[4] = alignment records, uncompressed bytes, references, malformed records
 void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // ---- pipeline.cpp ----

@@ -267,6 +267,32 @@ extern "C" int ampli_host_compute_amplicon_counts(const char *vcf, const char *b
     return rc;
 }
 
+extern "C" int ampli_host_compute_read_evidence(const char *vcf, const char *bam, const char *out_dir, int32_t threads, int32_t mbq, int32_t mrq,
+                                               int32_t min_alt, double z_min, int64_t *stats)
+{
+    if (!vcf || !bam || !out_dir) { g_err = "vcf, bam and out_dir are required"; return AMPLI_E_INVALID; }
+    ReArgs a;
+    a.vcf = vcf; a.bam = bam; a.out_dir = out_dir;
+    a.threads = std::to_string(threads); a.mbq = std::to_string(mbq); a.mrq = std::to_string(mrq); a.min_alt = std::to_string(min_alt);
+    char z[40];
+    snprintf(z, sizeof z, "%.17g", z_min);
+    a.z_min = z;
+    a.stats = stats;
+    std::string err;
+    a.error = &err;
+    const int rc = run_compute_read_evidence(a);
+    if (rc) g_err = err;
+    return rc;
+}
+
+extern "C" int ampli_host_evidence_score(const int32_t *hist, int64_t P, const int8_t *ref_nt, const int8_t *alt_nt, int64_t *out_int, int32_t *out_med,
+                                         double *out_z2, int8_t *alt_used)
+{
+    if (!hist || P < 0 || !ref_nt || !alt_nt || !out_int || !out_med || !out_z2 || !alt_used) { g_err = "bad argument"; return AMPLI_E_INVALID; }
+    evidence_score_host(hist, P, ref_nt, alt_nt, out_int, out_med, out_z2, alt_used);
+    return 0;
+}
+
 extern "C" int64_t ampli_host_amplicon_arrays(const char *bed, const char *ref_names, int64_t cap, uint64_t *lo, uint64_t *hi, uint64_t *reach, int64_t *amp_off,
                                               int32_t *row_of, int64_t *n_rows)
 {

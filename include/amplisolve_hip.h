@@ -178,6 +178,12 @@ extern "C" {
  *   (C30) amplicon layers: ampli_amplicon_layers FULLY OVERWRITES d_layers [L][P][8], d_layer_amp [L][P] and d_total [P][8] with plain
  *        stores (one lane owns the cells of a position: nothing is cleared, nothing is added to), positions under no amplicon included
  *        (absent-record markers, -1 and zeros).  Nothing else is written.  d_counts is read only at walk entries below W.
+ *   (C31) read-level evidence (tests/test_gpu_evidence_contracts.py): ampli_pileup_evidence ADDS TO d_hist inside [0, P) positions and,
+ *        when it is not NULL, to the two words of d_stats (zero them for the counts of one call; batches of one file add up).  Nothing
+ *        else is written.
+ *   (C32) evidence scores: ampli_evidence_score FULLY OVERWRITES d_int [P][3][3], d_med [P][3][2], d_z2 [P][3] and d_alt_used [P] with
+ *        plain stores (one lane owns a cell: nothing is cleared, nothing is added to), untested cells included.  Nothing else is written,
+ *        d_hist, d_ref_nt and d_alt_nt included.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -1293,6 +1299,53 @@ int ampli_pileup_amplicon_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint
 int ampli_amplicon_layers(ampli_ctx *ctx, const int32_t *d_counts, const uint64_t *d_lo, const uint64_t *d_hi, const uint64_t *d_reach,
                           const int64_t *d_amp_off, int64_t A, int64_t W, const uint64_t *d_keys, int64_t P, int32_t L, int32_t *d_layers,
                           int32_t *d_layer_amp, int32_t *d_total);
+
+/*
+ * Read-level evidence over the same alignment records: what the reads behind a count looked like.  The stream contract is
+ * ampli_pileup_count's (d_bam, d_rec_off, d_keys; this kernel reads the records straight from global memory and needs neither ascending
+ * offsets nor the 16 bytes behind).
+ *
+ * Counted column.  A counted column is exactly a column that ampli_pileup_count adds to counts[p][nt]: the read is kept (placed, none of
+ * the flags 0x4 / 0x100 / 0x200 / 0x400, MAPQ >= mrq); it is an M / = / X column whose reference position is the panel key d_keys[p]; its
+ * base is A/C/G/T; its quality is >= mbq.  The effective operations are those of ampli_pileup_indel_count: zero-length operations and P
+ * are dropped.
+ * Bins.  Every counted column adds 1 to three bins of d_hist, int32 [P][4][AMPLI_EVIDENCE_METRICS][AMPLI_EVIDENCE_BINS] in the order
+ * (position, nt, metric, bin).  Strands are pooled.  d_hist is ACCUMULATED into.
+ *   AMPLI_EVIDENCE_BQ   bin min(q, 63), q the column's quality byte
+ *   AMPLI_EVIDENCE_MQ   bin min(mapq >> 2, 63)
+ *   AMPLI_EVIDENCE_POS  bin min(d, 63) with d = min(i, l_seq - 1 - i), i the column's 0-based index into the record's SEQ: soft-clipped
+ *                       and inserted bases in front of the column count towards i, hard clips and deletions do not
+ * Invariant.  For every position, nt and metric the sum over the 64 bins equals counts[p][nt] of ampli_pileup_count over the same records,
+ * mbq and mrq.
+ * d_stats (optional, may be NULL) uint64 [2], accumulated: reads kept, columns counted.  Bad arguments give AMPLI_E_INVALID ("bad
+ * argument"), more than 2^31 - 1 read groups AMPLI_E_RANGE.  n_reads == 0 or P == 0 is a no-op that returns AMPLI_OK.
+ * Stated limits.  MAPQ is seen only at or above mrq and qualities only at or above mbq (that is what makes the invariant hold); strands
+ * are pooled; POS is the distance to the nearer end of the stored sequence, not to the primer.
+ */
+int ampli_pileup_evidence(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *d_rec_off, int64_t n_reads, const uint64_t *d_keys, int64_t P,
+                          int32_t mbq, int32_t mrq, int32_t *d_hist, uint64_t *d_stats);
+/*
+ * The rank-sum score of alt reads against ref reads, one cell per (position, metric) of d_hist.  d_ref_nt, d_alt_nt: int8 [P].
+ * An alt of -1 means "choose": the non-reference nt with the largest total count (over its BQ bins), ties to the lowest index.  A ref
+ * outside 0 .. 3 leaves the position's cells untested, and so does an alt outside -1 .. 3 or equal to ref; a side without a usable nt reads
+ * as an empty histogram.
+ * With a_b and r_b the alt and ref histograms of the metric, n1 = sum a_b, n2 = sum r_b, N = n1 + n2, t_b = a_b + r_b:
+ *   1. U2 = sum_b a_b (2 R_<b + r_b) with R_<b = sum_{c<b} r_c, int64: twice the Mann-Whitney U of alt over ref, ties counted half.
+ *   2. D = U2 - n1 n2, int64.
+ *   3. Medians: the smallest b with 2 cum_b >= n, per side; -1 when n = 0.
+ *   4. In doubles, nothing contracted: Td = sum_b ascending ((double)t_b x (double)t_b x (double)t_b - (double)t_b), Nd = (double)N,
+ *      c = (Nd + 1.0) - Td / (Nd x (Nd - 1.0)), v = (double)n1 x (double)n2 x c.
+ *   5. z2 = 3.0 x (double)D x (double)D / v, negated when D < 0: the signed square of the tie-corrected normal score without continuity
+ *      correction.  A negative value means the alt reads rank below the ref reads.
+ * Every operation is one IEEE + - x / in this order; no sqrt, erfc or log runs on the device.
+ * Untested cells: n1 = 0, n2 = 0, N >= 2^30 (keeps U2 < 2^63) or !(v > 0) (all reads in one bin).  Such a cell gets u2 = -1 and z2 = 0; its
+ * counts and medians are still written.
+ * Outputs, every cell with one owner and overwritten: d_int int64 [P][3][3] = n_ref, n_alt, u2; d_med int32 [P][3][2] = med_ref, med_alt;
+ * d_z2 double [P][3]; d_alt_used int8 [P], the alt nt that was used, or -1.  A null pointer or P < 0 gives AMPLI_E_INVALID ("bad
+ * argument"), P == 0 is a no-op.  The score is a normal approximation: report it only from a few reads a side (computeReadEvidence: min_alt).
+ */
+int ampli_evidence_score(ampli_ctx *ctx, const int32_t *d_hist, int64_t P, const int8_t *d_ref_nt, const int8_t *d_alt_nt, int64_t *d_int,
+                         int32_t *d_med, double *d_z2, int8_t *d_alt_used);
 
 /* tuning knobs.  reduce_sample_splits: 0 = automatic.  reduce_general: 0 = the fast error_reduce kernel
  * (valid while every strand depth is < 2^22; it raises AMPLI_FLAG_RERUN_GENERAL otherwise), 1 = the literal

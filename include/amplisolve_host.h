@@ -176,6 +176,19 @@ int ampli_host_compute_amplicon_counts(const char *vcf, const char *bam, const c
  * rows of the file.  Returns A >= 0, or a negative code: AMPLI_E_RANGE when A > cap or W >= 2^31, AMPLI_E_INVALID for a bad argument or file. */
 int64_t ampli_host_amplicon_arrays(const char *bed, const char *ref_names, int64_t cap, uint64_t *lo, uint64_t *hi, uint64_t *reach, int64_t *amp_off,
                                    int32_t *row_of, int64_t *n_rows);
+/* computeReadEvidence: the same walk with ampli_pileup_evidence per batch and one ampli_evidence_score over the listed lines ->
+ * <out_dir>/<bam name>.EVIDENCE.txt (chr pos ref alt n_ref n_alt, per metric med_ref med_alt z, the verdict) and <out_dir>/<bam name>
+ * .EVIDENCE.HIST.txt.  vcf: the calls (chr pos id ref alt; an alt of . takes the non-reference base with the most reads).  min_alt >= 1: the
+ * reads either allele needs for a verdict; z_min > 0: the score from which a metric is flagged.  Bad numbers and unreadable inputs are refused
+ * before the device is opened; a failure leaves no output file behind.  stats (optional) [4]: alignment records, reads kept, columns counted,
+ * lines written. */
+int ampli_host_compute_read_evidence(const char *vcf, const char *bam, const char *out_dir, int32_t threads, int32_t mbq, int32_t mrq, int32_t min_alt,
+                                     double z_min, int64_t *stats);
+/* ampli_evidence_score on the host (no GPU): the same planes -- hist int32 [P][4][3][64], ref_nt and alt_nt int8 [P] -- through the same
+ * arithmetic (ampli_ev_* of csrc/ampli_math.h), so out_int [P][3][3], out_med [P][3][2], out_z2 [P][3] and alt_used [P] equal the device's bit
+ * for bit.  Returns 0, or AMPLI_E_INVALID for a null pointer or P < 0. */
+int ampli_host_evidence_score(const int32_t *hist, int64_t P, const int8_t *ref_nt, const int8_t *alt_nt, int64_t *out_int, int32_t *out_med,
+                              double *out_z2, int8_t *alt_used);
 /* the container only (no GPU): stats[4] = alignment records, uncompressed bytes, reference sequences, malformed records (complete
  * records whose CIGAR does not add up to their l_seq or whose fields overrun their block: counted and skipped).  Bytes behind the
  * last complete record -- a truncated or desynchronised stream -- are an error (AMPLI_E_INVALID), not a count: since round 3 the call

@@ -221,4 +221,13 @@ typedef struct ampli_fraction_params {
  * insertion, kind 1 = deletion; an event of length L falls into bin min(L, AMPLI_INDEL_LEN_BINS) - 1, so the last bin holds L >= 32. */
 #define AMPLI_INDEL_LEN_BINS 32
 
+/* Read-level evidence from alignments: ampli_pileup_evidence's histograms are int32 [P][4][AMPLI_EVIDENCE_METRICS]
+ * [AMPLI_EVIDENCE_BINS] in the order (position, nt, metric, bin); the metrics are the base quality of the counted column, the MAPQ of its
+ * read (in steps of 4) and the column's distance to the nearer end of the stored sequence, each clamped into the last bin. */
+#define AMPLI_EVIDENCE_METRICS 3
+#define AMPLI_EVIDENCE_BINS 64
+#define AMPLI_EVIDENCE_BQ 0
+#define AMPLI_EVIDENCE_MQ 1
+#define AMPLI_EVIDENCE_POS 2
+
 #endif /* AMPLISOLVE_TYPES_H */
