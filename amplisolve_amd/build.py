@@ -30,7 +30,7 @@ HOST_LIB = os.path.join(LIB, "libamplisolve_host.so")
 HIP_SOURCES = ["ampli_kernels.hip", "ampli_exchange.hip", "ampli_loo.hip", "ampli_limits.hip", "ampli_dispersion.hip", "ampli_concordance.hip", "ampli_contamination.hip",
                "ampli_amplicon.hip", "ampli_spectrum.hip", "ampli_exceedance.hip", "ampli_overdispersion.hip", "ampli_paired.hip", "ampli_fdr.hip", "ampli_dilution.hip", "ampli_monitor.hip", "ampli_allelic.hip", "ampli_fraction.hip", "ampli_aux.hip",
                "ampli_runtime.hip", "ampli_pileup.hip", "ampli_indel.hip", "ampli_amplicon_count.hip", "ampli_evidence.hip", "ampli_comm.hip"]
-HIP_HEADERS = ["ampli_device.h", "ampli_internal.h", "ampli_math.h", "ampli_synth.h"]
+HIP_HEADERS = ["ampli_bam.h", "ampli_device.h", "ampli_internal.h", "ampli_math.h", "ampli_synth.h"]
 # the public headers; amplisolve_types.h is included by the other two and by csrc/ampli_math.h, so both libraries depend on it
 INCLUDE = os.path.join(ROOT, "include")
 TYPES_H = os.path.join(INCLUDE, "amplisolve_types.h")

@@ -7,6 +7,7 @@
 #include <climits>
 #include <cstdint>
 
+#include "ampli_bam.h"    // the record layout, the keys and their searches
 #include "ampli_device.h" // with_bool, the launch dispatch
 #include "ampli_internal.h"
 
@@ -26,62 +27,6 @@
 constexpr int AMPCOUNT_READS = 256;
 constexpr int AMPCOUNT_WINDOW = 512;
 
-__device__ __forceinline__ unsigned ampcount_ld_u32(const unsigned char *p) // ld_u32_unaligned of ampli_pileup.hip
-{
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
-struct ampcount_read { // the header fields of a kept read, wave-uniform
-    const unsigned char *cig, *seq, *qual;
-    long long pos; // 0-based
-    int ref_id, n_cigar, rev;
-};
-
-// false: the read is not kept (unplaced, a filtered flag, MAPQ < mrq)
-__device__ __forceinline__ bool ampcount_header(const unsigned char *r, const int mrq, ampcount_read &h)
-{
-    const int ref_id = (int)ampcount_ld_u32(r), pos = (int)ampcount_ld_u32(r + 4);
-    const unsigned bin_mq_nl = ampcount_ld_u32(r + 8), flag_nc = ampcount_ld_u32(r + 12);
-    const int l_read_name = (int)(bin_mq_nl & 0xffu), mapq = (int)((bin_mq_nl >> 8) & 0xffu);
-    const unsigned flag = flag_nc >> 16;
-    if (ref_id < 0 || pos < 0 || (flag & (0x4u | 0x100u | 0x200u | 0x400u)) != 0 || mapq < mrq) return false;
-    const int l_seq = (int)ampcount_ld_u32(r + 16);
-    h.ref_id = ref_id;
-    h.pos = pos;
-    h.n_cigar = (int)(flag_nc & 0xffffu);
-    h.rev = (int)((flag >> 4) & 1u);
-    h.cig = r + 32 + l_read_name;
-    h.seq = h.cig + 4 * (size_t)h.n_cigar;
-    h.qual = h.seq + (l_seq + 1) / 2;
-    return true;
-}
-
-// first index in [0, n) with v[i] >= key (n if none)
-__device__ __forceinline__ long long ampcount_lower(const unsigned long long *__restrict__ v, const long long n, const unsigned long long key)
-{
-    long long a = 0, b = n;
-    while (a < b) {
-        const long long mid = (a + b) >> 1;
-        if (v[mid] < key) a = mid + 1;
-        else b = mid;
-    }
-    return a;
-}
-
-// first index in [0, n) with v[i] > key (n if none)
-__device__ __forceinline__ long long ampcount_upper(const unsigned long long *__restrict__ v, const long long n, const unsigned long long key)
-{
-    long long a = 0, b = n;
-    while (a < b) {
-        const long long mid = (a + b) >> 1;
-        if (v[mid] <= key) a = mid + 1;
-        else b = mid;
-    }
-    return a;
-}
-
 struct ampcount_hit { // the amplicon a read is assigned to: its sorted index, its interval and its first walk entry
     long long a, first, last, off;
 };
@@ -89,20 +34,22 @@ struct ampcount_hit { // the amplicon a read is assigned to: its sorted index, i
 // The amplicon of a kept read; false: none (R = 0, no overlap, or an overlap under the threshold).  Wave-uniform, every lane returns the
 // same.  c0, c1: the candidate range of the wave's previous read, tried first -- the reads of an amplicon follow each other, and four
 // independent loads say whether the range still holds, where the two searches are eighteen dependent ones.  Start with c0 = -1.
-__device__ __forceinline__ bool ampcount_assign(const ampcount_read &h, const int lane, const unsigned long long *__restrict__ lo,
+__device__ __forceinline__ bool ampcount_assign(const BamRead &h, const int lane, const unsigned long long *__restrict__ lo,
                                                 const unsigned long long *__restrict__ hi, const unsigned long long *__restrict__ reach,
                                                 const long long *__restrict__ amp_off, const long long A, const int min_overlap, long long &c0,
                                                 long long &c1, ampcount_hit &hit)
 {
     long long R = 0; // reference positions the alignment spans: M = X D N
     for (int c = 0; c < h.n_cigar; ++c) {
-        const unsigned op_len = ampcount_ld_u32(h.cig + 4 * (size_t)c);
+        // bam_cigar and bam_op_match || bam_op_ref of ampli_bam.h, written out: with the helpers this loop -- a chain of dependent loads in
+        // front of every read's assignment -- made the kernel 1.3 % slower (profiles/bam_walks)
+        const unsigned op_len = bam_u32()(h.cig + 4 * (size_t)c);
         const unsigned op = op_len & 15u;
         if (op == 0 || op == 2 || op == 3 || op == 7 || op == 8) R += (long long)(op_len >> 4);
     }
     if (R == 0) return false;
     const long long sf = h.pos + 1, sl = h.pos + R; // 1-based, inclusive
-    const unsigned long long ref_hi = (unsigned long long)(unsigned)h.ref_id << 32;
+    const unsigned long long ref_hi = bam_key(h.ref_id, 0);
     // (a span that runs past 2^32 - 1 is searched with its end at 2^32 - 1: no amplicon starts behind that)
     const unsigned long long kf = ref_hi | (unsigned long long)sf, kl = ref_hi | (unsigned long long)(sl < 0xffffffffll ? sl : 0xffffffffll);
     // c0: the first a with reach[a] >= span_first (A if none); c1: the last a with lo[a] <= span_last (-1 if none)
@@ -113,8 +60,8 @@ __device__ __forceinline__ bool ampcount_assign(const ampcount_read &h, const in
         ok0 = (c0 == A || r0 >= kf) && (c0 == 0 || r0m < kf);
         ok1 = (c1 < 0 || l1 <= kl) && (c1 + 1 == A || l1p > kl);
     }
-    if (!ok0) c0 = ampcount_lower(reach, A, kf);
-    if (!ok1) c1 = ampcount_upper(lo, A, kl) - 1;
+    if (!ok0) c0 = bam_lower<long long>(reach, 0, A, kf);
+    if (!ok1) c1 = bam_upper<long long>(lo, 0, A, kl) - 1;
     // the key: largest overlap, then smallest anchor distance, then lowest index
     long long b_ov = -1, b_an = 0, b_a = -1, b_first = 0, b_last = 0, b_off = 0;
     for (long long a0 = c0; a0 <= c1; a0 += 64) {
@@ -180,8 +127,8 @@ __global__ __launch_bounds__(256) void amplicon_count_kernel(const unsigned char
     if (wave == 0) { // the window starts at the walk entry the workgroup's first assigned read begins in
         long long wb = 0;
         for (long long rd = first; rd < end; ++rd) {
-            ampcount_read h;
-            if (!ampcount_header(bam + rec_off[rd] + 4, mrq, h)) continue;
+            BamRead h;
+            if (!bam_read_header<bam_u32>(bam + rec_off[rd] + 4, mrq, h)) continue;
             ampcount_hit hit;
             if (!ampcount_assign(h, lane, lo, hi, reach, amp_off, A, min_overlap, c0, c1, hit)) continue;
             wb = hit.off + (h.pos + 1 > hit.first ? h.pos + 1 - hit.first : 0);
@@ -196,8 +143,8 @@ __global__ __launch_bounds__(256) void amplicon_count_kernel(const unsigned char
     int run_rev = 0;
     unsigned long long run_n = 0;
     for (long long read = first + wave; read < end; read += 4) {
-        ampcount_read h;
-        if (!ampcount_header(bam + rec_off[read] + 4, mrq, h)) continue;
+        BamRead h;
+        if (!bam_read_header<bam_u32>(bam + rec_off[read] + 4, mrq, h)) continue;
         ++kept;
         ampcount_hit hit;
         if (!ampcount_assign(h, lane, lo, hi, reach, amp_off, A, min_overlap, c0, c1, hit)) continue; // off-target: in the statistics and nowhere else
@@ -215,19 +162,16 @@ __global__ __launch_bounds__(256) void amplicon_count_kernel(const unsigned char
         long long refpos = h.pos + 1;            // 1-based position of the next column
         long long qpos = 0;
         for (int c = 0; c < h.n_cigar; ++c) {
-            const unsigned op_len = ampcount_ld_u32(h.cig + 4 * (size_t)c);
-            const unsigned op = op_len & 15u;
-            const long long len = (long long)(op_len >> 4);
-            if (op == 0 || op == 7 || op == 8) { // a match run: M, =, X; its columns refpos .. refpos + len - 1, those inside [af, al] are counted
+            const BamOp o = bam_cigar<bam_u32>(h.cig, c);
+            const long long len = o.len;
+            if (bam_op_match(o.op)) { // a match run: M, =, X; its columns refpos .. refpos + len - 1, those inside [af, al] are counted
                 const long long j0 = af > refpos ? af - refpos : 0;
                 const long long j1 = al - refpos + 1 < len ? al - refpos + 1 : len; // exclusive
                 const long long inside = j1 > j0 ? j1 - j0 : 0;
                 clipped += (unsigned long long)(len - inside);
                 for (long long j = j0 + lane; j < j1; j += 64) {
                     const long long q = qpos + j;
-                    const unsigned byte = h.seq[q >> 1];
-                    const unsigned nib = (q & 1) ? (byte & 15u) : (byte >> 4);
-                    const int nt = nib == 1 ? 0 : nib == 2 ? 1 : nib == 4 ? 2 : nib == 8 ? 3 : -1;
+                    const int nt = bam_nt(h.seq, q);
                     if (nt < 0 || (int)h.qual[q] < mbq) continue;
                     const long long w = cell0 + refpos + j; // in [amp_off[a], amp_off[a + 1]): j0 <= j < j1
                     const long long rel = w - wb;
@@ -242,9 +186,9 @@ __global__ __launch_bounds__(256) void amplicon_count_kernel(const unsigned char
                 }
                 refpos += len;
                 qpos += len;
-            } else if (op == 1 || op == 4) { // I, S
+            } else if (bam_op_query(o.op)) { // I, S
                 qpos += len;
-            } else if (op == 2 || op == 3) { // D, N
+            } else if (bam_op_ref(o.op)) { // D, N
                 refpos += len;
             } // H, P: neither
         }
@@ -280,7 +224,7 @@ __global__ __launch_bounds__(256) void amplicon_layers_kernel(const int *__restr
     const long long p = (long long)blockIdx.x * 256 + threadIdx.x;
     if (p >= P) return;
     const unsigned long long key = keys[p];
-    const long long c0 = ampcount_lower(reach, A, key), c1 = ampcount_upper(lo, A, key) - 1;
+    const long long c0 = bam_lower<long long>(reach, 0, A, key), c1 = bam_upper<long long>(lo, 0, A, key) - 1;
     int4 t0 = make_int4(0, 0, 0, 0), t1 = make_int4(0, 0, 0, 0);
     int l = 0;
     for (long long a = c0; a <= c1; ++a) {

@@ -6,6 +6,7 @@
 
 #include <cstdint>
 
+#include "ampli_bam.h" // the record layout, the keys and their searches
 #include "ampli_internal.h"
 #include "ampli_math.h" // ampli_ev_*: the score's arithmetic, shared with the host library
 
@@ -26,13 +27,6 @@ constexpr int EVIDENCE_READS = 256;
 constexpr int EVIDENCE_WINDOW = 8;
 constexpr int EVIDENCE_CELLS = 4 * AMPLI_EVIDENCE_METRICS * AMPLI_EVIDENCE_BINS; // counters of one key
 
-__device__ __forceinline__ unsigned evidence_ld_u32(const unsigned char *p) // ld_u32_unaligned of ampli_pileup.hip
-{
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void evidence_count_kernel(const unsigned char *__restrict__ bam, const unsigned long long *__restrict__ rec_off,
                                                              const long long n_reads, const unsigned long long *__restrict__ keys, const long long P,
                                                              const int mbq, const int mrq, int *__restrict__ hist, unsigned long long *__restrict__ stats)
@@ -44,6 +38,7 @@ __global__ __launch_bounds__(256) void evidence_count_kernel(const unsigned char
     __shared__ unsigned long long win_k0; // the key of the start of the workgroup's first placed read: win_base is its lower bound
     __shared__ unsigned long long s_stats[2];
     const long long first = (long long)blockIdx.x * EVIDENCE_READS;
+    const long long end = first + EVIDENCE_READS < n_reads ? first + EVIDENCE_READS : n_reads;
     {
         int4 *w4 = (int4 *)win;
         for (int i = threadIdx.x; i < EVIDENCE_WINDOW * EVIDENCE_CELLS / 4; i += 256) w4[i] = make_int4(0, 0, 0, 0);
@@ -51,24 +46,8 @@ __global__ __launch_bounds__(256) void evidence_count_kernel(const unsigned char
     if (threadIdx.x < EVIDENCE_WINDOW) touched[threadIdx.x] = 0;
     if (threadIdx.x == 0) {
         s_stats[0] = s_stats[1] = 0;
-        long long wb = 0;
-        unsigned long long wk0 = ~0ull;
-        for (long long rd = first; rd < n_reads && rd < first + EVIDENCE_READS; ++rd) {
-            const unsigned char *r = bam + rec_off[rd] + 4;
-            const int ref_id = (int)evidence_ld_u32(r), pos = (int)evidence_ld_u32(r + 4);
-            if (ref_id < 0 || pos < 0) continue;
-            const unsigned long long k0 = ((unsigned long long)(unsigned)ref_id << 32) | (unsigned long long)((long long)pos + 1);
-            long long lo = 0, hi = P;
-            while (lo < hi) {
-                const long long mid = (lo + hi) >> 1;
-                if (keys[mid] < k0) lo = mid + 1;
-                else hi = mid;
-            }
-            wb = lo;
-            wk0 = k0;
-            break;
-        }
-        win_base = wb;
+        unsigned long long wk0;
+        win_base = bam_window_base(bam, rec_off, first, end, keys, P, wk0);
         win_k0 = wk0;
     }
     __syncthreads();
@@ -80,95 +59,61 @@ __global__ __launch_bounds__(256) void evidence_count_kernel(const unsigned char
     const auto key_at = [&](long long k) { return k >= wb && k < wb + nw ? wkeys[k - wb] : keys[k]; };
     const long long read = first + threadIdx.x;
     unsigned kept = 0, added = 0;
-    if (read < n_reads) {
-        const unsigned char *r = bam + rec_off[read] + 4; // past block_size
-        const int ref_id = (int)evidence_ld_u32(r), pos = (int)evidence_ld_u32(r + 4);
-        const unsigned bin_mq_nl = evidence_ld_u32(r + 8), flag_nc = evidence_ld_u32(r + 12);
-        const int l_read_name = (int)(bin_mq_nl & 0xffu), mapq = (int)((bin_mq_nl >> 8) & 0xffu);
-        const int n_cigar = (int)(flag_nc & 0xffffu);
-        const unsigned flag = flag_nc >> 16;
-        if (!(ref_id < 0 || pos < 0 || (flag & (0x4u | 0x100u | 0x200u | 0x400u)) != 0 || mapq < mrq)) {
-            kept = 1;
-            const int l_seq = (int)evidence_ld_u32(r + 16);
-            const unsigned char *cig = r + 32 + l_read_name;
-            const unsigned char *seq = cig + 4 * (size_t)n_cigar;
-            const unsigned char *qual = seq + (l_seq + 1) / 2;
-            const unsigned rid = (unsigned)ref_id;
-            const unsigned long long ref_hi = (unsigned long long)rid << 32;
-            const int mq_bin = (mapq >> 2) < AMPLI_EVIDENCE_BINS - 1 ? (mapq >> 2) : AMPLI_EVIDENCE_BINS - 1;
-            // k: the first key not below the read's start; from here on "the first key not below the next column"
-            const unsigned long long k0 = ref_hi | (unsigned long long)((long long)pos + 1);
-            long long k;
-            if (nw > 0 && k0 >= wk0 && k0 <= wkeys[nw - 1]) { // its lower bound lies inside the window: the search stays in LDS
-                int a = 0, b = nw;
-                while (a < b) {
-                    const int mid = (a + b) >> 1;
-                    if (wkeys[mid] < k0) a = mid + 1;
-                    else b = mid;
-                }
-                k = wb + a;
-            } else {
-                long long a = 0, b = P;
-                while (a < b) {
-                    const long long mid = (a + b) >> 1;
-                    if (keys[mid] < k0) a = mid + 1;
-                    else b = mid;
-                }
-                k = a;
-            }
-            long long refpos = pos; // 0-based
-            int qpos = 0;
-            for (int c = 0; c < n_cigar && k < P; ++c) {
-                const unsigned op_len = evidence_ld_u32(cig + 4 * (size_t)c);
-                const unsigned op = op_len & 15u;
-                const int len = (int)(op_len >> 4);
-                if (op == 0 || op == 7 || op == 8) { // M, =, X: the listed keys on columns refpos + 1 .. refpos + len (1-based)
-                    for (; k < P; ++k) {
-                        const unsigned long long kk = key_at(k);
-                        const long long x = (long long)(kk & 0xffffffffull);
-                        if ((unsigned)(kk >> 32) != rid || x > refpos + len) break;
-                        const int q = qpos + (int)(x - 1 - refpos);
-                        const unsigned nib = (seq[q >> 1] >> ((~q & 1) * 4)) & 15u;
-                        const int b4 = nib == 1u ? 0 : (nib == 2u ? 1 : (nib == 4u ? 2 : (nib == 8u ? 3 : -1)));
-                        const int bq = (int)qual[q];
-                        if (b4 < 0 || bq < mbq) continue;
-                        int d = q < l_seq - 1 - q ? q : l_seq - 1 - q;
-                        d = d < 0 ? 0 : d; // (a record whose CIGAR overruns its l_seq: the host scanner drops those)
-                        const int bins[AMPLI_EVIDENCE_METRICS] = {bq < AMPLI_EVIDENCE_BINS - 1 ? bq : AMPLI_EVIDENCE_BINS - 1, mq_bin,
-                                                                  d < AMPLI_EVIDENCE_BINS - 1 ? d : AMPLI_EVIDENCE_BINS - 1};
-                        if (k >= wb && k < wb + nw) {
-                            const int w = (int)(k - wb);
-                            int *cell = win + (w * 4 + b4) * (AMPLI_EVIDENCE_METRICS * AMPLI_EVIDENCE_BINS);
-#pragma unroll
-                            for (int m = 0; m < AMPLI_EVIDENCE_METRICS; ++m) atomicAdd(&cell[m * AMPLI_EVIDENCE_BINS + bins[m]], 1);
-                            touched[w] = 1;
-                        } else {
-                            int *cell = hist + (k * 4 + b4) * (long long)(AMPLI_EVIDENCE_METRICS * AMPLI_EVIDENCE_BINS);
-#pragma unroll
-                            for (int m = 0; m < AMPLI_EVIDENCE_METRICS; ++m) atomicAdd(&cell[m * AMPLI_EVIDENCE_BINS + bins[m]], 1);
-                        }
-                        ++added;
-                    }
-                    refpos += len;
-                    qpos += len;
-                } else if (op == 1 || op == 4) { // I, S
-                    qpos += len;
-                } else if (op == 2 || op == 3) { // D, N: the keys on the positions it spans are no column of this read
-                    refpos += len;
+    BamRead h;
+    if (read < n_reads && bam_read_header<bam_u32>(bam + rec_off[read] + 4, mrq, h)) { // + 4: past block_size
+        kept = 1;
+        const unsigned rid = (unsigned)h.ref_id;
+        const unsigned long long ref_hi = bam_key(h.ref_id, 0);
+        const int mq_bin = (h.mapq >> 2) < AMPLI_EVIDENCE_BINS - 1 ? (h.mapq >> 2) : AMPLI_EVIDENCE_BINS - 1;
+        // k: the first key not below the read's start; from here on "the first key not below the next column"
+        const unsigned long long k0 = bam_key(h.ref_id, h.pos + 1);
+        long long k;
+        if (nw > 0 && k0 >= wk0 && k0 <= wkeys[nw - 1]) k = wb + bam_lower<int>(wkeys, 0, nw, k0); // its lower bound lies inside the window: LDS
+        else k = bam_lower<long long>(keys, 0, P, k0);
+        long long refpos = h.pos; // 0-based
+        int qpos = 0;
+        for (int c = 0; c < h.n_cigar && k < P; ++c) {
+            const BamOp o = bam_cigar<bam_u32>(h.cig, c);
+            const int len = o.len;
+            if (bam_op_match(o.op)) { // M, =, X: the listed keys on columns refpos + 1 .. refpos + len (1-based)
+                for (; k < P; ++k) {
                     const unsigned long long kk = key_at(k);
-                    if ((unsigned)(kk >> 32) == rid && (long long)(kk & 0xffffffffull) <= refpos) {
-                        // first key behind the gap: (rid, refpos + 1), or the next reference's first where that leaves 32 bits
-                        const unsigned long long t = refpos + 1 <= 0xffffffffll ? (ref_hi | (unsigned long long)(refpos + 1)) : ref_hi + (1ull << 32);
-                        long long a = k + 1, b = P;
-                        while (a < b) {
-                            const long long mid = (a + b) >> 1;
-                            if (keys[mid] < t) a = mid + 1;
-                            else b = mid;
-                        }
-                        k = a;
+                    const long long x = (long long)(kk & 0xffffffffull);
+                    if ((unsigned)(kk >> 32) != rid || x > refpos + len) break;
+                    const int q = qpos + (int)(x - 1 - refpos);
+                    const int b4 = bam_nt(h.seq, q);
+                    const int bq = (int)h.qual[q];
+                    if (b4 < 0 || bq < mbq) continue;
+                    int d = q < h.l_seq - 1 - q ? q : h.l_seq - 1 - q;
+                    d = d < 0 ? 0 : d; // (a record whose CIGAR overruns its l_seq: the host scanner drops those)
+                    const int bins[AMPLI_EVIDENCE_METRICS] = {bq < AMPLI_EVIDENCE_BINS - 1 ? bq : AMPLI_EVIDENCE_BINS - 1, mq_bin,
+                                                              d < AMPLI_EVIDENCE_BINS - 1 ? d : AMPLI_EVIDENCE_BINS - 1};
+                    if (k >= wb && k < wb + nw) {
+                        const int w = (int)(k - wb);
+                        int *cell = win + (w * 4 + b4) * (AMPLI_EVIDENCE_METRICS * AMPLI_EVIDENCE_BINS);
+#pragma unroll
+                        for (int m = 0; m < AMPLI_EVIDENCE_METRICS; ++m) atomicAdd(&cell[m * AMPLI_EVIDENCE_BINS + bins[m]], 1);
+                        touched[w] = 1;
+                    } else {
+                        int *cell = hist + (k * 4 + b4) * (long long)(AMPLI_EVIDENCE_METRICS * AMPLI_EVIDENCE_BINS);
+#pragma unroll
+                        for (int m = 0; m < AMPLI_EVIDENCE_METRICS; ++m) atomicAdd(&cell[m * AMPLI_EVIDENCE_BINS + bins[m]], 1);
                     }
-                } // H, P: neither
-            }
+                    ++added;
+                }
+                refpos += len;
+                qpos += len;
+            } else if (bam_op_query(o.op)) { // I, S
+                qpos += len;
+            } else if (bam_op_ref(o.op)) { // D, N: the keys on the positions it spans are no column of this read
+                refpos += len;
+                const unsigned long long kk = key_at(k);
+                if ((unsigned)(kk >> 32) == rid && (long long)(kk & 0xffffffffull) <= refpos) {
+                    // first key behind the gap: (rid, refpos + 1), or the next reference's first where that leaves 32 bits
+                    const unsigned long long t = refpos + 1 <= 0xffffffffll ? bam_key(h.ref_id, refpos + 1) : ref_hi + (1ull << 32);
+                    k = bam_lower<long long>(keys, k + 1, P, t);
+                }
+            } // H, P: neither
         }
     }
     if (stats && (kept | added)) { // one pair of LDS atomics per thread, one pair of global atomics per workgroup

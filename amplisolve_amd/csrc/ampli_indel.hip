@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "ampli_bam.h"    // the record layout, the keys and their searches
 #include "ampli_device.h" // with_bool, the launch dispatch
 #include "ampli_internal.h"
 
@@ -24,13 +25,6 @@
 constexpr int INDEL_READS = 256;
 constexpr int INDEL_WINDOW = 1024;
 
-__device__ __forceinline__ unsigned indel_ld_u32(const unsigned char *p) // ld_u32_unaligned of ampli_pileup.hip
-{
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
-
 template <bool LENGTHS>
 __global__ __launch_bounds__(256) void indel_count_kernel(const unsigned char *__restrict__ bam, const unsigned long long *__restrict__ rec_off,
                                                           const long long n_reads, const unsigned long long *__restrict__ keys, const long long P,
@@ -42,24 +36,11 @@ __global__ __launch_bounds__(256) void indel_count_kernel(const unsigned char *_
     __shared__ long long win_base;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long first = (long long)blockIdx.x * INDEL_READS;
+    const long long end = first + INDEL_READS < n_reads ? first + INDEL_READS : n_reads;
     for (int i = threadIdx.x; i < INDEL_WINDOW * 2; i += 256) win[i] = 0;
-    if (threadIdx.x == 0) { // the window starts at the first panel position at or behind the start of the workgroup's first placed read
-        long long wb = 0;
-        for (long long rd = first; rd < n_reads && rd < first + INDEL_READS; ++rd) {
-            const unsigned char *r = bam + rec_off[rd] + 4;
-            const int ref_id = (int)indel_ld_u32(r), pos = (int)indel_ld_u32(r + 4);
-            if (ref_id < 0 || pos < 0) continue;
-            const unsigned long long k0 = ((unsigned long long)(unsigned)ref_id << 32) | (unsigned long long)((long long)pos + 1);
-            long long lo = 0, hi = P;
-            while (lo < hi) {
-                const long long mid = (lo + hi) >> 1;
-                if (keys[mid] < k0) lo = mid + 1;
-                else hi = mid;
-            }
-            wb = lo;
-            break;
-        }
-        win_base = wb;
+    if (threadIdx.x == 0) {
+        unsigned long long k0;
+        win_base = bam_window_base(bam, rec_off, first, end, keys, P, k0);
     }
     __syncthreads();
     const long long wb = win_base;
@@ -69,20 +50,22 @@ __global__ __launch_bounds__(256) void indel_count_kernel(const unsigned char *_
     unsigned long long kept = 0, added = 0;
     unsigned long long prev_k0 = ~0ull; // the reads of an amplicon start at the same place: the last run's search is usually this run's
     int prev_lo = 0;
-    for (long long read = first + wave; read < n_reads && read < first + INDEL_READS; read += 4) {
+    for (long long read = first + wave; read < end; read += 4) {
+        // bam_read_header<bam_u32> of ampli_bam.h, written out: through the helper both instantiations take 54 VGPRs instead of 52
+        // (profiles/bam_walks).  A change to the record layout there is a change here.
         const unsigned char *r = bam + rec_off[read] + 4; // past block_size
-        const int ref_id = (int)indel_ld_u32(r), pos = (int)indel_ld_u32(r + 4);
-        const unsigned bin_mq_nl = indel_ld_u32(r + 8), flag_nc = indel_ld_u32(r + 12);
+        const int ref_id = (int)bam_u32()(r), pos = (int)bam_u32()(r + 4);
+        const unsigned bin_mq_nl = bam_u32()(r + 8), flag_nc = bam_u32()(r + 12);
         const int l_read_name = (int)(bin_mq_nl & 0xffu), mapq = (int)((bin_mq_nl >> 8) & 0xffu);
         const int n_cigar = (int)(flag_nc & 0xffffu);
         const unsigned flag = flag_nc >> 16;
-        if (ref_id < 0 || pos < 0 || (flag & (0x4u | 0x100u | 0x200u | 0x400u)) != 0 || mapq < mrq) continue;
+        if (ref_id < 0 || pos < 0 || (flag & BAM_FILTERED) != 0 || mapq < mrq) continue;
         ++kept;
-        const int l_seq = (int)indel_ld_u32(r + 16);
+        const int l_seq = (int)bam_u32()(r + 16);
         const unsigned char *cig = r + 32 + l_read_name;
         const unsigned char *qual = cig + 4 * (size_t)n_cigar + (l_seq + 1) / 2;
         const int rev = (int)((flag >> 4) & 1u);
-        const unsigned long long ref_hi = (unsigned long long)(unsigned)ref_id << 32;
+        const unsigned long long ref_hi = bam_key(ref_id, 0);
         long long refpos = pos; // 0-based
         int qpos = 0;
         // the state: "the previous effective operation was a match run, ending at column run_end (1-based) with query index run_q", and
@@ -91,34 +74,24 @@ __global__ __launch_bounds__(256) void indel_count_kernel(const unsigned char *_
         long long run_end = 0;
         int run_q = 0, pend = 0, pend_len = 0;
         for (int c = 0; c < n_cigar; ++c) {
-            const unsigned op_len = indel_ld_u32(cig + 4 * (size_t)c);
-            const unsigned op = op_len & 15u;
-            const int len = (int)(op_len >> 4);
+            const BamOp o = bam_cigar<bam_u32>(cig, c);
+            const unsigned op = o.op;
+            const int len = o.len;
             if (len == 0 || op == 6) continue; // not an effective operation: zero length, or P
-            if (op == 0 || op == 7 || op == 8) { // a match run: M, =, X
+            if (bam_op_match(op)) { // a match run: M, =, X
                 // it first settles what is pending: the pending event at its anchor, or a reference junction between two adjacent runs
                 if (run && lane == 0 && (int)qual[run_q] >= mbq) {
                     const unsigned long long key = ref_hi | (unsigned long long)run_end;
                     const bool inwin = pend == 0 && nw > 0 && key >= wkeys[0] && key <= wkeys[nw - 1];
                     if (inwin) {
-                        int a = 0, b = nw;
-                        while (a < b) {
-                            const int mid = (a + b) >> 1;
-                            if (wkeys[mid] < key) a = mid + 1;
-                            else b = mid;
-                        }
+                        const int a = bam_lower<int>(wkeys, 0, nw, key);
                         if (wkeys[a] == key) { // (a < nw: key <= wkeys[nw - 1])
                             atomicAdd(&win[a * 2], 1);
                             if (rev) atomicAdd(&win[a * 2 + 1], 1);
                             ++added;
                         }
                     } else {
-                        long long a = 0, b = P;
-                        while (a < b) {
-                            const long long mid = (a + b) >> 1;
-                            if (keys[mid] < key) a = mid + 1;
-                            else b = mid;
-                        }
+                        const long long a = bam_lower<long long>(keys, 0, P, key);
                         if (a < P && keys[a] == key) {
                             atomicAdd(&counts[a * 8 + pend], 1);
                             if (rev) atomicAdd(&counts[a * 8 + 4 + pend], 1);
@@ -136,34 +109,15 @@ __global__ __launch_bounds__(256) void indel_count_kernel(const unsigned char *_
                 // the anchors lie inside the window's key range: everything below happens in LDS
                 const bool inwin = n > 0 && nw > 0 && k0 >= wkeys[0] && k0 + (unsigned long long)n - 1 <= wkeys[nw - 1];
                 if (inwin) {
-                    int lo;
-                    if (k0 == prev_k0) {
-                        lo = prev_lo;
-                    } else { // first window key >= k0 (wave-uniform)
-                        int l = 0, h = nw;
-                        while (l < h) {
-                            const int mid = (l + h) >> 1;
-                            if (wkeys[mid] < k0) l = mid + 1;
-                            else h = mid;
-                        }
-                        lo = l;
+                    if (k0 != prev_k0) { // first window key >= k0 (wave-uniform)
+                        prev_lo = bam_lower<int>(wkeys, 0, nw, k0);
                         prev_k0 = k0;
-                        prev_lo = l;
                     }
+                    const int lo = prev_lo;
                     const int wend = lo + n < nw ? lo + n : nw; // the keys of these anchors are among the next `n`
                     for (int j = lane; j < n; j += 64) {
-                        const unsigned long long key = k0 + (unsigned long long)j;
-                        int a = lo + j < wend ? lo + j : wend - 1; // no gap in the panel along this run: the key sits at lo + j
-                        if (wkeys[a] != key) {
-                            int b = wend;
-                            a = lo;
-                            while (a < b) {
-                                const int mid = (a + b) >> 1;
-                                if (wkeys[mid] < key) a = mid + 1;
-                                else b = mid;
-                            }
-                        }
-                        if (a < wend && wkeys[a] == key && (int)qual[qpos + j] >= mbq) {
+                        const int a = bam_window_find(wkeys, lo, wend, j, k0 + (unsigned long long)j);
+                        if (a >= 0 && (int)qual[qpos + j] >= mbq) {
                             atomicAdd(&win[a * 2], 1);
                             if (rev) atomicAdd(&win[a * 2 + 1], 1);
                             ++added;
@@ -171,22 +125,12 @@ __global__ __launch_bounds__(256) void indel_count_kernel(const unsigned char *_
                     }
                 } else if (n > 0) {
                     // outside the window (unsorted file, a run that leaves the window, a position before it): global search and counters
-                    long long lo = 0, hi = P;
-                    while (lo < hi) {
-                        const long long mid = (lo + hi) >> 1;
-                        if (keys[mid] < k0) lo = mid + 1;
-                        else hi = mid;
-                    }
+                    const long long lo = bam_lower<long long>(keys, 0, P, k0);
                     const long long wend = lo + n < P ? lo + n : P;
                     if (lo < wend && keys[lo] < k0 + (unsigned long long)n) {
                         for (int j = lane; j < n; j += 64) {
                             const unsigned long long key = k0 + (unsigned long long)j;
-                            long long a = lo, b = wend;
-                            while (a < b) {
-                                const long long mid = (a + b) >> 1;
-                                if (keys[mid] < key) a = mid + 1;
-                                else b = mid;
-                            }
+                            const long long a = bam_lower<long long>(keys, lo, wend, key);
                             if (a < wend && keys[a] == key && (int)qual[qpos + j] >= mbq) {
                                 atomicAdd(&counts[a * 8], 1);
                                 if (rev) atomicAdd(&counts[a * 8 + 4], 1);
@@ -209,8 +153,8 @@ __global__ __launch_bounds__(256) void indel_count_kernel(const unsigned char *_
             } else { // every other case clears both states
                 run = false;
                 pend = 0;
-                if (op == 1 || op == 4) qpos += len;        // I, S
-                else if (op == 2 || op == 3) refpos += len; // D, N
+                if (bam_op_query(op)) qpos += len;      // I, S
+                else if (bam_op_ref(op)) refpos += len; // D, N
                 // H: neither
             }
         }

@@ -36,6 +36,8 @@
 //                        hand-over and drain body, launch dispatch, the host helpers one unit defines for the others
 // See include/amplisolve_hip.h for the data layout and DESIGN.md for the rooflines.  The library's other translation units:
 // ampli_runtime.hip (context, streams, memory, settings), ampli_pileup.hip (pileup_count_kernel, the step upstream of the path),
+// ampli_indel.hip, ampli_amplicon_count.hip, ampli_evidence.hip (the other walks over a BAM stream's records), ampli_bam.h (the record
+// layout, the position keys and their searches, the base decode and the CIGAR classes those four walks share),
 // ampli_comm.hip (RCCL binding of the multi-GPU merge), ampli_internal.h (the context and the stream helpers they all share).
 #include <hip/hip_runtime.h>
 

@@ -4,6 +4,7 @@
 
 #include <cstdint>
 
+#include "ampli_bam.h" // the record layout, the keys and their searches
 #include "ampli_internal.h"
 
 // ---------------------------------------------------------------------------
@@ -17,12 +18,6 @@
 //   counts[p][0..3] = A,C,G,T over both strands, counts[p][4..7] = the same on the reverse strand (flag 0x10).
 // keys: the panel's unique positions as (BAM reference id << 32 | 1-based position), sorted ascending.
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ unsigned ld_u32_unaligned(const unsigned char *p)
-{
-    unsigned v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
-}
 
 // A workgroup takes PILEUP_READS consecutive reads (one wave per read at a time, lanes over the bases of a match run) and counts
 // into a private LDS window of PILEUP_WINDOW panel positions that starts where its first read starts: a coordinate-sorted BAM keeps
@@ -32,6 +27,79 @@ __device__ __forceinline__ unsigned ld_u32_unaligned(const unsigned char *p)
 constexpr int PILEUP_READS = 256;
 constexpr int PILEUP_WINDOW = 1024;
 
+// One column of a match run that lies on panel position a: base q of the read into ctr[a][b4], and ctr[a][4 + b4] on the reverse strand.
+// ctr: the LDS window (a: window index) or the global counters (a: panel index).  true: the base was counted.
+template <typename I>
+__device__ __forceinline__ bool pileup_column(int *ctr, const I a, const unsigned char *seq, const unsigned char *qual, const int q, const int rev,
+                                              const int mbq)
+{
+    const int b4 = bam_nt(seq, q);
+    if (b4 < 0 || (int)qual[q] < mbq) return false;
+    atomicAdd(&ctr[a * 8 + b4], 1);
+    if (rev) atomicAdd(&ctr[a * 8 + 4 + b4], 1);
+    return true;
+}
+
+// The wave-per-read walk over reads first + wave, first + wave + 4, .. < end, the records read straight from global memory.  WINDOW: runs
+// inside the key range of the LDS window (win, its nw keys in wkeys) are searched and counted there; without it, and for every other
+// run, global search and global counters.  kept counts on lane 0 only, added on every lane.
+template <bool WINDOW>
+__device__ __forceinline__ void pileup_wave_walk(const unsigned char *__restrict__ bam, const unsigned long long *__restrict__ rec_off, const long long first,
+                                                 const long long end, const unsigned long long *__restrict__ keys, const long long P, const int mbq,
+                                                 const int mrq, int *__restrict__ counts, int *win, const unsigned long long *wkeys, const int nw,
+                                                 unsigned long long &kept, unsigned long long &added)
+{
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    unsigned long long prev_k0 = ~0ull; // the reads of an amplicon start at the same place: the last run's search is usually this run's
+    int prev_lo = 0;
+    for (long long read = first + wave; read < end; read += 4) {
+        BamRead h;
+        if (!bam_read_header<bam_u32>(bam + rec_off[read] + 4, mrq, h)) continue; // + 4: past block_size
+        if (lane == 0) ++kept;
+        long long refpos = h.pos; // 0-based
+        int qpos = 0;
+        for (int c = 0; c < h.n_cigar; ++c) {
+            const BamOp o = bam_cigar<bam_u32>(h.cig, c);
+            const int len = o.len;
+            if (bam_op_match(o.op)) {
+                const unsigned long long k0 = bam_key(h.ref_id, refpos + 1);
+                // the run lies inside the window's key range: everything below happens in LDS.  (No len > 0 as in the staged walk: a
+                // zero-length run executes no column on either side.)
+                const bool inwin = WINDOW && nw > 0 && k0 >= wkeys[0] && k0 + (unsigned long long)len - 1 <= wkeys[nw - 1];
+                if (inwin) {
+                    if (k0 != prev_k0) { // first window key >= k0 (wave-uniform)
+                        prev_lo = bam_lower<int>(wkeys, 0, nw, k0);
+                        prev_k0 = k0;
+                    }
+                    const int lo = prev_lo;
+                    const int wend = lo + len < nw ? lo + len : nw; // the keys of this run are among the next `len`
+                    for (int j = lane; j < len; j += 64) {
+                        const int a = bam_window_find(wkeys, lo, wend, j, k0 + (unsigned long long)j);
+                        if (a >= 0 && pileup_column(win, a, h.seq, h.qual, qpos + j, h.rev, mbq)) ++added;
+                    }
+                } else {
+                    // outside the window (unsorted file, a run that leaves the window, a position before it): global search and counters
+                    const long long lo = bam_lower<long long>(keys, 0, P, k0);
+                    const long long wend = lo + len < P ? lo + len : P;
+                    if (lo < wend && keys[lo] < k0 + (unsigned long long)len) {
+                        for (int j = lane; j < len; j += 64) {
+                            const unsigned long long key = k0 + (unsigned long long)j;
+                            const long long a = bam_lower<long long>(keys, lo, wend, key);
+                            if (a < wend && keys[a] == key && pileup_column(counts, a, h.seq, h.qual, qpos + j, h.rev, mbq)) ++added;
+                        }
+                    }
+                }
+                refpos += len;
+                qpos += len;
+            } else if (bam_op_query(o.op)) {
+                qpos += len;
+            } else if (bam_op_ref(o.op)) {
+                refpos += len;
+            }
+        }
+    }
+}
+
 __global__ __launch_bounds__(256) void pileup_count_kernel(const unsigned char *__restrict__ bam, const unsigned long long *__restrict__ rec_off,
                                                            const long long n_reads, const unsigned long long *__restrict__ keys, const long long P,
                                                            const int mbq, const int mrq, int *__restrict__ counts, unsigned long long *__restrict__ stats)
@@ -39,26 +107,12 @@ __global__ __launch_bounds__(256) void pileup_count_kernel(const unsigned char *
     __shared__ int win[PILEUP_WINDOW * 8];
     __shared__ unsigned long long wkeys[PILEUP_WINDOW]; // the window's panel keys: every search of an in-window run stays in LDS
     __shared__ long long win_base;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long first = (long long)blockIdx.x * PILEUP_READS;
+    const long long end = first + PILEUP_READS < n_reads ? first + PILEUP_READS : n_reads;
     for (int i = threadIdx.x; i < PILEUP_WINDOW * 8; i += 256) win[i] = 0;
-    if (threadIdx.x == 0) { // the window starts at the first panel position at or behind the start of the workgroup's first placed read
-        long long wb = 0;
-        for (long long rd = first; rd < n_reads && rd < first + PILEUP_READS; ++rd) {
-            const unsigned char *r = bam + rec_off[rd] + 4;
-            const int ref_id = (int)ld_u32_unaligned(r), pos = (int)ld_u32_unaligned(r + 4);
-            if (ref_id < 0 || pos < 0) continue;
-            const unsigned long long k0 = ((unsigned long long)(unsigned)ref_id << 32) | (unsigned long long)((long long)pos + 1);
-            long long lo = 0, hi = P;
-            while (lo < hi) {
-                const long long mid = (lo + hi) >> 1;
-                if (keys[mid] < k0) lo = mid + 1;
-                else hi = mid;
-            }
-            wb = lo;
-            break;
-        }
-        win_base = wb;
+    if (threadIdx.x == 0) {
+        unsigned long long k0;
+        win_base = bam_window_base(bam, rec_off, first, end, keys, P, k0);
     }
     __syncthreads();
     const long long wb = win_base;
@@ -66,119 +120,15 @@ __global__ __launch_bounds__(256) void pileup_count_kernel(const unsigned char *
     for (int i = threadIdx.x; i < nw; i += 256) wkeys[i] = keys[wb + i];
     __syncthreads();
     unsigned long long kept = 0, added = 0;
-    unsigned long long prev_k0 = ~0ull; // the reads of an amplicon start at the same place: the last run's search is usually this run's
-    int prev_lo = 0;
-    for (long long read = first + wave; read < n_reads && read < first + PILEUP_READS; read += 4) {
-        const unsigned char *r = bam + rec_off[read] + 4; // past block_size
-        const int ref_id = (int)ld_u32_unaligned(r), pos = (int)ld_u32_unaligned(r + 4);
-        const unsigned bin_mq_nl = ld_u32_unaligned(r + 8), flag_nc = ld_u32_unaligned(r + 12);
-        const int l_read_name = (int)(bin_mq_nl & 0xffu), mapq = (int)((bin_mq_nl >> 8) & 0xffu);
-        const int n_cigar = (int)(flag_nc & 0xffffu);
-        const unsigned flag = flag_nc >> 16;
-        if (ref_id < 0 || pos < 0 || (flag & (0x4u | 0x100u | 0x200u | 0x400u)) != 0 || mapq < mrq) continue;
-        ++kept;
-        const int l_seq = (int)ld_u32_unaligned(r + 16);
-        const unsigned char *cig = r + 32 + l_read_name;
-        const unsigned char *seq = cig + 4 * (size_t)n_cigar;
-        const unsigned char *qual = seq + (l_seq + 1) / 2;
-        const int rev = (int)((flag >> 4) & 1u);
-        long long refpos = pos; // 0-based
-        int qpos = 0;
-        for (int c = 0; c < n_cigar; ++c) {
-            const unsigned op_len = ld_u32_unaligned(cig + 4 * (size_t)c);
-            const unsigned op = op_len & 15u;
-            const int len = (int)(op_len >> 4);
-            if (op == 0 || op == 7 || op == 8) { // M, =, X
-                const unsigned long long k0 = ((unsigned long long)(unsigned)ref_id << 32) | (unsigned long long)(refpos + 1);
-                // the run lies inside the window's key range: everything below happens in LDS
-                const bool inwin = nw > 0 && k0 >= wkeys[0] && k0 + (unsigned long long)len - 1 <= wkeys[nw - 1];
-                if (inwin) {
-                    int lo;
-                    if (k0 == prev_k0) {
-                        lo = prev_lo;
-                    } else { // first window key >= k0 (wave-uniform)
-                        int l = 0, h = nw;
-                        while (l < h) {
-                            const int mid = (l + h) >> 1;
-                            if (wkeys[mid] < k0) l = mid + 1;
-                            else h = mid;
-                        }
-                        lo = l;
-                        prev_k0 = k0;
-                        prev_lo = l;
-                    }
-                    const int wend = lo + len < nw ? lo + len : nw; // the keys of this run are among the next `len`
-                    for (int j = lane; j < len; j += 64) {
-                        const unsigned long long key = k0 + (unsigned long long)j;
-                        int a = lo + j < wend ? lo + j : wend - 1; // no gap in the panel along this run: the key sits at lo + j
-                        if (wkeys[a] != key) {
-                            int b = wend;
-                            a = lo;
-                            while (a < b) {
-                                const int mid = (a + b) >> 1;
-                                if (wkeys[mid] < key) a = mid + 1;
-                                else b = mid;
-                            }
-                        }
-                        if (a < wend && wkeys[a] == key) {
-                            const int q = qpos + j;
-                            const unsigned nib = (seq[q >> 1] >> ((~q & 1) * 4)) & 15u;
-                            const int b4 = nib == 1u ? 0 : (nib == 2u ? 1 : (nib == 4u ? 2 : (nib == 8u ? 3 : -1)));
-                            if (b4 >= 0 && (int)qual[q] >= mbq) {
-                                atomicAdd(&win[a * 8 + b4], 1);
-                                if (rev) atomicAdd(&win[a * 8 + 4 + b4], 1);
-                                ++added;
-                            }
-                        }
-                    }
-                } else {
-                    // outside the window (unsorted file, a run that leaves the window, a position before it): global search and counters
-                    long long lo = 0, hi = P;
-                    while (lo < hi) {
-                        const long long mid = (lo + hi) >> 1;
-                        if (keys[mid] < k0) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    const long long wend = lo + len < P ? lo + len : P;
-                    if (lo < wend && keys[lo] < k0 + (unsigned long long)len) {
-                        for (int j = lane; j < len; j += 64) {
-                            const unsigned long long key = k0 + (unsigned long long)j;
-                            long long a = lo, b = wend;
-                            while (a < b) {
-                                const long long mid = (a + b) >> 1;
-                                if (keys[mid] < key) a = mid + 1;
-                                else b = mid;
-                            }
-                            if (a < wend && keys[a] == key) {
-                                const int q = qpos + j;
-                                const unsigned nib = (seq[q >> 1] >> ((~q & 1) * 4)) & 15u;
-                                const int b4 = nib == 1u ? 0 : (nib == 2u ? 1 : (nib == 4u ? 2 : (nib == 8u ? 3 : -1)));
-                                if (b4 >= 0 && (int)qual[q] >= mbq) {
-                                    atomicAdd(&counts[a * 8 + b4], 1);
-                                    if (rev) atomicAdd(&counts[a * 8 + 4 + b4], 1);
-                                    ++added;
-                                }
-                            }
-                        }
-                    }
-                }
-                refpos += len;
-                qpos += len;
-            } else if (op == 1 || op == 4) { // I, S
-                qpos += len;
-            } else if (op == 2 || op == 3) { // D, N
-                refpos += len;
-            } // H, P: neither
-        }
-    }
+    pileup_wave_walk<true>(bam, rec_off, first, end, keys, P, mbq, mrq, counts, win, wkeys, nw, kept, added);
     __syncthreads();
     for (int i = threadIdx.x; i < PILEUP_WINDOW * 8; i += 256) {
         const int v = win[i];
         if (v != 0 && wb + (i >> 3) < P) atomicAdd(&counts[(wb + (i >> 3)) * 8 + (i & 7)], v);
     }
     if (stats) {
-        if (lane == 0 && kept) atomicAdd(&stats[0], kept); // reads kept
-        if (added) atomicAdd(&stats[1], added);            // bases counted
+        if (kept) atomicAdd(&stats[0], kept);   // reads kept
+        if (added) atomicAdd(&stats[1], added); // bases counted
     }
 }
 
@@ -194,14 +144,6 @@ __global__ __launch_bounds__(256) void pileup_count_kernel(const unsigned char *
 constexpr int PILEUP_STAGE = 56 * 1024; // bytes of records a workgroup stages
 constexpr int PILEUP_SWINDOW = 384;     // panel positions of the staged kernel's LDS window
 constexpr int PILEUP_ROT = 3;
-
-__device__ __forceinline__ unsigned lds_u32(const unsigned char *p) // unaligned little-endian dword out of LDS
-{
-    const unsigned *q = (const unsigned *)((uintptr_t)p & ~(uintptr_t)3);
-    const unsigned sh = (unsigned)((uintptr_t)p & 3u);
-    const unsigned lo = q[0], hi = q[1];
-    return sh ? __builtin_amdgcn_alignbyte(hi, lo, sh) : lo;
-}
 
 __global__ __launch_bounds__(256) void pileup_count_staged_kernel(const unsigned char *__restrict__ bam, const unsigned long long *__restrict__ rec_off,
                                                                   const long long n_reads, const unsigned long long *__restrict__ keys, const long long P,
@@ -219,23 +161,9 @@ __global__ __launch_bounds__(256) void pileup_count_staged_kernel(const unsigned
     if (threadIdx.x == 0) {
         const unsigned long long b0 = rec_off[first], last = rec_off[first + n_here - 1];
         s_span[0] = b0 & ~15ull;
-        s_span[1] = last + 4ull + (unsigned long long)ld_u32_unaligned(bam + last);
-        long long wb = 0; // the window starts at the first panel position at or behind the start of the group's first placed read
-        for (int k = 0; k < n_here; ++k) {
-            const unsigned char *r = bam + rec_off[first + k] + 4;
-            const int ref_id = (int)ld_u32_unaligned(r), pos = (int)ld_u32_unaligned(r + 4);
-            if (ref_id < 0 || pos < 0) continue;
-            const unsigned long long k0 = ((unsigned long long)(unsigned)ref_id << 32) | (unsigned long long)((long long)pos + 1);
-            long long lo = 0, hi = P;
-            while (lo < hi) {
-                const long long mid = (lo + hi) >> 1;
-                if (keys[mid] < k0) lo = mid + 1;
-                else hi = mid;
-            }
-            wb = lo;
-            break;
-        }
-        s_wb = wb;
+        s_span[1] = last + 4ull + (unsigned long long)bam_u32()(bam + last);
+        unsigned long long k0;
+        s_wb = bam_window_base(bam, rec_off, first, first + n_here, keys, P, k0);
     }
     __syncthreads();
     const long long wb = s_wb;
@@ -253,162 +181,50 @@ __global__ __launch_bounds__(256) void pileup_count_staged_kernel(const unsigned
     unsigned long long kept = 0, added = 0;
     if (staged) {
         const int t = threadIdx.x;
-        if (t < n_here) {
-            const unsigned char *r = stage + (rec_off[first + t] - g0) + 4; // past block_size
-            const int ref_id = (int)lds_u32(r), pos = (int)lds_u32(r + 4);
-            const unsigned bin_mq_nl = lds_u32(r + 8), flag_nc = lds_u32(r + 12);
-            const int l_read_name = (int)(bin_mq_nl & 0xffu), mapq = (int)((bin_mq_nl >> 8) & 0xffu);
-            const int n_cigar = (int)(flag_nc & 0xffffu);
-            const unsigned flag = flag_nc >> 16;
-            if (!(ref_id < 0 || pos < 0 || (flag & (0x4u | 0x100u | 0x200u | 0x400u)) != 0 || mapq < mrq)) {
-                kept = 1;
-                const int l_seq = (int)lds_u32(r + 16);
-                const unsigned char *cig = r + 32 + l_read_name;
-                const unsigned char *seq = cig + 4 * (size_t)n_cigar;
-                const unsigned char *qual = seq + (l_seq + 1) / 2;
-                const int rev = (int)((flag >> 4) & 1u);
-                const int lane = t & 63;
-                long long refpos = pos;
-                int qpos = 0;
-                for (int c = 0; c < n_cigar; ++c) {
-                    const unsigned op_len = lds_u32(cig + 4 * (size_t)c);
-                    const unsigned op = op_len & 15u;
-                    const int len = (int)(op_len >> 4);
-                    if (op == 0 || op == 7 || op == 8) { // M, =, X
-                        const unsigned long long k0 = ((unsigned long long)(unsigned)ref_id << 32) | (unsigned long long)(refpos + 1);
-                        const bool inwin = len > 0 && nw > 0 && k0 >= wkeys[0] && k0 + (unsigned long long)len - 1 <= wkeys[nw - 1];
-                        int lo = 0;
-                        long long glo = 0, gend = 0;
-                        if (inwin) { // first window key >= k0
-                            int l = 0, h = nw;
-                            while (l < h) {
-                                const int mid = (l + h) >> 1;
-                                if (wkeys[mid] < k0) l = mid + 1;
-                                else h = mid;
-                            }
-                            lo = l;
-                        } else if (len > 0) { // outside the window: global keys, global counters
-                            long long l = 0, h = P;
-                            while (l < h) {
-                                const long long mid = (l + h) >> 1;
-                                if (keys[mid] < k0) l = mid + 1;
-                                else h = mid;
-                            }
-                            glo = l;
-                            gend = l + len < P ? l + len : P;
+        BamRead h;
+        if (t < n_here && bam_read_header<lds_u32>(stage + (rec_off[first + t] - g0) + 4, mrq, h)) { // + 4: past block_size
+            kept = 1;
+            const int lane = t & 63;
+            long long refpos = h.pos;
+            int qpos = 0;
+            for (int c = 0; c < h.n_cigar; ++c) {
+                const BamOp o = bam_cigar<lds_u32>(h.cig, c);
+                const int len = o.len;
+                if (bam_op_match(o.op)) {
+                    const unsigned long long k0 = bam_key(h.ref_id, refpos + 1);
+                    const bool inwin = len > 0 && nw > 0 && k0 >= wkeys[0] && k0 + (unsigned long long)len - 1 <= wkeys[nw - 1];
+                    int lo = 0;
+                    long long glo = 0, gend = 0;
+                    if (inwin) { // first window key >= k0
+                        lo = bam_lower<int>(wkeys, 0, nw, k0);
+                    } else if (len > 0) { // outside the window: global keys, global counters
+                        glo = bam_lower<long long>(keys, 0, P, k0);
+                        gend = glo + len < P ? glo + len : P;
+                    }
+                    const int wend = lo + len < nw ? lo + len : nw;
+                    int j = len > 0 ? (lane * PILEUP_ROT) % len : 0; // rotated start: the lanes of a wave hit different counters
+                    for (int step = 0; step < len; ++step, j = j + 1 == len ? 0 : j + 1) {
+                        const unsigned long long key = k0 + (unsigned long long)j;
+                        if (inwin) {
+                            const int a = bam_window_find(wkeys, lo, wend, j, key);
+                            if (a >= 0 && pileup_column(win, a, h.seq, h.qual, qpos + j, h.rev, mbq)) ++added;
+                        } else if (glo < gend) {
+                            const long long a = bam_lower<long long>(keys, glo, gend, key);
+                            if (a < gend && keys[a] == key && pileup_column(counts, a, h.seq, h.qual, qpos + j, h.rev, mbq)) ++added;
                         }
-                        const int wend = lo + len < nw ? lo + len : nw;
-                        int j = len > 0 ? (lane * PILEUP_ROT) % len : 0; // rotated start: the lanes of a wave hit different counters
-                        for (int step = 0; step < len; ++step, j = j + 1 == len ? 0 : j + 1) {
-                            const unsigned long long key = k0 + (unsigned long long)j;
-                            long long a = -1; // index of the key among the panel positions, -1: not a panel position
-                            if (inwin) {
-                                int x = lo + j < wend ? lo + j : wend - 1;
-                                if (wkeys[x] != key) {
-                                    int b = wend;
-                                    x = lo;
-                                    while (x < b) {
-                                        const int mid = (x + b) >> 1;
-                                        if (wkeys[mid] < key) x = mid + 1;
-                                        else b = mid;
-                                    }
-                                }
-                                if (x < wend && wkeys[x] == key) a = x;
-                            } else if (glo < gend) {
-                                long long x = glo, b = gend;
-                                while (x < b) {
-                                    const long long mid = (x + b) >> 1;
-                                    if (keys[mid] < key) x = mid + 1;
-                                    else b = mid;
-                                }
-                                if (x < gend && keys[x] == key) a = x;
-                            }
-                            if (a < 0) continue;
-                            const int q = qpos + j;
-                            const unsigned nib = (seq[q >> 1] >> ((~q & 1) * 4)) & 15u;
-                            const int b4 = nib == 1u ? 0 : (nib == 2u ? 1 : (nib == 4u ? 2 : (nib == 8u ? 3 : -1)));
-                            if (b4 < 0 || (int)qual[q] < mbq) continue;
-                            if (inwin) {
-                                atomicAdd(&win[a * 8 + b4], 1);
-                                if (rev) atomicAdd(&win[a * 8 + 4 + b4], 1);
-                            } else {
-                                atomicAdd(&counts[a * 8 + b4], 1);
-                                if (rev) atomicAdd(&counts[a * 8 + 4 + b4], 1);
-                            }
-                            ++added;
-                        }
-                        refpos += len;
-                        qpos += len;
-                    } else if (op == 1 || op == 4) { // I, S
-                        qpos += len;
-                    } else if (op == 2 || op == 3) { // D, N
-                        refpos += len;
-                    } // H, P: neither
+                    }
+                    refpos += len;
+                    qpos += len;
+                } else if (bam_op_query(o.op)) {
+                    qpos += len;
+                } else if (bam_op_ref(o.op)) {
+                    refpos += len;
                 }
             }
         }
     } else {
         // records too long for the stage: one wave per read at a time, straight from global memory, global counters
-        const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-        for (long long read = first + wave; read < first + n_here; read += 4) {
-            const unsigned char *r = bam + rec_off[read] + 4;
-            const int ref_id = (int)ld_u32_unaligned(r), pos = (int)ld_u32_unaligned(r + 4);
-            const unsigned bin_mq_nl = ld_u32_unaligned(r + 8), flag_nc = ld_u32_unaligned(r + 12);
-            const int l_read_name = (int)(bin_mq_nl & 0xffu), mapq = (int)((bin_mq_nl >> 8) & 0xffu);
-            const int n_cigar = (int)(flag_nc & 0xffffu);
-            const unsigned flag = flag_nc >> 16;
-            if (ref_id < 0 || pos < 0 || (flag & (0x4u | 0x100u | 0x200u | 0x400u)) != 0 || mapq < mrq) continue;
-            if (lane == 0) ++kept;
-            const int l_seq = (int)ld_u32_unaligned(r + 16);
-            const unsigned char *cig = r + 32 + l_read_name;
-            const unsigned char *seq = cig + 4 * (size_t)n_cigar;
-            const unsigned char *qual = seq + (l_seq + 1) / 2;
-            const int rev = (int)((flag >> 4) & 1u);
-            long long refpos = pos;
-            int qpos = 0;
-            for (int c = 0; c < n_cigar; ++c) {
-                const unsigned op_len = ld_u32_unaligned(cig + 4 * (size_t)c);
-                const unsigned op = op_len & 15u;
-                const int len = (int)(op_len >> 4);
-                if (op == 0 || op == 7 || op == 8) {
-                    const unsigned long long k0 = ((unsigned long long)(unsigned)ref_id << 32) | (unsigned long long)(refpos + 1);
-                    long long lo = 0, hi = P;
-                    while (lo < hi) {
-                        const long long mid = (lo + hi) >> 1;
-                        if (keys[mid] < k0) lo = mid + 1;
-                        else hi = mid;
-                    }
-                    const long long wend = lo + len < P ? lo + len : P;
-                    if (lo < wend && keys[lo] < k0 + (unsigned long long)len) {
-                        for (int j = lane; j < len; j += 64) {
-                            const unsigned long long key = k0 + (unsigned long long)j;
-                            long long a = lo, b = wend;
-                            while (a < b) {
-                                const long long mid = (a + b) >> 1;
-                                if (keys[mid] < key) a = mid + 1;
-                                else b = mid;
-                            }
-                            if (a < wend && keys[a] == key) {
-                                const int q = qpos + j;
-                                const unsigned nib = (seq[q >> 1] >> ((~q & 1) * 4)) & 15u;
-                                const int b4 = nib == 1u ? 0 : (nib == 2u ? 1 : (nib == 4u ? 2 : (nib == 8u ? 3 : -1)));
-                                if (b4 >= 0 && (int)qual[q] >= mbq) {
-                                    atomicAdd(&counts[a * 8 + b4], 1);
-                                    if (rev) atomicAdd(&counts[a * 8 + 4 + b4], 1);
-                                    ++added;
-                                }
-                            }
-                        }
-                    }
-                    refpos += len;
-                    qpos += len;
-                } else if (op == 1 || op == 4) {
-                    qpos += len;
-                } else if (op == 2 || op == 3) {
-                    refpos += len;
-                }
-            }
-        }
+        pileup_wave_walk<false>(bam, rec_off, first, first + n_here, keys, P, mbq, mrq, counts, nullptr, nullptr, 0, kept, added);
     }
     __syncthreads();
     for (int i = threadIdx.x; i < PILEUP_SWINDOW * 8; i += 256) {
