@@ -258,6 +258,11 @@ extern "C" int ampli_pileup_amplicon_count(ampli_ctx *ctx, const uint8_t *d_bam,
     if (!ctx) return AMPLI_E_INVALID;
     if (!d_bam || !d_rec_off || n_reads < 0 || !d_lo || !d_hi || !d_reach || !d_amp_off || A < 0 || W < 0 || !d_counts || !d_amp_reads)
         return fail(ctx, AMPLI_E_INVALID, "pileup_amplicon_count: bad argument");
+    if ((((uintptr_t)d_rec_off | (uintptr_t)d_lo | (uintptr_t)d_hi | (uintptr_t)d_reach | (uintptr_t)d_amp_off | (uintptr_t)d_amp_reads | (uintptr_t)d_stats) & 7) != 0 ||
+        ((uintptr_t)d_counts & 3) != 0)
+        return fail(ctx, AMPLI_E_INVALID,
+                    "pileup_amplicon_count: bad argument (8-byte aligned d_rec_off, d_lo, d_hi, d_reach, d_amp_off, d_amp_reads and d_stats, 4-byte aligned "
+                    "d_counts)");
     if (min_overlap < 1 || min_overlap > 100) return fail(ctx, AMPLI_E_INVALID, "pileup_amplicon_count: min_overlap must lie in 1 .. 100");
     if (W > 0x7fffffffll) return fail(ctx, AMPLI_E_RANGE, "pileup_amplicon_count: 2^31 walk entries or more");
     if ((n_reads + AMPCOUNT_READS - 1) / AMPCOUNT_READS > 0x7fffffffll)
@@ -282,6 +287,12 @@ extern "C" int ampli_amplicon_layers(ampli_ctx *ctx, const int32_t *d_counts, co
     if (!d_counts || !d_lo || !d_hi || !d_reach || !d_amp_off || A < 0 || W < 0 || !d_keys || P < 0 || L < 0 || (L > 0 && (!d_layers || !d_layer_amp)) ||
         !d_total)
         return fail(ctx, AMPLI_E_INVALID, "amplicon_layers: bad argument");
+    // the gather loads and stores int4: d_counts, d_layers and d_total are 16-byte aligned by the contract; the other pointers are typed
+    if ((((uintptr_t)d_counts | (uintptr_t)d_layers | (uintptr_t)d_total) & 15) != 0 ||
+        (((uintptr_t)d_lo | (uintptr_t)d_hi | (uintptr_t)d_reach | (uintptr_t)d_amp_off | (uintptr_t)d_keys) & 7) != 0 || ((uintptr_t)d_layer_amp & 3) != 0)
+        return fail(ctx, AMPLI_E_INVALID,
+                    "amplicon_layers: bad argument (16-byte aligned d_counts, d_layers and d_total, 8-byte aligned d_lo, d_hi, d_reach, d_amp_off and d_keys, "
+                    "4-byte aligned d_layer_amp)");
     if (W > 0x7fffffffll) return fail(ctx, AMPLI_E_RANGE, "amplicon_layers: 2^31 walk entries or more");
     if ((P + 255) / 256 > 0x7fffffffll) return fail(ctx, AMPLI_E_RANGE, "amplicon_layers: too many positions in one call");
     if (A == 0 || P == 0) return AMPLI_OK;

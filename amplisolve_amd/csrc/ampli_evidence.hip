@@ -140,6 +140,8 @@ extern "C" int ampli_pileup_evidence(ampli_ctx *ctx, const uint8_t *d_bam, const
 {
     if (!ctx) return AMPLI_E_INVALID;
     if (!d_bam || !d_rec_off || n_reads < 0 || !d_keys || P < 0 || !d_hist) return fail(ctx, AMPLI_E_INVALID, "pileup_evidence: bad argument");
+    if ((((uintptr_t)d_rec_off | (uintptr_t)d_keys | (uintptr_t)d_stats) & 7) != 0 || ((uintptr_t)d_hist & 3) != 0)
+        return fail(ctx, AMPLI_E_INVALID, "pileup_evidence: bad argument (8-byte aligned d_rec_off, d_keys and d_stats, 4-byte aligned d_hist)");
     if (n_reads == 0 || P == 0) return AMPLI_OK;
     if ((n_reads + EVIDENCE_READS - 1) / EVIDENCE_READS > 0x7fffffffll)
         return fail(ctx, AMPLI_E_RANGE, "pileup_evidence: too many reads in one call; split the batch");
@@ -185,6 +187,8 @@ extern "C" int ampli_evidence_score(ampli_ctx *ctx, const int32_t *d_hist, int64
 {
     if (!ctx) return AMPLI_E_INVALID;
     if (!d_hist || P < 0 || !d_ref_nt || !d_alt_nt || !d_int || !d_med || !d_z2 || !d_alt_used) return fail(ctx, AMPLI_E_INVALID, "evidence_score: bad argument");
+    if ((((uintptr_t)d_int | (uintptr_t)d_z2) & 7) != 0 || (((uintptr_t)d_hist | (uintptr_t)d_med) & 3) != 0)
+        return fail(ctx, AMPLI_E_INVALID, "evidence_score: bad argument (8-byte aligned d_int and d_z2, 4-byte aligned d_hist and d_med)");
     if (P == 0) return AMPLI_OK;
     const int64_t groups = (P * AMPLI_EVIDENCE_METRICS + 255) / 256;
     if (groups > 0x7fffffffll) return fail(ctx, AMPLI_E_RANGE, "evidence_score: too many positions in one call");

@@ -175,6 +175,8 @@ extern "C" int ampli_pileup_indel_count(ampli_ctx *ctx, const uint8_t *d_bam, co
 {
     if (!ctx) return AMPLI_E_INVALID;
     if (!d_bam || !d_rec_off || n_reads < 0 || !d_keys || P < 0 || !d_counts) return fail(ctx, AMPLI_E_INVALID, "pileup_indel_count: bad argument");
+    if ((((uintptr_t)d_rec_off | (uintptr_t)d_keys | (uintptr_t)d_stats) & 7) != 0 || (((uintptr_t)d_counts | (uintptr_t)d_lengths) & 3) != 0)
+        return fail(ctx, AMPLI_E_INVALID, "pileup_indel_count: bad argument (8-byte aligned d_rec_off, d_keys and d_stats, 4-byte aligned d_counts and d_lengths)");
     if (n_reads == 0 || P == 0) return AMPLI_OK;
     if ((n_reads + INDEL_READS - 1) / INDEL_READS > 0x7fffffffll)
         return fail(ctx, AMPLI_E_RANGE, "pileup_indel_count: too many reads in one call; split the batch");

@@ -242,6 +242,9 @@ extern "C" int ampli_pileup_count(ampli_ctx *ctx, const uint8_t *d_bam, const ui
 {
     if (!ctx) return AMPLI_E_INVALID;
     if (!d_bam || !d_rec_off || n_reads < 0 || !d_keys || P <= 0 || !d_counts) return fail(ctx, AMPLI_E_INVALID, "pileup_count: bad argument");
+    // the staged kernel copies uint4 pieces from d_bam + (offset & ~15); the other pointers are typed
+    if (((uintptr_t)d_bam & 15) != 0 || (((uintptr_t)d_rec_off | (uintptr_t)d_keys | (uintptr_t)d_stats) & 7) != 0 || ((uintptr_t)d_counts & 3) != 0)
+        return fail(ctx, AMPLI_E_INVALID, "pileup_count: bad argument (16-byte aligned d_bam, 8-byte aligned d_rec_off, d_keys and d_stats, 4-byte aligned d_counts)");
     if (n_reads == 0) return AMPLI_OK;
     if ((n_reads + PILEUP_READS - 1) / PILEUP_READS > 0x7fffffffll) return fail(ctx, AMPLI_E_RANGE, "pileup_count: too many reads in one call; split the batch");
     HIP_TRY(ctx, hipSetDevice(ctx->device));

@@ -1204,7 +1204,9 @@ int ampli_synth_ref(ampli_ctx *ctx, uint8_t *d_ref_code, int64_t P, uint64_t see
  * positions as (BAM reference id << 32 | 1-based position), ascending.  d_counts int32 [P][8] = {A,C,G,T, Ars,Crs,Grs,Trs} is
  * ACCUMULATED into (zero it first; batches of one file add up).  Kept reads: mapped, not secondary / QC-fail / duplicate,
  * MAPQ >= mrq; counted bases: M / = / X columns, A/C/G/T, base quality >= mbq.  d_stats (optional, 2 words, accumulated):
- * reads kept, bases counted.
+ * reads kept, bases counted.  AMPLI_E_INVALID, before anything is launched: a d_bam that is not 16-byte aligned, or d_rec_off, d_keys,
+ * d_stats (8 bytes) or d_counts (4 bytes) below the alignment of its type.  The three walks below and the two gathers refuse typed
+ * pointers below their natural alignment in the same way.
  */
 int ampli_pileup_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *d_rec_off, int64_t n_reads, const uint64_t *d_keys, int64_t P,
                        int32_t mbq, int32_t mrq, int32_t *d_counts, uint64_t *d_stats);
@@ -1291,8 +1293,8 @@ int ampli_pileup_amplicon_count(ampli_ctx *ctx, const uint8_t *d_bam, const uint
  * of the l-th covering amplicon.  Where there is none, it is the project's absent-record marker: slot 0 = INT32_MIN, the rest 0.
  * d_layers: int32 [L][P][8].  d_layer_amp: int32 [L][P], that amplicon's sorted index, or -1.  d_total: int32 [P][8], the sum over ALL
  * covering amplicons, including those beyond L.  Every output cell has one owner and is overwritten, not accumulated.  A position under
- * no amplicon gets zeros in d_total.  d_counts, d_layers and d_total are 16-byte aligned.  L = 0 gives the totals alone (d_layers and
- * d_layer_amp may then be NULL).
+ * no amplicon gets zeros in d_total.  d_counts, d_layers and d_total are 16-byte aligned (the gather loads and stores int4; anything else
+ * is AMPLI_E_INVALID).  L = 0 gives the totals alone (d_layers and d_layer_amp may then be NULL).
  * Refusals as above (AMPLI_E_RANGE: W >= 2^31; AMPLI_E_INVALID: a null required pointer, negative sizes).  A = 0 or P = 0 is a
  * successful no-op.  Layer order is genomic and not biological.
  */

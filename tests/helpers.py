@@ -149,6 +149,26 @@ def fenced(shape, dtype, poison=0xFF, device="cuda"):
     return view, check
 
 
+def assert_misaligned_refused(ctx, call, good, shifts, outputs, message=b"bad argument"):
+    """`call(*good)` would succeed (ctx.h first, device pointers as integers).  For every (index, bytes) of `shifts` the same call with
+    that pointer moved by so many bytes -- below the alignment the contract gives it -- returns AMPLI_E_INVALID (-1) with `message`, and
+    afterwards every byte of the fenced `outputs` ((view, check) pairs of fenced(), stats included) and of their guards still holds the
+    poison: a refusal launches nothing."""
+    import torch
+
+    for at, by in shifts:
+        args = list(good)
+        assert isinstance(args[at], int) and args[at] % 16 == 0 and 0 < by < 16, at
+        args[at] += by
+        assert call(*args) == -1, f"argument {at} moved by {by} byte(s) was not refused"
+        assert message in ctx.lib.ampli_last_error(ctx.h), ctx.lib.ampli_last_error(ctx.h)
+    ctx.sync()
+    torch.cuda.synchronize()
+    for view, check in outputs:
+        assert bool((check.raw == check.raw[0]).all()), "a refused call wrote to an output"
+        check()
+
+
 def synth_recs(P, n, first=0, seed=SEED, depth=2000, tumour=False):
     out = np.empty((n, P, 8), np.int32)
     rc = host_lib().ampli_host_synth_fill(out.ctypes.data_as(C.c_void_p), P, n, first, seed, depth, int(tumour))

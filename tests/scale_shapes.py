@@ -112,3 +112,103 @@ def big_special_rows():
     wraps), the first that starts past 2^32 bytes, and the last row.  The whole output is 1.09e9 four-byte elements: an offset of 2^31
     ELEMENTS does not exist at this shape."""
     return (0, -(-(1 << 31) // BIG_ROW_BYTES), -(-(1 << 32) // BIG_ROW_BYTES), BIG_ROWS - 1)
+
+
+# ---- E: alignment streams whose byte offsets pass 2^31 and 2^32.  One allocation filled with the byte 0x01, d_bam 2 GiB into it; the
+# records of one stream lie in three places: at d_bam, BAM_ROOM past 2^31 bytes from it and 2 * BAM_ROOM past 2^32.  A place holds less
+# than BAM_ROOM bytes, so an offset of place 2 cut to 32 bits lands in [2 * BAM_ROOM, 3 * BAM_ROOM) -- behind place 0's records -- and an
+# offset of place 1 sign-extended from 32 bits lands BAM_ROOM bytes into the allocation, 2 GiB below d_bam: on the pattern both times.
+BAM_BASE = 1 << 31
+BAM_ROOM = 1 << 20
+BAM_PLACES = (0, (1 << 31) + BAM_ROOM, (1 << 32) + 2 * BAM_ROOM)
+BAM_READS = 3 * 256 + 40
+BAM_SHIFT = 100
+BAM_SOURCE = "fuzz_12_2048_reads"  # of tests/pileup_model.py: short amplicon reads with indels, clips, odd operations, both strands, a full panel
+BAM_PATTERN = 0x01
+
+
+def bam_bytes():
+    """bytes of the allocation: the base offset, the last place and its room"""
+    return BAM_BASE + BAM_PLACES[2] + BAM_ROOM
+
+
+@functools.lru_cache(None)
+def bam_filtered_mask():
+    """BAM_FILTERED as csrc/ampli_bam.h states it"""
+    m = re.search(r"^constexpr unsigned BAM_FILTERED = ([^;]+);", _text("ampli_bam.h"), re.M)
+    assert m, "no `constexpr unsigned BAM_FILTERED = ...;` line in ampli_bam.h"
+    mask = 0
+    for term in m.group(1).split("|"):
+        mask |= int(term.strip().rstrip("u"), 16)
+    return mask
+
+
+def bam_cuts(arrangement):
+    """the reads [cut[k], cut[k + 1]) lie in place k.  "staged": every group of 256 consecutive reads lies wholly inside one place (the
+    last, partial group behind the third); "fallback": the same stream with the cuts BAM_SHIFT reads later, so that the second and the
+    third group each straddle a gap"""
+    shift = {"staged": 0, "fallback": BAM_SHIFT}[arrangement]
+    return (0, 256 + shift, 512 + shift, BAM_READS)
+
+
+@functools.lru_cache(None)
+def bam_stream():
+    """(buf, rec_off, keys, intervals, mbq, mrq): the first BAM_READS reads of BAM_SOURCE as a dense stream, its panel, and the design
+    tests/walk_cross.design_of derives from the panel for the amplicon walk; mbq = mrq = 20 (the case's own 40 / 21 keep a third of
+    the reads and a tenth of their bases)"""
+    from tests import pileup_model as pm
+    from tests import walk_cross as wc
+
+    case = next(c for c in pm.cases() if c.name == BAM_SOURCE)
+    buf, off = pm.build_stream(case.reads[:BAM_READS], lead=5, trail=16)
+    for a in (buf, off):
+        a.setflags(write=False)
+    return buf, off, case.keys, tuple(wc.design_of(case.keys)), 20, 20
+
+
+def bam_layout(arrangement):
+    """([(offset from d_bam, first byte, end byte in the dense buffer)] per place, rec_off of the placed stream): a place's records keep
+    their distances and the 16-byte phase of the place's first record"""
+    import numpy as np
+
+    from tests import pileup_model as pm
+
+    buf, off = bam_stream()[:2]
+    end = pm.headers(buf, off).end
+    cuts = bam_cuts(arrangement)
+    o = off.astype(np.int64)
+    pieces, wide = [], np.empty(len(o), np.int64)
+    for k in range(3):
+        a, b = cuts[k], cuts[k + 1]
+        at = BAM_PLACES[k] + int(o[a] & 15)
+        pieces.append((at, int(o[a]), int(end[b - 1])))
+        wide[a:b] = at + (o[a:b] - o[a])
+    return pieces, wide.astype(np.uint64)
+
+
+def bam_group_spans(arrangement):
+    """int64 [groups][2] of the placed stream, as tests/pileup_model.group_spans computes them: from a group's first offset rounded down
+    to 16 to the end of its last record"""
+    import numpy as np
+
+    from tests import pileup_model as pm
+
+    buf, off = bam_stream()[:2]
+    size = pm.headers(buf, off).end - off.astype(np.int64)
+    wide = bam_layout(arrangement)[1].astype(np.int64)
+    R = pm.geometry().reads
+    first = wide[0::R]
+    last = np.minimum(np.arange(len(first)) * R + R, len(wide)) - 1
+    return np.stack([first & ~np.int64(15), wide[last] + size[last]], 1)
+
+
+# ---- F: outputs of the read walks beyond 2^32 bytes: cells of `cell_bytes` bytes per key (or walk entry), real work on four of them
+CELL_BYTES = {"evidence_hist": 3072, "indel_lengths": 256, "pileup_counts": 32, "amplicon_counts": 32, "layers_total": 32}
+CELL_EXTRA = 1000  # cells behind the first one past 2^32 bytes
+
+
+def special_cells(cell_bytes):
+    """(cells, (0, the first cell that starts at or past 2^31 bytes, the first at or past 2^32 bytes, the last cell))"""
+    c31, c32 = -(-(1 << 31) // cell_bytes), -(-(1 << 32) // cell_bytes)
+    n = c32 + CELL_EXTRA
+    return n, (0, c31, c32, n - 1)

@@ -66,3 +66,27 @@ def test_the_layers_call_overwrites_every_cell_and_nothing_beyond(ctx, name, L):
         assert bool((layers.view(torch.uint8) == 0xFF).all()) and bool((layer_amp.view(torch.uint8) == 0x5A).all())
     for c in (c0, c1, c2):
         c()
+
+
+def test_misaligned_pointers_are_refused_before_anything_is_launched(ctx):
+    """ampli_pileup_amplicon_count: every 8-byte array below 8 bytes, d_counts below 4.  ampli_amplicon_layers: d_counts, d_layers and
+    d_total below 16 bytes (the gather loads and stores int4), the 8-byte arrays below 8, d_layer_amp below 4.  AMPLI_E_INVALID, and the
+    fenced outputs (the statistics included) are untouched"""
+    import torch
+
+    case = BY_NAME["three_amplicons_over_one_position_L_2"]
+    bam, off, lo, hi, reach, amp_off = am.upload(case)
+    A, W = len(case.amps.lo), int(case.amps.amp_off[-1])
+    counts, amp_reads, stats = helpers.fenced((W, 8), torch.int32), helpers.fenced((A, 2), torch.int64), helpers.fenced((4,), torch.int64)
+    ptr = lambda t: t.data_ptr()  # noqa: E731
+    good = (ctx.h, ptr(bam), ptr(off), off.numel(), ptr(lo), ptr(hi), ptr(reach), ptr(amp_off), A, W, case.mbq, case.mrq, case.min_overlap, ptr(counts[0]),
+            ptr(amp_reads[0]), ptr(stats[0]))
+    helpers.assert_misaligned_refused(ctx, ctx.lib.ampli_pileup_amplicon_count, good, [(2, 4), (4, 4), (5, 4), (6, 4), (7, 4), (13, 2), (14, 4), (15, 4)],
+                                      [counts, amp_reads, stats], b"pileup_amplicon_count: bad argument")
+    walked = torch.zeros((W, 8), dtype=torch.int32, device="cuda")
+    keys = am._up(case.keys)
+    P = keys.numel()
+    layers, layer_amp, total = helpers.fenced((2, P, 8), torch.int32), helpers.fenced((2, P), torch.int32), helpers.fenced((P, 8), torch.int32)
+    good = (ctx.h, ptr(walked), ptr(lo), ptr(hi), ptr(reach), ptr(amp_off), A, W, ptr(keys), P, 2, ptr(layers[0]), ptr(layer_amp[0]), ptr(total[0]))
+    helpers.assert_misaligned_refused(ctx, ctx.lib.ampli_amplicon_layers, good, [(1, 4), (1, 8), (2, 4), (3, 4), (4, 4), (5, 4), (8, 4), (11, 4), (11, 8), (12, 2), (13, 4), (13, 8)],
+                                      [layers, layer_amp, total], b"amplicon_layers: bad argument")

@@ -142,3 +142,23 @@ def test_score_argument_checks(ctx):
     assert call(None, *good[1:]) != 0
     assert call(*good[:2], 0, *good[3:]) == 0 and call(*good) == 0
     ctx.sync()
+
+
+def test_misaligned_pointers_are_refused_before_anything_is_launched(ctx):
+    """ampli_pileup_evidence: d_rec_off, d_keys and d_stats below 8 bytes, d_hist below 4; ampli_evidence_score: d_int and d_z2 below 8,
+    d_hist and d_med below 4.  AMPLI_E_INVALID, and the fenced outputs are untouched"""
+    import torch
+
+    from tests.helpers import assert_misaligned_refused, fenced
+
+    case = BY_NAME["odd_l_seq_9"]
+    bam, off, keys = em.upload(case)
+    P = keys.numel()
+    hist, stats = fenced((P, 4, em.METRICS, em.BINS), torch.int32), fenced((2,), torch.int64)
+    good = (ctx.h, bam.data_ptr(), off.data_ptr(), off.numel(), keys.data_ptr(), P, 20, 20, hist[0].data_ptr(), stats[0].data_ptr())
+    assert_misaligned_refused(ctx, ctx.lib.ampli_pileup_evidence, good, [(2, 4), (4, 4), (8, 2), (9, 4)], [hist, stats], b"pileup_evidence: bad argument")
+    planes = torch.zeros((P, 4, em.METRICS, em.BINS), dtype=torch.int32, device="cuda")
+    nt = torch.zeros(P, dtype=torch.int8, device="cuda")
+    outs = [fenced((P, 3, 3), torch.int64), fenced((P, 3, 2), torch.int32), fenced((P, 3), torch.float64), fenced((P,), torch.int8)]
+    good = (ctx.h, planes.data_ptr(), P, nt.data_ptr(), nt.data_ptr()) + tuple(o[0].data_ptr() for o in outs)
+    assert_misaligned_refused(ctx, ctx.lib.ampli_evidence_score, good, [(1, 2), (5, 4), (6, 2), (7, 4)], outs, b"evidence_score: bad argument")

@@ -83,3 +83,18 @@ def test_argument_checks(ctx):
     assert call(*good) == 0
     ctx.sync()
     assert np.array_equal(counts.cpu().numpy().astype(np.int64), case.want().counts)
+
+
+def test_misaligned_pointers_are_refused_before_anything_is_launched(ctx):
+    """d_rec_off, d_keys and d_stats below 8 bytes, d_counts and d_lengths below 4: AMPLI_E_INVALID, and the fenced outputs are untouched"""
+    import torch
+
+    from tests.helpers import assert_misaligned_refused, fenced
+
+    case = BY_NAME["insertion_forward_10M2I10M"]
+    bam, off, keys = im.upload(case)
+    P = keys.numel()
+    counts, lengths, stats = fenced((P, 8), torch.int32), fenced((P, 2, im.BINS), torch.int32), fenced((2,), torch.int64)
+    good = (ctx.h, bam.data_ptr(), off.data_ptr(), off.numel(), keys.data_ptr(), P, 20, 20, counts[0].data_ptr(), lengths[0].data_ptr(), stats[0].data_ptr())
+    assert_misaligned_refused(ctx, ctx.lib.ampli_pileup_indel_count, good, [(2, 4), (4, 4), (8, 2), (9, 2), (10, 4)], [counts, lengths, stats],
+                              b"pileup_indel_count: bad argument")

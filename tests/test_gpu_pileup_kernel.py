@@ -72,6 +72,21 @@ def test_no_reads_is_accepted_and_writes_nothing(ctx):
     assert not d.mismatches(np.zeros((len(case.keys), 8), np.int64), 0, 0)
 
 
+def test_misaligned_pointers_are_refused_before_anything_is_launched(ctx):
+    """d_bam below 16 bytes (the staged kernel copies uint4 pieces from d_bam + (offset & ~15)), d_rec_off, d_keys and d_stats below 8,
+    d_counts below 4: AMPLI_E_INVALID, and the fenced counts and stats are untouched"""
+    import torch
+
+    from tests.helpers import assert_misaligned_refused, fenced
+
+    case, = _pick("group_size_257")
+    up = lambda a, t: torch.from_numpy(np.ascontiguousarray(a).view(t)).cuda()  # noqa: E731
+    bam, off, keys = up(case.buf, np.uint8), up(case.rec_off, np.int64), up(case.keys, np.int64)
+    counts, stats = fenced((len(case.keys), 8), torch.int32), fenced((2,), torch.int64)
+    good = (ctx.h, bam.data_ptr(), off.data_ptr(), case.n_reads, keys.data_ptr(), len(case.keys), case.mbq, case.mrq, counts[0].data_ptr(), stats[0].data_ptr())
+    assert_misaligned_refused(ctx, ctx.lib.ampli_pileup_count, good, [(1, 1), (1, 4), (1, 8), (2, 4), (4, 4), (8, 2), (9, 4)], [counts, stats], b"pileup_count: bad argument")
+
+
 @pytest.fixture(scope="module")
 def wave_per_read_library(tmp_path_factory):
     """ampli_pileup.hip built with -DAMPLI_PILEUP_WAVE_PER_READ (+ the runtime it needs) into a temporary directory"""
