@@ -6,7 +6,10 @@ the library or the GPU is missing the calls raise AmpliError.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
+import functools
+import inspect
 from dataclasses import dataclass
 
 from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice, Call, DiluteMix, FractionParams, GenotypeParams, LooCall, MonitorParams, Records,
@@ -71,6 +74,34 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def _on_stream(fn):
+    """fn(self, ...) with the context's stream as torch's current stream (the contract in Context's docstring): every torch allocation,
+    fill, upload and readback inside fn is then ordered on it and comes from its pool of the caching allocator.  Where the context's
+    stream is already current -- the default context -- fn runs as it is: one look at torch's current stream per call."""
+    @functools.wraps(fn)
+    def on_stream(self, *args, **kw):
+        import torch
+
+        if self.stream is None or torch.cuda.current_stream(self.device).cuda_stream == self._stream_ptr:
+            return fn(self, *args, **kw)
+        with torch.cuda.stream(self.stream):
+            return fn(self, *args, **kw)
+
+    on_stream.on_stream = True
+    return on_stream
+
+
+class _StaticOrBound:
+    """fn(ctx_or_None, ...) as a method that may also be called on the class, as the static method it once was: ctx is then None"""
+
+    def __init__(self, fn):
+        self.fn = fn
+        functools.update_wrapper(self, fn)
+
+    def __get__(self, obj, cls=None):
+        return functools.partial(self.fn, obj)
+
+
 class Acc:
     """Accumulator table (ampli_acc_table) living in one device buffer."""
 
@@ -83,8 +114,10 @@ class Acc:
         nbytes = lib.ampli_acc_bytes(self.P)
         dev = device if device is not None else ctx.device
         if buf is None:
-            # over-allocate on the host so the base can be 256-byte aligned like a device allocation
-            raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
+            # over-allocate on the host so the base can be 256-byte aligned like a device allocation; a device table comes from the pool
+            # of the context's stream
+            with (torch.cuda.stream(ctx.stream) if ctx is not None and device is None and ctx.stream is not None else contextlib.nullcontext()):
+                raw = torch.empty(nbytes + 256, dtype=torch.uint8, device=dev)
             off = (-raw.data_ptr()) % 256
             buf = raw[off: off + nbytes]
         self.buf = buf
@@ -129,6 +162,22 @@ class ErrorTable:
 
 
 class Context:
+    """One device, one stream, and every entry point of libamplisolve_hip.so as a method.
+
+    The stream contract.  The context's stream is torch's current stream at the time the context is created
+    (`with torch.cuda.stream(s): ctx = Context(0)`); Context.stream is that torch.cuda.Stream.
+      * Every device operation a method causes is ordered on the context's stream, whatever torch's current stream is when the method
+        is called: the kernels, the fills of outputs that are added to, the uploads of host arrays and the readbacks.
+      * Tensors a method returns are valid in that stream's order (and come from that stream's pool of torch's caching allocator): use
+        them under torch.cuda.stream(ctx.stream), or after ctx.sync(), or make the other stream wait on an event of this one.
+      * A method that returns host values (flags, pack16 / pack24's fits, read_calls, read_loo_calls, n_calls_total, the limit and power
+        statistics) synchronises that stream and no other.  acc_merge synchronises it too (include/amplisolve_hip.h).
+    Tensors the caller brings are read and written in the same order: what fills them has to be ordered before the call on the
+    context's stream.  The setters, getters, event and graph handles cause no device operation of torch's and are not wrapped.
+    With own_stream=True the kernels run on a stream of the library's own (hipStreamNonBlocking) and Context.stream is None: torch's
+    part of a method -- allocations, fills, uploads, readbacks -- stays on torch's current stream, and ordering the two is the
+    caller's business (bring every output, or ctx.sync() and torch.cuda.synchronize() between the steps), as before."""
+
     def __init__(self, device: int = 0, own_stream: bool = False):
         import torch
 
@@ -151,6 +200,10 @@ class Context:
             raise AmpliError(f"ampli_ctx_create: {self.lib.ampli_strerror(rc).decode()}")
         self.h = h
         self.own_stream = own_stream
+        # the context's stream as torch knows it: the caller's torch.cuda.Stream.  A context that owns its stream (own_stream=True) has
+        # none: its methods' torch operations stay on torch's current stream, as they always were ("left out")
+        self._stream_ptr = int(self.lib.ampli_stream(self.h) or 0)
+        self.stream = None if own_stream else torch.cuda.current_stream(self.device)
 
     def close(self):
         if getattr(self, "h", None):
@@ -180,6 +233,21 @@ class Context:
             t = (torch.zeros if zero else torch.empty)(tuple(shape), dtype=dtype, device=self.device)
         assert _ok(t, dtype, shape)
         return t
+
+    def _levels(self, levels):
+        """allele-fraction levels as float32 on the device, or None without any.  Uploaded once per distinct set: an upload from pageable
+        host memory waits for everything enqueued on the stream, which would make detection_limits / detection_power synchronous."""
+        import torch
+
+        key = tuple(float(x) for x in levels)
+        if not key:
+            return None
+        cache = self.__dict__.setdefault("_level_sets", {})
+        if key not in cache:
+            if len(cache) >= 64:
+                cache.clear()
+            cache[key] = torch.tensor(key, dtype=torch.float32, device=self.device)
+        return cache[key]
 
     def _csr(self, off, ent, max_len: int, bound: int):
         """Position lists as a CSR on the device: (off int32 [n + 1], ent int32 [W] -- both read as uint32 --, W).  Host arrays are
@@ -441,7 +509,7 @@ class Context:
 
         n, R = rec.n_samples, P + rec.E
         d = self.device
-        lv = torch.tensor([float(x) for x in levels], dtype=torch.float32, device=d) if len(levels) else None
+        lv = self._levels(levels)
         min_reads = torch.empty((n, R, 4, 2), dtype=torch.int32, device=d)
         status = torch.empty((n, R, 4), dtype=torch.uint8, device=d)
         if counts is None:
@@ -467,7 +535,7 @@ class Context:
 
         n, R = rec.n_samples, P + rec.E
         d = self.device
-        lv = torch.tensor([float(x) for x in levels], dtype=torch.float32, device=d) if len(levels) else None
+        lv = self._levels(levels)
         power = torch.empty((n, R, 4, len(levels)), dtype=torch.float32, device=d) if want_power else None
         lod = torch.empty((n, R, 4), dtype=torch.float32, device=d) if want_lod else None
         if counts is None:
@@ -1160,9 +1228,12 @@ class Context:
                                                     mode, _ptr(call_mask), _ptr(calls_buf), capacity, _ptr(n_calls), _ptr(q), _ptr(af)))
         return dict(call_mask=call_mask, q=q, af=af, calls_buf=calls_buf, n_calls=n_calls, capacity=capacity)
 
-    @staticmethod
-    def n_calls_total(res) -> int:
-        return int(res["n_calls"][::CALL_COUNTER_STRIDE].sum().item())
+    def _n_calls_total(self, res) -> int:
+        """the entries of a compact call list (synchronises the context's stream; Context.n_calls_total(res) on the class: torch's current stream)"""
+        read = (lambda self, res: int(res["n_calls"][::CALL_COUNTER_STRIDE].sum().item()))
+        return read(None, res) if self is None else _on_stream(read)(self, res)
+
+    n_calls_total = _StaticOrBound(_n_calls_total)
 
     def read_calls(self, res) -> list[dict]:
         """Copy the compact call list to the host, sorted into the reference's emission order."""
@@ -1217,3 +1288,20 @@ class Context:
         out = torch.empty((P,), dtype=torch.uint8, device=self.device)
         self._check(self.lib.ampli_synth_ref(self.h, _ptr(out), P, seed))
         return out
+
+
+# The stream contract in one place: every method that allocates, fills, uploads or reads back with torch runs under the context's
+# stream.  Left as they are: what touches no tensor (setters, getters, events, graph handles, sync) and what only wraps pointers;
+# n_calls_total places itself.  Plain functions only: anything else that is added to the class (a staticmethod, a property) has to be
+# placed by hand, and says so here.
+_PLAIN = {"close", "sync", "records", "dilution_records", "pack", "set_record_layout", "set_tuning", "last_reduce_kernel", "graph_begin", "graph_end",
+          "graph_launch", "graph_destroy", "set_async_drain", "wait_calls", "set_ranges", "ranges_concurrent", "ranges_join", "range_record",
+          "set_reduce_compact", "set_slice_format", "set_poisson_tuning", "set_queue_items", "flags", "event", "record", "elapsed_ms", "limit_stats",
+          "power_stats", "last_spectrum_segments", "fdr_workspace_bytes", "set_slice_group", "slice_len", "regions"}
+for _name, _fn in list(vars(Context).items()):
+    if _name.startswith("__") or _name in ("LAYOUTS", "n_calls_total"):
+        continue
+    assert inspect.isfunction(_fn), f"Context.{_name} is no plain function: place it on the context's stream by hand"
+    if _name not in _PLAIN and (not _name.startswith("_") or _name == "_read_list"):
+        setattr(Context, _name, _on_stream(_fn))
+del _name, _fn

@@ -368,6 +368,7 @@ int ampli_error_sums_inorder(ampli_ctx *ctx, const ampli_records *recs, int64_t 
  * samples) into d_dst (may alias parts[0]).  Sums add; the germ-max triple
  * composes as the reference's sequential state machine would.  This is the
  * local half of the multi-GPU merge and of in-GPU sample splitting.
+ * Synchronises the stream: the list of the parts' pointers is uploaded from the caller's stack.
  */
 int ampli_acc_merge(ampli_ctx *ctx, const ampli_acc_table *d_dst, const ampli_acc_table *d_parts,
                     int32_t nparts);
