@@ -6,3 +6,4 @@ This Python package is the thin test / bench harness over those C ABIs.
 """
 from ._lib import AmpliError, AmpliNoDevice, hip_lib, host_lib  # noqa: F401
 from .api import Context, ErrorTable, NT  # noqa: F401
+from .phase import phase_score, read_phase  # noqa: F401

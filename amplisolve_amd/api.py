@@ -37,6 +37,7 @@ from ._lib import (CONSTANTS, AccTable, AllelicParams, AmpliError, AmpliNoDevice
 #                                          8 + pair, AI_NO_PAIR: none), the untested score, the five sums of a region and the verdicts
 #   INDEL_LEN_BINS                         indel_count: the length bins per (position, kind) of its second output
 #   EVIDENCE_*                             read_evidence: the metrics per (position, nt), their indices and the bins of each
+#   PHASE_*                                phase.read_phase: the partners of a key, the states of a read at a key and the state OTHER
 globals().update({name[len("AMPLI_"):]: value for name, value in CONSTANTS.items()})
 
 # Python's own

@@ -29,7 +29,7 @@ HOST_LIB = os.path.join(LIB, "libamplisolve_host.so")
 # (the timed step itself) and the first lines of each file.
 HIP_SOURCES = ["ampli_kernels.hip", "ampli_exchange.hip", "ampli_loo.hip", "ampli_limits.hip", "ampli_dispersion.hip", "ampli_concordance.hip", "ampli_contamination.hip",
                "ampli_amplicon.hip", "ampli_spectrum.hip", "ampli_exceedance.hip", "ampli_overdispersion.hip", "ampli_paired.hip", "ampli_fdr.hip", "ampli_dilution.hip", "ampli_monitor.hip", "ampli_allelic.hip", "ampli_fraction.hip", "ampli_aux.hip",
-               "ampli_runtime.hip", "ampli_pileup.hip", "ampli_indel.hip", "ampli_amplicon_count.hip", "ampli_evidence.hip", "ampli_comm.hip"]
+               "ampli_runtime.hip", "ampli_pileup.hip", "ampli_indel.hip", "ampli_amplicon_count.hip", "ampli_evidence.hip", "ampli_phase.hip", "ampli_comm.hip"]
 HIP_HEADERS = ["ampli_bam.h", "ampli_device.h", "ampli_internal.h", "ampli_math.h", "ampli_synth.h"]
 # the public headers; amplisolve_types.h is included by the other two and by csrc/ampli_math.h, so both libraries depend on it
 INCLUDE = os.path.join(ROOT, "include")
@@ -47,7 +47,7 @@ EXECUTABLES = (("AmpliSolveErrorEstimation", "ee_main.cpp"), ("AmpliSolveVariant
                ("AmpliSolveInSilicoDilution", "di_main.cpp"), ("AmpliSolveVariantMonitoring", "mo_main.cpp"),
                ("AmpliSolveAllelicImbalance", "ai_main.cpp"), ("AmpliSolveTumourFraction", "tf_main.cpp"),
                ("computeIndelCounts", "ci_main.cpp"), ("computeAmpliconCounts", "ca_main.cpp"),
-               ("computeReadEvidence", "re_main.cpp"))
+               ("computeReadEvidence", "re_main.cpp"), ("computePhasing", "ph_main.cpp"))
 OBJ = os.path.join(PKG, "build")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-shared", "-std=c++17", "-ffp-contract=off"]
 CXX_FLAGS = ["-O2", "-fPIC", "-std=c++17", "-ffp-contract=off", "-Wall", "-pthread"]

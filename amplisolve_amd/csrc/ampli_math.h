@@ -1950,4 +1950,59 @@ AMPLI_FN void ampli_ev_cell(const int32_t *a, const int32_t *r, int64_t *o_int, 
     *o_z2 = D < 0 ? -z2 : z2;
 }
 
+// ---------------------------------------------------------------------------
+// Read-level phasing (the definition is the contract comment of ampli_phase_score, restated in tests/phase_model.py): do two
+// listed variants share their reads?  One pair = one 5 x 5 cell of ampli_pileup_phase's joint table, rows the state at key i, columns the
+// state at key j.  The four corners (ref / alt at i) x (ref / alt at j) are the 2 x 2 table of the exact test above: the score is
+// ampli_pair_score(n_aa, n_aa + n_ar, n_ra, n_ra + n_rr), positive when alt at j is commoner among the reads that show alt at i.
+// ---------------------------------------------------------------------------
+// is the pair tested?  pair_cell = i K + k inside [0, P K) with i + 1 + k < P; four nts in 0 .. 3; ref != alt on both sides
+AMPLI_FN int ampli_ph_tested(int64_t pair_cell, int64_t P, int ref_i, int alt_i, int ref_j, int alt_j)
+{
+    if (pair_cell < 0 || pair_cell >= P * AMPLI_PHASE_PARTNERS) return 0;
+    const int64_t i = pair_cell / AMPLI_PHASE_PARTNERS, k = pair_cell - i * AMPLI_PHASE_PARTNERS;
+    if (i + 1 + k >= P) return 0;
+    if ((unsigned)ref_i > 3u || (unsigned)alt_i > 3u || (unsigned)ref_j > 3u || (unsigned)alt_j > 3u) return 0;
+    return ref_i != alt_i && ref_j != alt_j;
+}
+
+// the six counts of a tested pair's cell [5][5]: rr, ra, ar, aa (the first letter is the state at key i), joint, other
+AMPLI_FN void ampli_ph_counts(const int32_t *cell, int ref_i, int alt_i, int ref_j, int alt_j, int64_t *v)
+{
+    int64_t joint = 0;
+    for (int c = 0; c < AMPLI_PHASE_STATES * AMPLI_PHASE_STATES; ++c) joint += cell[c];
+    v[0] = cell[ref_i * AMPLI_PHASE_STATES + ref_j];
+    v[1] = cell[ref_i * AMPLI_PHASE_STATES + alt_j];
+    v[2] = cell[alt_i * AMPLI_PHASE_STATES + ref_j];
+    v[3] = cell[alt_i * AMPLI_PHASE_STATES + alt_j];
+    v[4] = joint;
+    v[5] = joint - (v[0] + v[1] + v[2] + v[3]);
+}
+
+// the class: bit 0 = aa, bit 1 = ar, bit 2 = ra present.  A group x is present iff x >= min_alt and 100 x >= min_share m, m the reads
+// that show an alt at either key; compared in int64
+AMPLI_FN int32_t ampli_ph_class(int64_t n_ra, int64_t n_ar, int64_t n_aa, int32_t min_alt, int32_t min_share)
+{
+    const int64_t m = n_aa + n_ar + n_ra;
+    const int aa = n_aa >= min_alt && 100 * n_aa >= (int64_t)min_share * m;
+    const int ar = n_ar >= min_alt && 100 * n_ar >= (int64_t)min_share * m;
+    const int ra = n_ra >= min_alt && 100 * n_ra >= (int64_t)min_share * m;
+    return (int32_t)(aa | (ar << 1) | (ra << 2));
+}
+
+// the whole of one pair (host, tests): v [6], the score, the class.  An untested pair: six -1, score 0, class -1
+AMPLI_FN void ampli_ph_cell(const int32_t *table, int64_t P, int64_t pair_cell, const int8_t *nt, int32_t min_alt, int32_t min_share, int64_t *v, float *score,
+                            int32_t *cls)
+{
+    if (!ampli_ph_tested(pair_cell, P, nt[0], nt[1], nt[2], nt[3])) {
+        for (int c = 0; c < 6; ++c) v[c] = -1;
+        *score = 0.0f;
+        *cls = -1;
+        return;
+    }
+    ampli_ph_counts(table + pair_cell * (AMPLI_PHASE_STATES * AMPLI_PHASE_STATES), nt[0], nt[1], nt[2], nt[3], v);
+    *score = ampli_pair_score(v[3], v[3] + v[2], v[1], v[1] + v[0], (int32_t *)0);
+    *cls = ampli_ph_class(v[1], v[2], v[3], min_alt, min_share);
+}
+
 #endif

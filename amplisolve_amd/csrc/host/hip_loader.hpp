@@ -23,6 +23,7 @@
     X(hetsite_reference_records) X(allelic_site_records) X(allelic_region_sums) X(fraction_records)                               \
     X(event_create) X(event_destroy) X(event_record) X(event_sync) X(pileup_count) X(pileup_indel_count) X(comm_create)           \
     X(comm_destroy) X(pileup_amplicon_count) X(amplicon_layers) X(pileup_evidence) X(evidence_score)                              \
+    X(pileup_phase) X(phase_score)                                                                                                \
     X(comm_reduce_scatter_f64) X(comm_all_to_all_f32) X(comm_all_gather_bytes) X(comm_all_reduce_max_i32)                         \
     X(comm_exclusive_sum_i64) X(comm_barrier)
 

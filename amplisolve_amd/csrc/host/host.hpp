@@ -281,6 +281,41 @@ struct EvidenceListed {
 int64_t write_evidence_files(const std::string &out_dir, const std::string &name, const std::vector<EvidenceListed> &listed, const int32_t *hist /* [L][4][3][64] */,
                              const int64_t *v_int /* [L][3][3] */, const int32_t *v_med /* [L][3][2] */, const double *v_z2 /* [L][3] */,
                              const int8_t *ref_nt, const int8_t *alt_used /* [L] */, int64_t min_alt, double z_min);
+// ---- run_ph.cpp ----
+// computePhasing: one BAM file and a list of calls -> <out_dir>/<name>.PHASE.txt + <name>.PHASE.MNV.txt.  The numbers as the
+// command line gives them.
+struct PhArgs {
+    std::string vcf, bam, out_dir;
+    std::string threads = "4", mbq = "20", mrq = "20", min_alt = "4", min_share = "10", q_min = "13", max_dist = "200";
+    int64_t *stats = nullptr; // optional [6]: records, reads kept, reads covering two keys, cells incremented, pairs written, MNV lines written
+    std::string *error = nullptr;
+};
+int run_compute_phasing(const PhArgs &a);
+// the score of ampli_phase_score on the host (ampli_ph_* of csrc/ampli_math.h): the same table, the same integers
+void phase_score_host(const int32_t *table, int64_t P, const int64_t *pair_cell, const int8_t *pair_nt, int64_t Q, int32_t min_alt, int32_t min_share, int64_t *o_int,
+                      float *o_score, int32_t *o_class);
+// one listed line and its index into the sorted keys (-1: unknown chromosome); one pair of listed lines a, b (indices into the list)
+struct PhaseListed {
+    std::string chrom, ref, alt;
+    int64_t pos = 0, key_index = -1;
+};
+struct PhasePair {
+    int64_t a = 0, b = 0;
+    int64_t slot = -1; // its index among the formed pairs (the rows of the score's outputs), -1: NOT_FORMED
+    std::string verdict;
+    int64_t n_aa = 0;
+};
+// every two listed lines a, b with a key on one chromosome and 0 < pos_b - pos_a <= max_dist, in the order (key of a, key of b, list order);
+// pair_cell / pair_nt: the formed ones (key indices at most AMPLI_PHASE_PARTNERS apart) as ampli_phase_score takes them
+std::vector<PhasePair> phase_pairs(const std::vector<PhaseListed> &listed, int64_t max_dist, std::vector<int64_t> &pair_cell, std::vector<int8_t> &pair_nt);
+// the verdict of a formed pair from its class and score
+const char *phase_verdict(int32_t cls, float score, double q_min);
+// chains of 2 or 3 lines at consecutive positions, every two of them CIS, grown greedily in (key, list) order; a line is in at most one
+std::vector<std::vector<int64_t>> phase_chains(const std::vector<PhaseListed> &listed, const std::vector<PhasePair> &pairs);
+// sets the pairs' verdicts and writes the command's two files from host arrays alone (no device: tools/phase_sanitize.cpp); returns the
+// lines written to <name>.PHASE.txt, *mnv (optional) those of <name>.PHASE.MNV.txt; both files under temporary names, renamed at the end
+int64_t write_phase_files(const std::string &out_dir, const std::string &name, const std::vector<PhaseListed> &listed, std::vector<PhasePair> &pairs,
+                          const int64_t *v_int /* [Q][6] */, const float *v_score /* [Q] */, const int32_t *v_class /* [Q] */, double q_min, int64_t *mnv);
 // BGZF + BAM structure only (no GPU): stats[4] = alignment records, uncompressed bytes, references, malformed records
 void bam_scan(const std::string &bam, int n_threads, int64_t stats[4]);
 // ---- pipeline.cpp ----

@@ -293,6 +293,81 @@ extern "C" int ampli_host_evidence_score(const int32_t *hist, int64_t P, const i
     return 0;
 }
 
+extern "C" int ampli_host_compute_phasing(const char *vcf, const char *bam, const char *out_dir, int32_t threads, int32_t mbq, int32_t mrq, int32_t min_alt,
+                                          int32_t min_share, double q_min, int32_t max_dist, int64_t *stats)
+{
+    if (!vcf || !bam || !out_dir) { g_err = "vcf, bam and out_dir are required"; return AMPLI_E_INVALID; }
+    PhArgs a;
+    a.vcf = vcf; a.bam = bam; a.out_dir = out_dir;
+    a.threads = std::to_string(threads); a.mbq = std::to_string(mbq); a.mrq = std::to_string(mrq); a.min_alt = std::to_string(min_alt);
+    a.min_share = std::to_string(min_share); a.max_dist = std::to_string(max_dist);
+    char q[40];
+    snprintf(q, sizeof q, "%.17g", q_min);
+    a.q_min = q;
+    a.stats = stats;
+    std::string err;
+    a.error = &err;
+    const int rc = run_compute_phasing(a);
+    if (rc) g_err = err;
+    return rc;
+}
+
+extern "C" int ampli_host_phase_score(const int32_t *table, int64_t P, const int64_t *pair_cell, const int8_t *pair_nt, int64_t Q, int32_t min_alt, int32_t min_share,
+                                      int64_t *out_int, float *out_score, int32_t *out_class)
+{
+    if (!table || P < 0 || !pair_cell || !pair_nt || Q < 0 || min_alt < 1 || min_share < 0 || min_share > 100 || !out_int || !out_score || !out_class) {
+        g_err = "bad argument";
+        return AMPLI_E_INVALID;
+    }
+    phase_score_host(table, P, pair_cell, pair_nt, Q, min_alt, min_share, out_int, out_score, out_class);
+    return 0;
+}
+
+extern "C" int ampli_host_phase_files(const char *list, const int64_t *key_index, int64_t L, const int32_t *table, int64_t P, int32_t min_alt, int32_t min_share,
+                                      double q_min, int64_t max_dist, const char *out_dir, const char *name, int64_t *stats)
+{
+    if (!list || !key_index || L < 0 || !table || P < 0 || min_alt < 1 || min_share < 0 || min_share > 100 || !(q_min > 0.0) || max_dist < 1 || !out_dir || !name) {
+        g_err = "bad argument";
+        return AMPLI_E_INVALID;
+    }
+    try {
+        std::vector<PhaseListed> listed;
+        for (const char *p = list; *p && (int64_t)listed.size() < L;) { // chr \t pos \t ref \t alt \n
+            const char *e = strchr(p, '\n');
+            const std::string line(p, e ? (size_t)(e - p) : strlen(p));
+            p = e ? e + 1 : p + strlen(p);
+            PhaseListed v;
+            size_t at = 0;
+            std::string col[4];
+            for (int c = 0; c < 4; ++c) {
+                const size_t tab = line.find('\t', at);
+                col[c] = line.substr(at, tab == std::string::npos ? std::string::npos : tab - at);
+                at = tab == std::string::npos ? line.size() : tab + 1;
+            }
+            v.chrom = col[0]; v.pos = atoll(col[1].c_str()); v.ref = col[2]; v.alt = col[3];
+            v.key_index = key_index[listed.size()];
+            if (v.key_index >= P) throw Error{AMPLI_E_INVALID, "a key index beyond the table"};
+            listed.push_back(v);
+        }
+        if ((int64_t)listed.size() != L) throw Error{AMPLI_E_INVALID, "fewer lines than L"};
+        std::vector<int64_t> pair_cell;
+        std::vector<int8_t> pair_nt;
+        std::vector<PhasePair> pairs = phase_pairs(listed, max_dist, pair_cell, pair_nt);
+        const size_t Q = pair_cell.size();
+        std::vector<int64_t> v_int(Q * 6 + 1);
+        std::vector<float> v_score(Q + 1);
+        std::vector<int32_t> v_class(Q + 1);
+        phase_score_host(table, P, pair_cell.data(), pair_nt.data(), (int64_t)Q, min_alt, min_share, v_int.data(), v_score.data(), v_class.data());
+        int64_t mnv = 0;
+        const int64_t written = write_phase_files(out_dir, name, listed, pairs, v_int.data(), v_score.data(), v_class.data(), q_min, &mnv);
+        if (stats) { stats[0] = written; stats[1] = (int64_t)Q; stats[2] = mnv; }
+        return 0;
+    } catch (const Error &e) {
+        g_err = e.msg;
+        return e.code ? e.code : -1;
+    }
+}
+
 extern "C" int64_t ampli_host_amplicon_arrays(const char *bed, const char *ref_names, int64_t cap, uint64_t *lo, uint64_t *hi, uint64_t *reach, int64_t *amp_off,
                                               int32_t *row_of, int64_t *n_rows)
 {

@@ -184,6 +184,12 @@ extern "C" {
  *   (C32) evidence scores: ampli_evidence_score FULLY OVERWRITES d_int [P][3][3], d_med [P][3][2], d_z2 [P][3] and d_alt_used [P] with
  *        plain stores (one lane owns a cell: nothing is cleared, nothing is added to), untested cells included.  Nothing else is written,
  *        d_hist, d_ref_nt and d_alt_nt included.
+ *   (C33) read-level phasing (tests/test_gpu_phase_contracts.py): ampli_pileup_phase ADDS TO d_table inside [0, P) keys and, when it is
+ *        not NULL, to the three words of d_stats (zero them for the counts of one call; batches of one file add up).  A cell (i, k) with
+ *        i + 1 + k >= P is never written.  Nothing else is written.
+ *   (C34) phase scores: ampli_phase_score FULLY OVERWRITES d_int [Q][6], d_score [Q] and d_class [Q] with plain stores (one lane owns a
+ *        pair: nothing is cleared, nothing is added to), untested pairs included (-1, 0, -1).  Nothing else is written, d_table,
+ *        d_pair_cell and d_pair_nt included; d_table is read only at the cell of a tested pair.
  */
 typedef struct ampli_ctx ampli_ctx;
 
@@ -1349,6 +1355,50 @@ int ampli_pileup_evidence(ampli_ctx *ctx, const uint8_t *d_bam, const uint64_t *
  */
 int ampli_evidence_score(ampli_ctx *ctx, const int32_t *d_hist, int64_t P, const int8_t *d_ref_nt, const int8_t *d_alt_nt, int64_t *d_int,
                          int32_t *d_med, double *d_z2, int8_t *d_alt_used);
+
+/*
+ * Read-level phasing over the same alignment records: which alleles a read shows at two listed positions at once.  The stream
+ * contract is ampli_pileup_evidence's (d_bam, d_rec_off, d_keys ascending; the records are read straight from global memory), and so are
+ * the kept-read filter and the effective operations.  The context is the LAST parameter of this entry point and of ampli_phase_score.
+ *
+ * Covered key.  A key is covered by a kept read iff it is on the read's reference and its position lies in [pos + 1, pos + L], L the summed
+ * length of the read's effective M = X D N operations.  The keys a read covers are a contiguous range of the list.
+ * State of a read at a covered key.  0 .. 3 = A C G T where the key falls on an M / = / X column whose base is A/C/G/T with quality >= mbq:
+ * exactly a counted column of ampli_pileup_evidence.  AMPLI_PHASE_OTHER (4) otherwise: a base below mbq, a non-ACGT base, a key inside a
+ * D or an N.
+ * Output.  d_table is int32 [P][K][5][5], K = AMPLI_PHASE_PARTNERS, in the order (key i, partner k, state at key i, state at key
+ * i + 1 + k), and is ACCUMULATED into.  Every kept read adds 1 to d_table[i][k][s_i][s_j] for every two keys i < j = i + 1 + k <= i + K that
+ * it both covers.  Cells with i + 1 + k >= P are never written.
+ * d_stats (optional, may be NULL) uint64 [3], accumulated: reads kept, reads covering at least two keys, cells incremented.
+ * Invariant.  Take a pair cell (i, k) where every kept read that covers one of the two keys covers both.  Then for s <= 3 the sum over t of
+ * d_table[i][k][s][t] equals counts[i][s] of ampli_pileup_count (its slots 0 .. 3: both strands pooled) over the same records, mbq and
+ * mrq, and the sum over s of d_table[i][k][s][t] equals counts[j][t] for t <= 3.
+ * Bad arguments and alignments (8 bytes: d_rec_off, d_keys, d_stats; 4 bytes: d_table) give AMPLI_E_INVALID ("bad argument"), more than
+ * 2^31 - 1 read groups AMPLI_E_RANGE.  n_reads == 0 or P == 0 is a no-op that returns AMPLI_OK.
+ * Stated limits.  Records are counted, not fragments: overlapping mates count twice, as in computeCounts.  Only the next K listed keys are
+ * partners: pairs further apart in the list are never counted.  Strands are pooled.  An insertion has no key.
+ */
+int ampli_pileup_phase(const uint8_t *d_bam, const uint64_t *d_rec_off, int64_t n_reads, const uint64_t *d_keys, int64_t P, int32_t mbq, int32_t mrq,
+                       int32_t *d_table, uint64_t *d_stats, ampli_ctx *ctx);
+/*
+ * The pair score over the joint table: are the alts of two listed keys on the same reads?  The alleles are chosen here, not in
+ * the walk.  d_pair_cell: int64 [Q], each i K + k (the pair of key i and key j = i + 1 + k); d_pair_nt: int8 [Q][4], each ref_i, alt_i,
+ * ref_j, alt_j in 0 .. 3 = A C G T.  min_alt >= 1; min_share in 0 .. 100 (per cent).  The context is the LAST parameter.
+ * Counts, from the pair's 5 x 5 cell (the first letter is the state at key i): n_rr, n_ra, n_ar, n_aa its four corners; n_joint the sum
+ * of all 25; n_other = n_joint - the four corners.
+ * Score = ampli_pair_score_records' exact conditional test of the 2 x 2 table with k_a = n_aa, d_a = n_aa + n_ar, k_b = n_ra,
+ * d_b = n_ra + n_rr: positive when alt at j is commoner among the reads that show alt at i -- the two are linked in cis --, negative when
+ * it is rarer, +0 without a difference.
+ * Class, a bit mask.  With m = n_aa + n_ar + n_ra a group x is present iff x >= min_alt and 100 x >= min_share m, compared in int64.
+ * Bit 0: aa, bit 1: ar, bit 2: ra.
+ * Untested pairs: a pair cell outside [0, P K) or with i + 1 + k >= P; any nt outside 0 .. 3; ref == alt on either side.  Such a pair gets
+ * class -1 and score 0, and its counts are written as -1; d_table is not read for it.
+ * Outputs, each cell with one owner and overwritten: d_int int64 [Q][6] = rr, ra, ar, aa, joint, other; d_score float [Q]; d_class int32
+ * [Q].  A null pointer, P < 0, Q < 0, a min_alt or min_share outside its range or a misaligned pointer (8 bytes: d_pair_cell, d_int; 4 bytes:
+ * d_table, d_score, d_class) gives AMPLI_E_INVALID ("bad argument"), more than 2^31 - 1 groups of 256 pairs AMPLI_E_RANGE.  Q == 0 is a no-op.
+ */
+int ampli_phase_score(const int32_t *d_table, int64_t P, const int64_t *d_pair_cell, const int8_t *d_pair_nt, int64_t Q, int32_t min_alt, int32_t min_share,
+                      int64_t *d_int, float *d_score, int32_t *d_class, ampli_ctx *ctx);
 
 /* tuning knobs.  reduce_sample_splits: 0 = automatic.  reduce_general: 0 = the fast error_reduce kernel
  * (valid while every strand depth is < 2^22; it raises AMPLI_FLAG_RERUN_GENERAL otherwise), 1 = the literal

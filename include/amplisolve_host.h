@@ -189,6 +189,26 @@ int ampli_host_compute_read_evidence(const char *vcf, const char *bam, const cha
  * for bit.  Returns 0, or AMPLI_E_INVALID for a null pointer or P < 0. */
 int ampli_host_evidence_score(const int32_t *hist, int64_t P, const int8_t *ref_nt, const int8_t *alt_nt, int64_t *out_int, int32_t *out_med,
                               double *out_z2, int8_t *alt_used);
+/* computePhasing: the same walk with ampli_pileup_phase per batch and one ampli_phase_score over every formed pair of listed lines ->
+ * <out_dir>/<bam name>.PHASE.txt (chr posA refA altA posB refB altB n_joint n_rr n_ra n_ar n_aa n_other exp_aa score verdict, one line per two
+ * listed lines on one chromosome at most max_dist apart) and <out_dir>/<bam name>.PHASE.MNV.txt (chains of 2 or 3 consecutive positions that are
+ * CIS in pairs).  vcf: the calls (chr pos id ref alt).  min_alt >= 1 and min_share in 0 .. 100: when a group of reads is present; q_min > 0: the
+ * score CIS and NESTED_* need; max_dist >= 1.  Bad numbers and unreadable inputs are refused before the device is opened; a failure leaves no
+ * output file behind.  stats (optional) [6]: alignment records, reads kept, reads covering at least two keys, cells incremented, pairs written,
+ * chains written. */
+int ampli_host_compute_phasing(const char *vcf, const char *bam, const char *out_dir, int32_t threads, int32_t mbq, int32_t mrq, int32_t min_alt,
+                               int32_t min_share, double q_min, int32_t max_dist, int64_t *stats);
+/* ampli_phase_score on the host (no GPU): the same table -- int32 [P][8][5][5] --, pair_cell int64 [Q] and pair_nt int8 [Q][4] through the same
+ * arithmetic (ampli_ph_* of csrc/ampli_math.h): out_int [Q][6] and out_class [Q] equal the device's, out_score [Q] to the rounding of the two
+ * math libraries.  Returns 0, or AMPLI_E_INVALID for a null pointer, P < 0, Q < 0, min_alt < 1 or min_share outside 0 .. 100. */
+int ampli_host_phase_score(const int32_t *table, int64_t P, const int64_t *pair_cell, const int8_t *pair_nt, int64_t Q, int32_t min_alt, int32_t min_share,
+                           int64_t *out_int, float *out_score, int32_t *out_class);
+/* What computePhasing does behind its walk, from host arrays (no GPU): the pairs of the L listed lines (list: "chr \t pos \t ref \t alt \n" per
+ * line; key_index [L]: each line's index into the table's keys, -1 for an unknown chromosome), ampli_host_phase_score over the formed ones, the
+ * verdicts, the chains, and the two files <out_dir>/<name>.PHASE.txt and <name>.PHASE.MNV.txt.  stats (optional) [3]: pairs written, pairs
+ * scored, chains written.  Returns 0 or a negative code. */
+int ampli_host_phase_files(const char *list, const int64_t *key_index, int64_t L, const int32_t *table, int64_t P, int32_t min_alt, int32_t min_share,
+                           double q_min, int64_t max_dist, const char *out_dir, const char *name, int64_t *stats);
 /* the container only (no GPU): stats[4] = alignment records, uncompressed bytes, reference sequences, malformed records (complete
  * records whose CIGAR does not add up to their l_seq or whose fields overrun their block: counted and skipped).  Bytes behind the
  * last complete record -- a truncated or desynchronised stream -- are an error (AMPLI_E_INVALID), not a count: since round 3 the call

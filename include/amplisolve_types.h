@@ -230,4 +230,12 @@ typedef struct ampli_fraction_params {
 #define AMPLI_EVIDENCE_MQ 1
 #define AMPLI_EVIDENCE_POS 2
 
+/* Read-level phasing from alignments: ampli_pileup_phase's joint table is int32 [P][AMPLI_PHASE_PARTNERS][AMPLI_PHASE_STATES]
+ * [AMPLI_PHASE_STATES] in the order (key i, partner k, state at key i, state at key i + 1 + k): a key is paired with the next
+ * AMPLI_PHASE_PARTNERS listed keys; a read's state at a key it covers is 0 .. 3 = A C G T for a counted column and AMPLI_PHASE_OTHER for
+ * everything else (a base below mbq, a non-ACGT base, a key inside a deletion or a reference skip). */
+#define AMPLI_PHASE_PARTNERS 8
+#define AMPLI_PHASE_STATES 5
+#define AMPLI_PHASE_OTHER 4
+
 #endif /* AMPLISOLVE_TYPES_H */
